@@ -22,13 +22,28 @@ own operands and its own output, every rank its own sets), so that by the time a
 least 1 GiB of other bytes has passed and nothing of it is left in the 256 MiB Infinity Cache.  `value`,
 `ms_per_step` and `roofline.frac` are therefore ALL-HBM figures at every N: every algorithmic byte of a timed
 step crosses HBM.  The loop of rounds 1-3 — one set, K steps, its 256 MiB u8 operand (at N = 8: both operands
-of a shard) served on-die from the second step on — is measured after the timed region on every rank and
+of a shard) served on-die from the second step on — is measured with --full after the timed region on every rank and
 reported as `roofline.cache_resident_loop` (and per rank in `roofline.per_gpu[*].cache_resident_loop`).
 
-Rank 0 prints ONE JSON line: BASELINE.json's metric (Gcells/s, whole job), a
+Rank 0 prints ONE JSON line: BASELINE.json's metric (Gcells/s, whole job) and a
 `roofline` object for the dominant kernel (HIP-event timed, algorithmic bytes =
-11 B/cell) and, at N=1, a `cpu_baseline` object: the oracle's reference-shaped
-port of the same operation timed on this box's host cores on a bounded sample.
+11 B/cell).  A plain run does only that: set up, clock ramp and warm-up, the K
+timed steps, the line.  With --full the run also checks and measures what lies
+beside the headline, all after the timed region: the bit-exact check of the
+timed output (`verified`), the one-set loop (`roofline.cache_resident_loop`),
+the reference streams (`roofline.reference_streams`) and, at N=1, a
+`cpu_baseline` object: the oracle's reference-shaped port of the same operation
+timed on this box's host cores on a bounded sample.
+
+  python bench.py --gpus 1 --steps 200 --warmup 20 --full
+  python bench.py --gpus 1 --steps 200 --warmup 20 --dump-outputs DIR
+
+--dump-outputs DIR writes what the last timed step computed to DIR/<name>.npy
+(float64, masks float32; at most 64 MB in all: a larger output is sampled in
+fixed, seeded blocks of cells whose first cells go to DIR/<name>_index.npy).
+The inputs are seeded and the timed steps always start at the same operand set,
+so the same arguments give the same files on any build that computes the same
+cells.
 
 Other workloads (not bench lines; used for profiles/ and DESIGN.md):
   --workload masked_chain   config 3: f32 (a+b)*c with 30 % nodata masks
@@ -54,6 +69,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s)
 METRIC = "Gcells/s + HBM-GB/s roofline %, u8/u16->f64 16384^2, 1/2/4/8 GPUs"
+DUMP_BYTES = 48 << 20   # --dump-outputs: bytes of sampled cells over all files of all ranks (indices come on top, < 1 MB)
+DUMP_BLOCK = 4096       # cells per sampled block
 
 
 def parse():
@@ -100,7 +117,51 @@ def parse():
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="ec_tune_set(KEY, VALUE) before anything is launched (A/B runs for profiles/, e.g. --tune mall_mb=0); "
                          "recorded in config.tune")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also check the timed output (`verified`) and measure the one-set loop, the "
+                         "reference streams and (N = 1) the cpu_baseline; a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, masks float32; a fixed, "
+                         "seeded sample of blocks when the output exceeds the 64 MB budget)")
     return ap.parse_args()
+
+
+def dump_outputs(dirname: str, outputs: dict, first_cell: int, rank: int, world: int) -> list:
+    """Writes the arrays of `outputs` ({name: CellBuffer | Mask | numpy array}: what the last timed step left; the buffers
+    are this rank's shard, whose first cell is `first_cell` of the raster) to DIR/<name>.npy, at N > 1 as
+    DIR/<name>.rank<r>.npy.  A buffer larger than its share of DUMP_BYTES is sampled: blocks of DUMP_BLOCK cells chosen by
+    a fixed seed (the first and the last block always among them), and the raster index of each block's first cell goes
+    to DIR/<name>_index.npy.  Returns the file names written."""
+    import numpy as np
+
+    import erased_cells_hip as ec
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if world == 1 else f".rank{rank}"
+    share = DUMP_BYTES // (world * max(1, len(outputs)))
+    written = []
+    for name, arr in outputs.items():
+        if isinstance(arr, np.ndarray):
+            host, idx = arr.astype(np.float64), None
+        else:
+            n = len(arr)
+            wdt = np.float32 if isinstance(arr, ec.Mask) else np.float64
+            nblocks = -(-n // DUMP_BLOCK)
+            take = share // (DUMP_BLOCK * np.dtype(wdt).itemsize)
+            if take >= nblocks:
+                host, idx = arr.to_numpy().astype(wdt), None
+            else:
+                rng = np.random.default_rng(0x5EED0D)
+                picked = rng.choice(np.arange(1, nblocks - 1), size=max(0, take - 2), replace=False)
+                blocks = np.unique(np.concatenate([[0, nblocks - 1], picked]))
+                host = np.concatenate([arr.shard(int(b) * DUMP_BLOCK, min(DUMP_BLOCK, n - int(b) * DUMP_BLOCK)).to_numpy()
+                                       for b in blocks]).astype(wdt)
+                idx = (blocks * DUMP_BLOCK + first_cell).astype(np.float64)
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), host)
+        written.append(f"{name}{sfx}.npy")
+        if idx is not None:
+            np.save(os.path.join(dirname, f"{name}_index{sfx}.npy"), idx)
+            written.append(f"{name}_index{sfx}.npy")
+    return written
 
 
 def cpu_baseline(side: int, target_s: float) -> dict:
@@ -328,6 +389,7 @@ def main():
     S = {"stream": stream}  # the launch stream; --graph points it at the capture stream while it records
     keep = []               # every set's buffers stay alive for the whole run
     scopes = {}             # div_u8_u16: set k -> (a, b, out) for the bit-exact check of the timed output
+    outs = {}               # set k -> {name: what a caller of the step receives} for --dump-outputs
     seed_of = lambda base, k: base + 16 * k  # noqa: E731
 
     def new(ct, seed=None, lo=0.0, hi=0.0, cells=None):
@@ -356,6 +418,7 @@ def main():
             b = new(ec.UInt16, seed_of(0x5EED0002, k), 1.0, 65535.0)
             out = new(ec.Float64)
             scopes[k] = dict(a=a, b=b, out=out, n=n)
+            outs[k] = {"out": out}
             return lambda: chk(L.ec_binop(ec.DIV, ec.UInt8, a.mem.ptr, ec.UInt16, b.mem.ptr, n, out.mem.ptr, S["stream"]))
     elif args.workload == "binop":  # any pair of cell types through the same entry point (profiles/)
         lt, rt, op = names.index(args.lt), names.index(args.rt), ["add", "sub", "mul", "div"].index(args.op)
@@ -368,6 +431,7 @@ def main():
         def build(k):
             a, b = new(lt, seed_of(0x5EED0021, k), 1.0, 100.0), new(rt, seed_of(0x5EED0022, k), 1.0, 100.0)
             out = new(ec.Float64)
+            outs[k] = {"out": out}
             return lambda: chk(L.ec_binop(op, lt, a.mem.ptr, rt, b.mem.ptr, n, out.mem.ptr, S["stream"]))
     elif args.workload == "masked_chain":
         fused = args.fused
@@ -381,6 +445,7 @@ def main():
             bufs = [new(ec.Float32, seed_of(0x5EED0003 + i, k), -1000.0, 1000.0) for i in range(3)]
             masks = [new_mask(seed_of(0x5EED0013 + i, k)) for i in range(3)]
             out, m2 = new(ec.Float64), new_mask()
+            outs[k] = {"out": out, "out_mask": m2}
             if fused:
                 dt4 = (C.c_uint8 * 4)(ec.Float32, ec.Float32, ec.Float32, 0)
                 p4 = (C.c_void_p * 4)(bufs[0].mem.ptr, bufs[1].mem.ptr, bufs[2].mem.ptr, None)
@@ -409,6 +474,7 @@ def main():
         def build(k):
             nir, red = new(ec.UInt16, seed_of(0x5EED0007, k), 5000.0, 40000.0), new(red_t, seed_of(0x5EED0008, k), 5000.0, 30000.0)
             out = new(ec.Float64)
+            outs[k] = {"out": out}
             if args.fused:
                 dt4 = (C.c_uint8 * 4)(ec.UInt16, red_t, ec.UInt16, red_t)
                 p4 = (C.c_void_p * 4)(nir.mem.ptr, red.mem.ptr, nir.mem.ptr, red.mem.ptr)
@@ -453,6 +519,7 @@ def main():
         def build(k):
             nir, red, blue = (new(U16, seed_of(0x5EED0031 + i, k), 2000.0 + 3000.0 * (2 - i), 20000.0 + 10000.0 * (2 - i)) for i in range(3))
             out = new(F64)
+            outs[k] = {"out": out}
             if args.fused:
                 p3 = (C.c_void_p * 3)(nir.mem.ptr, red.mem.ptr, blue.mem.ptr)
                 keep.append(p3)
@@ -481,6 +548,7 @@ def main():
 
         def build(k):
             a = new(ec.UInt16, seed_of(0x5EED0006, k), 1.0, 65534.0)
+            outs[k] = {"min_max": keys}  # decoded to (min, max) for the dump
 
             def step():
                 chk(L.ec_min_max_keys(ec.UInt16, a.mem.ptr, None, n, keys.data_ptr(), S["stream"]))
@@ -525,6 +593,9 @@ def main():
             step()
         torch.cuda.synchronize()
         ramp += 20
+    while turn["i"] % nsets:  # whole rotations, so the timed steps start at set 0 however long the ramp took (--dump-outputs)
+        step()
+        ramp += 1
     for _ in range(args.warmup):
         step()
     graph = None
@@ -562,25 +633,35 @@ def main():
     dev_ms = ev0.elapsed_time(ev1)  # HIP events on the launch stream
     last_set = (first_timed + args.steps - 1) % nsets  # the set the last timed step ran over
 
-    # ---- the timed output is checked, outside `value`: a slice at each end of this rank's shard against
+    # ---- what the last timed step computed, before anything after the timed region can write over it
+    dumped = None
+    if args.dump_outputs:
+        import numpy as np
+        last = dict(outs[last_set])
+        if "min_max" in last:  # the caller receives the decoded (min, max), not the keys
+            mn, mx = sharded.combine_min_max_keys(ec.UInt16, last["min_max"].cpu().tolist())
+            last["min_max"] = np.array([float(mn.value), float(mx.value)])
+        dumped = dump_outputs(args.dump_outputs, last, off, rank, world)
+
+    # ---- the timed output is checked (--full), outside `value`: a slice at each end of this rank's shard against
     # numpy's IEEE f64 arithmetic on the same operands (the oracle itself checks it in the cpu_baseline leg).  Every set
     # the timed region wrote is checked (at most nsets of them), the last one last: its head slice goes to the oracle.
-    scope = None
+    scope = scopes.get(last_set)
     verified = None
-    if args.workload == "div_u8_u16":
+    if args.full and args.workload == "div_u8_u16":
         touched = sorted({(first_timed + i) % nsets for i in range(min(args.steps, nsets))}, key=lambda k: k == last_set)
         verified = True
         for k in touched:
             scope = scopes[k]
             verified = verify_slices(scope) and verified
 
-    # ---- beside the headline, on EVERY rank and outside `value`: the same step over ONE set again and again — the loop
-    # the contract's wording suggests (one batch, K steps), what rounds 1-3 reported as the headline, and what a caller
+    # ---- beside the headline (--full), on EVERY rank and outside `value`: the same step over ONE set again and again — the
+    # loop the contract's wording suggests (one batch, K steps), what rounds 1-3 reported as the headline, and what a caller
     # who iterates over a resident raster sees.  Operands that fit the Infinity Cache are then served on-die from the
     # second step on (the 256 MiB u8 operand at N = 1; both operands of a 1/8 shard), so this figure divides bytes that
     # never crossed HBM by the HBM peak: it is reported as `roofline.cache_resident_loop`, never as `frac`.
     resident_ms, build_up = float("nan"), []
-    if not args.no_resident_loop and not args.graph:
+    if args.full and not args.no_resident_loop and not args.graph:
         # The loop's residency builds up slowly: from a cold start (the rotating steps leave nothing of this set on-die) the one-set
         # loop needs some 40 launches before the operands that fit the cache are served from it at the steady rate, whatever is done
         # to prime them (three read-only passes over the operands beforehand changed nothing: profiles/r04/resident_loop_build_up.md).
@@ -660,7 +741,7 @@ def main():
                                    "algorithmic byte of a timed step moves from / to HBM, none from the 256 MiB Infinity Cache",
                        "kernel_variant": "lds" if (args.variant or 0) == 1 else "direct", "tune": args.tune,
                        "clock_ramp_steps": ramp, "untimed_steps_before_timing": ramp + args.warmup,
-                       "launch": "hipGraph of the K steps" if args.graph else "K stream launches"},
+                       "launch": "hipGraph of the K steps" if args.graph else "K stream launches", "full": args.full},
             "roofline": {"bound": "hbm", "kernel": kernel,
                          "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
                          "traffic": traffic, "traffic_source": traffic_source,
@@ -682,6 +763,9 @@ def main():
                         "the 256 MiB Infinity Cache are served on-die from the second launch on (the 256 MiB u8 operand of the whole "
                         "raster; both operands of a 1/8 shard), so part of these bytes never crossed HBM.  Rounds 1-3 reported this as "
                         "the headline; since round 4 `value`, `ms_per_step` and `roofline.frac` come from the rotating sets above."}
+        if dumped is not None:
+            res["outputs"] = {"dir": os.path.abspath(args.dump_outputs), "operand_set": last_set, "files_rank0": dumped,
+                              "what": "what the last timed step computed (every rank writes its own shard's files)"}
         if verified is not None:
             res["verified"] = verified
             res["config"]["verified_how"] = ("after the timed region every rank compares 2^20 cells at each end of its output shard, for every "
@@ -697,7 +781,7 @@ def main():
                                       "what": "from_vec(u8)+from_vec(u16) over PCIe, divide, to_vec(f64) back; pageable host memory"}
             del r
             res["end_to_end_pcie_pipelined"] = e2e_pipelined(torch, ec, L, a, b, out, n)
-        if world == 1 and not args.no_reference_streams and args.workload == "div_u8_u16":
+        if args.full and world == 1 and not args.no_reference_streams and args.workload == "div_u8_u16":
             # SURVEY §8(d) "empirical ceiling": what plain streams of the same buffers reach on this box, so the
             # fraction of *achievable* bandwidth can be read next to the fraction of the nominal 8 TB/s.  Outside
             # the timed region; same launch shape family, no divide; rotating over the same operand sets (all-HBM, like `frac`).
@@ -724,7 +808,7 @@ def main():
                 "what": "library kernels over the same rotating operand sets, untimed by `value`: 3 B read + 8 B written with an add "
                         "instead of the divide; 8 B/cell written; 8 B/cell read",
             }
-        if world == 1 and not args.no_cpu_baseline and args.workload == "div_u8_u16":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "div_u8_u16":
             res["cpu_baseline"] = cpu_baseline(side, args.cpu_seconds)
             # the oracle as the checker of the timed output (same leg, outside `value`): 2^20 cells, bit for bit,
             # against both of its forms (reference-shaped and typed loop)

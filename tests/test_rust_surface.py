@@ -2,16 +2,19 @@
 public surface is held in lockstep with the reference's by text: every `pub fn`, trait method, `pub
 trait/enum/struct/type` and `impl ... for ...` header of the reference files on the path (src/lib.rs, buffer.rs,
 value.rs, ctype.rs, encoding.rs, error.rs, masked/*.rs — unit-test modules excluded) must appear, same name and
-same signature, in the crate.  Runs only where the reference tree is present (this container); on a box without
-it the test is skipped.  (The crate itself does reproduce the reference's declarations — that is the point of a
+same signature, in the crate.  The reference is not part of this repository: tests/golden/reference_surface.json holds,
+per reference file, each item's kind, name and the SHA-256 of its normalised header (`python tests/test_rust_surface.py
+--reference DIR` rewrites it from the reference's source tree), and the crate's headers are normalised and hashed alike.
+(The crate itself does reproduce the reference's declarations — that is the point of a
 drop-in; which lines, under which licence, is recorded in INTEGRATION.md §2 and held by tests/test_rust_provenance.py.)"""
+import hashlib
+import json
 import os
 import re
-
-import pytest
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/src"
+SURFACE = os.path.join(ROOT, "tests", "golden", "reference_surface.json")
 CRATE = os.path.join(ROOT, "erased-cells_amd", "rust", "erased-cells-hip", "src")
 REF_FILES = ["lib.rs", "buffer.rs", "value.rs", "ctype.rs", "encoding.rs", "error.rs", "masked/mask.rs",
              "masked/masked_buffer.rs", "masked/nodata.rs"]
@@ -68,17 +71,38 @@ def _crate_items() -> set:
     return items
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is not present on this box")
+def _digest(item: str) -> str:
+    return hashlib.sha256(item.encode()).hexdigest()
+
+
+def _kind_and_name(item: str) -> tuple:
+    m = re.match(r"(fn|pub(?:trait|enum|struct|type))([A-Za-z_][A-Za-z0-9_]*)", item)
+    return (m.group(1).replace("pub", ""), m.group(2)) if m else ("impl", None)
+
+
+def record_surface(ref_root: str) -> dict:
+    """{reference file: [{kind, name, sha256 of the normalised header}]} for REF_FILES of the reference tree at ref_root."""
+    out = {}
+    for rel in REF_FILES:
+        items = _items(open(os.path.join(ref_root, "src", rel)).read())
+        out[rel] = sorted(({"kind": k, "name": nm, "sha256": _digest(w)} for w in items for k, nm in [_kind_and_name(w)]),
+                          key=lambda e: (e["kind"], e["name"] or "", e["sha256"]))
+    return out
+
+
 def test_every_public_item_of_the_reference_exists_in_the_rust_crate():
-    have = _crate_items()
+    surface = json.load(open(SURFACE))["files"]
+    assert sorted(surface) == sorted(REF_FILES) and all(surface[rel] for rel in REF_FILES)
+    have = {_digest(i) for i in _crate_items()}
+    waived = {_digest(d) for d in DEVIATIONS}
     missing = {}
     for rel in REF_FILES:
-        want = _items(open(os.path.join(REF, rel)).read())
-        gone = sorted(w for w in want if w not in have and w not in DEVIATIONS)
+        gone = sorted(f"{e['kind']} {e['name'] or ''} (sha256 {e['sha256'][:12]})" for e in surface[rel]
+                      if e["sha256"] not in have and e["sha256"] not in waived)
         if gone:
             missing[rel] = gone
-    assert not missing, "reference items without a same-signature item in the Rust crate:\n" + \
-        "\n".join(f"  {k}: {v}" for k, v in missing.items())
+    assert not missing, "reference items without a same-signature item in the Rust crate (the headers themselves: " \
+        "`_items()` over the reference's file):\n" + "\n".join(f"  {k}: {v}" for k, v in missing.items())
 
 
 def test_crate_is_named_like_the_reference_library_and_carries_its_macro():
@@ -162,3 +186,13 @@ def test_rust_sources_are_balanced_and_call_only_declared_ffi_items():
             local = set(re.findall(r"\b(?:fn|let|mod|struct|type|const)\s+(ec_\w+|EC_\w+)", text))
             unknown = used - declared - local
             assert not unknown, f"{name} uses {sorted(unknown)}: not declared in ffi.rs"
+
+
+if __name__ == "__main__":  # python tests/test_rust_surface.py --reference DIR: rewrite tests/golden/reference_surface.json
+    if len(sys.argv) != 3 or sys.argv[1] != "--reference" or not os.path.isdir(os.path.join(sys.argv[2], "src")):
+        sys.exit("usage: python tests/test_rust_surface.py --reference DIR   (DIR: the erased-cells 0.1.1 source tree)")
+    with open(SURFACE, "w") as f:
+        json.dump({"reference": "erased-cells 0.1.1 (MIT License, Copyright (c) 2023 Astraea, Inc.)",
+                   "what": "public items of the reference files on the path: kind, name, SHA-256 of the normalised header",
+                   "files": record_surface(sys.argv[2])}, f, indent=1, sort_keys=True)
+        f.write("\n")

@@ -11,5 +11,5 @@ timeout -k 10 300 ./tools/tune_fused_any 16384 9 > $O/tune_fused_any.log 2>&1 ||
 cat $O/tune_fused_any.log
 timeout -k 10 300 ./tools/tune_fused_any_u2 16384 9 > $O/tune_fused_any_u2.log 2>&1 || { tail -20 $O/tune_fused_any_u2.log; exit 1; }
 tail -14 $O/tune_fused_any_u2.log
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 cat $O/bench_n1.json

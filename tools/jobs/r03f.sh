@@ -5,11 +5,11 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r03f; mkdir -p $O
 cd $R
 python -m pytest tests -x -q -m gpu --durations=6 > $O/pytest_gpu.log 2>&1 || { tail -60 $O/pytest_gpu.log; exit 1; }
 tail -10 $O/pytest_gpu.log
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
-python bench.py --steps 20 --warmup 5 > $O/bench_n1_driver_flags.json 2>> $O/bench_n1.err
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_n1_driver_flags.json 2>> $O/bench_n1.err
 rm -f $O/bench_all_workloads.jsonl
 for w in "--rows 2048" "--rows 2048 --graph" "--workload masked_chain" "--workload masked_chain --fused" "--workload minmax" "--workload minmax --side 32768" "--workload minmax --side 65536 --steps 20 --warmup 3" "--workload ndvi" "--workload ndvi --fused" "--workload ndvi --mixed" "--workload ndvi --fused --mixed" "--workload binop --lt u16 --rt u16 --op add" "--workload binop --lt f32 --rt f32 --op add" "--workload binop --lt u8 --rt u8 --op add" "--side 32768 --steps 40"; do
-  python bench.py $w --no-cpu-baseline >> $O/bench_all_workloads.jsonl 2>> $O/bench_all.err
+  python bench.py --full $w --no-cpu-baseline >> $O/bench_all_workloads.jsonl 2>> $O/bench_all.err
 done
 python tools/kernel_table.py > $O/kernel_table.md 2> $O/kernel_table.err || { tail -20 $O/kernel_table.err; exit 1; }
 echo "| G | cells/shard | K | async host/wall/gpu us | blocking host/wall/gpu us | plain one thread host/wall/gpu us | async again |" > $O/group_fanout_rows.md
@@ -19,8 +19,8 @@ for G in 1 2 4 8; do
 done
 cat $O/group_fanout_rows.md
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/prof_bench --output-format csv -- python3 /root/repo/bench.py --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/prof_bench.err
-rocprofv3 --kernel-trace --stats -d $O/prof_bench_loop --output-format csv -- python3 /root/repo/bench.py --no-cpu-baseline --no-fresh-inputs --no-reference-streams > $O/bench_loop_only_under_rocprof.json 2> $O/prof_bench_loop.err
+rocprofv3 --kernel-trace --stats -d $O/prof_bench --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/prof_bench.err
+rocprofv3 --kernel-trace --stats -d $O/prof_bench_loop --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-fresh-inputs --no-reference-streams > $O/bench_loop_only_under_rocprof.json 2> $O/prof_bench_loop.err
 rocprofv3 --kernel-trace --stats -d $O/prof_table --output-format csv -- python3 /root/repo/tools/kernel_table.py > $O/kernel_table_under_rocprof.md 2> $O/prof_table.err
 cd $R
 for d in prof_bench prof_bench_loop prof_table; do

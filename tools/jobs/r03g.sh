@@ -8,9 +8,9 @@ python -m pytest tests -x -q -m gpu --durations=6 > $O/pytest_gpu.log 2>&1 || { 
 tail -10 $O/pytest_gpu.log
 rm -f $O/bench_evi.jsonl
 for w in "--workload evi" "--workload evi --fused" "--workload evi --fused --side 8192" "--workload ndvi --fused" "--workload masked_chain --fused"; do
-  python bench.py $w --no-cpu-baseline >> $O/bench_evi.jsonl 2>> $O/bench_evi.err
+  python bench.py --full $w --no-cpu-baseline >> $O/bench_evi.jsonl 2>> $O/bench_evi.err
 done
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 python - <<'PY'
 import json
 r = json.load(open("gpurun_out/r03g/bench_n1.json")); rf = r["roofline"]

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r03m; mkdir -p $O
 cd $R
 python -m pytest tests -x -q -m gpu --durations=5 > $O/pytest_gpu.log 2>&1 || { tail -60 $O/pytest_gpu.log; exit 1; }
 tail -9 $O/pytest_gpu.log
-python bench.py --e2e > $O/bench_n1_e2e.json 2> $O/bench.err
+python bench.py --full --e2e > $O/bench_n1_e2e.json 2> $O/bench.err
 python tools/host_pipe_bench.py > $O/host_pipe_bench.md 2>> $O/bench.err
 cat $O/host_pipe_bench.md
 python - <<'PY'

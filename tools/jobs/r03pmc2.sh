@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 COMMON="--steps 5 --warmup 1 --ramp 0 --no-cpu-baseline --no-reference-streams --no-fresh-inputs"
 run() {  # name, counters, bench flags
   local name=$1 ctrs=$2; shift 2
-  rocprofv3 --pmc $ctrs --kernel-trace -d $O/$name --output-format csv -- python3 /root/repo/bench.py $COMMON "$@" > $O/$name.json 2> $O/$name.err || { tail -5 $O/$name.err; return 1; }
+  rocprofv3 --pmc $ctrs --kernel-trace -d $O/$name --output-format csv -- python3 $R/bench.py --full $COMMON "$@" > $O/$name.json 2> $O/$name.err || { tail -5 $O/$name.err; return 1; }
   find $O/$name -name '*kernel_trace.csv' -delete
   echo "done $name"
 }

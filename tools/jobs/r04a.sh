@@ -2,13 +2,13 @@
 set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04a; mkdir -p $O
 cd $R
-python bench.py > $O/bench_n1.json 2> $O/err || { tail -30 $O/err; exit 1; }
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_n1_driver_flags.json 2>> $O/err
-python bench.py --no-cpu-baseline --no-reference-streams --tune mall_mb=0 > $O/bench_n1_all_nt.json 2>> $O/err
-python bench.py --no-cpu-baseline --no-reference-streams --tune mall_mb=192 > $O/bench_n1_mall192.json 2>> $O/err
-python bench.py --no-cpu-baseline --no-reference-streams --rows 2048 > $O/bench_shard8.json 2>> $O/err
-python bench.py --no-cpu-baseline --no-reference-streams --rows 2048 --tune mall_mb=0 > $O/bench_shard8_all_nt.json 2>> $O/err
-python bench.py --no-cpu-baseline --no-reference-streams --sets 1 > $O/bench_n1_sets1.json 2>> $O/err
+python bench.py --full > $O/bench_n1.json 2> $O/err || { tail -30 $O/err; exit 1; }
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_n1_driver_flags.json 2>> $O/err
+python bench.py --full --no-cpu-baseline --no-reference-streams --tune mall_mb=0 > $O/bench_n1_all_nt.json 2>> $O/err
+python bench.py --full --no-cpu-baseline --no-reference-streams --tune mall_mb=192 > $O/bench_n1_mall192.json 2>> $O/err
+python bench.py --full --no-cpu-baseline --no-reference-streams --rows 2048 > $O/bench_shard8.json 2>> $O/err
+python bench.py --full --no-cpu-baseline --no-reference-streams --rows 2048 --tune mall_mb=0 > $O/bench_shard8_all_nt.json 2>> $O/err
+python bench.py --full --no-cpu-baseline --no-reference-streams --sets 1 > $O/bench_n1_sets1.json 2>> $O/err
 python - <<'PY'
 import json
 for f in ("bench_n1", "bench_n1_driver_flags", "bench_n1_all_nt", "bench_n1_mall192", "bench_shard8", "bench_shard8_all_nt", "bench_n1_sets1"):

@@ -7,12 +7,12 @@ python -m pytest tests -q -m gpu > $O/pytest_gpu.log 2>&1 || { grep -E "^(FAILED
 tail -3 $O/pytest_gpu.log
 NT=$R/erased-cells_amd/liberased_cells_hip_ntstore.so
 for rep in 1 2; do
-python bench.py --no-cpu-baseline > $O/bench_sc1_$rep.json 2>> $O/err
-EC_HIP_LIB=$NT python bench.py --no-cpu-baseline > $O/bench_nt_$rep.json 2>> $O/err
+python bench.py --full --no-cpu-baseline > $O/bench_sc1_$rep.json 2>> $O/err
+EC_HIP_LIB=$NT python bench.py --full --no-cpu-baseline > $O/bench_nt_$rep.json 2>> $O/err
 done
-python bench.py --no-cpu-baseline --rows 2048 > $O/bench_shard8_sc1.json 2>> $O/err
-EC_HIP_LIB=$NT python bench.py --no-cpu-baseline --rows 2048 > $O/bench_shard8_nt.json 2>> $O/err
-python bench.py --no-cpu-baseline --no-reference-streams --tune mall_mb=0 > $O/bench_sc1_all_nt_loads.json 2>> $O/err
+python bench.py --full --no-cpu-baseline --rows 2048 > $O/bench_shard8_sc1.json 2>> $O/err
+EC_HIP_LIB=$NT python bench.py --full --no-cpu-baseline --rows 2048 > $O/bench_shard8_nt.json 2>> $O/err
+python bench.py --full --no-cpu-baseline --no-reference-streams --tune mall_mb=0 > $O/bench_sc1_all_nt_loads.json 2>> $O/err
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/r04b/bench_*.json")):

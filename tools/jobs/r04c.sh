@@ -7,9 +7,9 @@ cd $R
 for wl in "u8 u16 div" "u8 u16 add" "u8 u8 div" "u8 u8 add" "u16 u8 add" "u16 u16 add"; do
   set -- $wl
   for f in 0 1 2 3; do
-    python bench.py --no-cpu-baseline --workload binop --lt $1 --rt $2 --op $3 --tune cache_force=$f --steps 100 > $O/binop_$1_$2_$3_force$f.json 2>> $O/err
+    python bench.py --full --no-cpu-baseline --workload binop --lt $1 --rt $2 --op $3 --tune cache_force=$f --steps 100 > $O/binop_$1_$2_$3_force$f.json 2>> $O/err
   done
-  python bench.py --no-cpu-baseline --workload binop --lt $1 --rt $2 --op $3 --steps 100 > $O/binop_$1_$2_$3_policy.json 2>> $O/err
+  python bench.py --full --no-cpu-baseline --workload binop --lt $1 --rt $2 --op $3 --steps 100 > $O/binop_$1_$2_$3_policy.json 2>> $O/err
 done
 python - <<'PY'
 import json, glob

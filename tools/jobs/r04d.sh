@@ -7,14 +7,14 @@ python -m pytest tests/test_gpu_parity.py tests/test_gpu_instantiations.py tests
 tail -2 $O/pytest_gpu.log
 A=$R/erased-cells_amd/liberased_cells_hip_sc1all.so; N=$R/erased-cells_amd/liberased_cells_hip_ntstore.so
 for rep in 1 2; do
-  python bench.py --no-cpu-baseline > $O/bench_p3_$rep.json 2>> $O/err
-  EC_HIP_LIB=$A python bench.py --no-cpu-baseline > $O/bench_sc1all_$rep.json 2>> $O/err
-  EC_HIP_LIB=$N python bench.py --no-cpu-baseline > $O/bench_nt_$rep.json 2>> $O/err
+  python bench.py --full --no-cpu-baseline > $O/bench_p3_$rep.json 2>> $O/err
+  EC_HIP_LIB=$A python bench.py --full --no-cpu-baseline > $O/bench_sc1all_$rep.json 2>> $O/err
+  EC_HIP_LIB=$N python bench.py --full --no-cpu-baseline > $O/bench_nt_$rep.json 2>> $O/err
   python tools/kernel_table.py > $O/kernel_table_p3_$rep.md 2>> $O/err
   EC_HIP_LIB=$A python tools/kernel_table.py > $O/kernel_table_sc1all_$rep.md 2>> $O/err
   EC_HIP_LIB=$N python tools/kernel_table.py > $O/kernel_table_nt_$rep.md 2>> $O/err
 done
-python bench.py --no-cpu-baseline --rows 2048 > $O/bench_shard8_p3.json 2>> $O/err
+python bench.py --full --no-cpu-baseline --rows 2048 > $O/bench_shard8_p3.json 2>> $O/err
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/r04d/bench_*.json")):

@@ -4,7 +4,7 @@ cd $R
 : > $O/ab.jsonl
 for w in "--workload masked_chain --fused" "--workload ndvi --fused" "--workload ndvi --fused --mixed" "--workload evi --fused" "--workload evi --fused --compiled"; do
   for k in 0 12 16 20 24 32 48; do
-    python bench.py --no-cpu-baseline --no-reference-streams --no-resident-loop --steps 60 $w --tune fused_lds_kb=$k 2>>$O/err | python -c "
+    python bench.py --full --no-cpu-baseline --no-reference-streams --no-resident-loop --steps 60 $w --tune fused_lds_kb=$k 2>>$O/err | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print(json.dumps({'w': '$w', 'lds_kb': $k, 'frac': round(d['roofline']['frac'],4), 'verified': d.get('verified')}))" >> $O/ab.jsonl
   done

@@ -2,12 +2,12 @@
 set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04j; mkdir -p $O
 cd $R
-python bench.py > $O/bench_n1.json 2> $O/err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_flags.json 2>> $O/err
-python bench.py --no-cpu-baseline --rows 2048 > $O/bench_shard8.json 2>> $O/err
+python bench.py --full > $O/bench_n1.json 2> $O/err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_flags.json 2>> $O/err
+python bench.py --full --no-cpu-baseline --rows 2048 > $O/bench_shard8.json 2>> $O/err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/prof_default --output-format csv -- python3 /root/repo/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default_under_rocprof.json 2> $O/prof_default.err || tail -5 $O/prof_default.err
-rocprofv3 --kernel-trace --stats -d $O/prof_rot --output-format csv -- python3 /root/repo/bench.py --no-cpu-baseline --no-resident-loop --no-reference-streams > $O/bench_rotating_only_under_rocprof.json 2> $O/prof_rot.err || tail -5 $O/prof_rot.err
+rocprofv3 --kernel-trace --stats -d $O/prof_default --output-format csv -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_default_under_rocprof.json 2> $O/prof_default.err || tail -5 $O/prof_default.err
+rocprofv3 --kernel-trace --stats -d $O/prof_rot --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-resident-loop --no-reference-streams > $O/bench_rotating_only_under_rocprof.json 2> $O/prof_rot.err || tail -5 $O/prof_rot.err
 cd $R
 for d in prof_default prof_rot; do
   f=$(find $O/$d -name '*kernel_stats.csv' | head -1); cp "$f" $O/${d}_kernel_stats.csv; find $O/$d -name '*kernel_trace.csv' -delete

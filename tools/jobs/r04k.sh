@@ -5,13 +5,13 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04k; mkdir -p $O
 cd $R
 python -m pytest tests -q -m gpu -s > $O/pytest_gpu.log 2>&1 || { grep -E "^(FAILED|ERROR)|passed|failed|Abort|fault" $O/pytest_gpu.log | tail -30; }
 grep -E "passed|failed" $O/pytest_gpu.log | tail -2
-python bench.py > $O/bench_n1.json 2> $O/err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_flags.json 2>> $O/err
-python bench.py --no-cpu-baseline --rows 2048 > $O/bench_shard8.json 2>> $O/err
-python bench.py --no-cpu-baseline --rows 2048 --graph > $O/bench_shard8_graph.json 2>> $O/err
+python bench.py --full > $O/bench_n1.json 2> $O/err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_flags.json 2>> $O/err
+python bench.py --full --no-cpu-baseline --rows 2048 > $O/bench_shard8.json 2>> $O/err
+python bench.py --full --no-cpu-baseline --rows 2048 --graph > $O/bench_shard8_graph.json 2>> $O/err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/prof_default --output-format csv -- python3 /root/repo/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default_under_rocprof.json 2> $O/prof_default.err || tail -5 $O/prof_default.err
-rocprofv3 --kernel-trace --stats -d $O/prof_rot --output-format csv -- python3 /root/repo/bench.py --no-cpu-baseline --no-resident-loop --no-reference-streams > $O/bench_rotating_only_under_rocprof.json 2> $O/prof_rot.err || tail -5 $O/prof_rot.err
+rocprofv3 --kernel-trace --stats -d $O/prof_default --output-format csv -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_default_under_rocprof.json 2> $O/prof_default.err || tail -5 $O/prof_default.err
+rocprofv3 --kernel-trace --stats -d $O/prof_rot --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-resident-loop --no-reference-streams > $O/bench_rotating_only_under_rocprof.json 2> $O/prof_rot.err || tail -5 $O/prof_rot.err
 cd $R
 for d in prof_default prof_rot; do
   f=$(find $O/$d -name '*kernel_stats.csv' | head -1); cp "$f" $O/${d}_kernel_stats.csv; find $O/$d -name '*kernel_trace.csv' -delete
@@ -23,7 +23,7 @@ for wl in "--workload masked_chain" "--workload masked_chain --fused" "--workloa
           "--workload ndvi" "--workload ndvi --fused" "--workload ndvi --fused --mixed" "--workload evi" "--workload evi --fused" "--workload evi --fused --interpret" \
           "--workload evi --fused --compiled" "--workload binop --lt u8 --rt u16 --op add" "--workload binop --lt u16 --rt u16 --op add" \
           "--workload binop --lt f32 --rt f32 --op add" "--workload binop --lt u8 --rt u8 --op div" "--workload binop --lt u8 --rt u8 --op add" "--side 32768" "--side 8192" "--side 4096"; do
-  python bench.py --no-cpu-baseline $wl >> $O/bench_all_workloads.jsonl 2>> $O/err
+  python bench.py --full --no-cpu-baseline $wl >> $O/bench_all_workloads.jsonl 2>> $O/err
 done
 python - <<'PY'
 import json

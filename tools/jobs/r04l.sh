@@ -8,6 +8,6 @@ python tools/placement_probe.py > $O/placement_probe.md 2> $O/err || tail -5 $O/
 cat $O/placement_probe.md
 python tools/kernel_table.py 32768 > $O/kernel_table_32768.md 2>> $O/err || tail -5 $O/err
 grep -E "^\| (min_max|mask_counts|first_diff|fill|binop (Add|Div) UInt8)" $O/kernel_table_32768.md | cut -c1-150
-python bench.py --no-cpu-baseline --steps 20 --warmup 5 > $O/bench.json 2>> $O/err
+python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $O/bench.json 2>> $O/err
 python -c "
 import json; r=json.load(open('gpurun_out/r04l/bench.json')); print(round(r['value'],1), round(r['roofline']['frac'],4), r['verified'])"

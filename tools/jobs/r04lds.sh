@@ -5,7 +5,7 @@ cd $R
 for w in "--lt f32 --rt f32" "--lt f64 --rt f32" "--lt u16 --rt u16" "--lt u8 --rt u16" "--lt u8 --rt u8" "--lt u16 --rt f32"; do
   for cfg in "0:-1" "1:0" "1:8" "1:16" "1:24" "1:32" "1:48"; do
     v=${cfg%%:*}; k=${cfg##*:}
-    python bench.py --no-cpu-baseline --no-reference-streams --no-resident-loop --steps 100 --workload binop --op add $w --tune binop_variant=$v --tune binop_lds_kb=$k 2>>$O/err | python -c "
+    python bench.py --full --no-cpu-baseline --no-reference-streams --no-resident-loop --steps 100 --workload binop --op add $w --tune binop_variant=$v --tune binop_lds_kb=$k 2>>$O/err | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print(json.dumps({'w': '$w', 'variant': $v, 'lds_kb': $k, 'frac': round(d['roofline']['frac'],4), 'verified': d.get('verified')}))" >> $O/ab.jsonl
   done

@@ -5,7 +5,7 @@ cd $R
 for w in "--lt u32 --rt f32" "--lt f64 --rt f32" "--lt f32 --rt f64" "--lt f64 --rt u32" "--lt f64 --rt u16" "--lt u16 --rt f64" "--lt f64 --rt u8" "--lt f32 --rt u16" "--lt u16 --rt u32" "--lt f32 --rt u8"; do
   for cfg in "0:-1" "1:0" "1:12" "1:16" "1:20" "1:24" "1:28" "1:32" "1:40"; do
     v=${cfg%%:*}; k=${cfg##*:}
-    python bench.py --no-cpu-baseline --no-reference-streams --no-resident-loop --steps 100 --workload binop --op add $w --tune binop_variant=$v --tune binop_lds_kb=$k 2>>$O/err | python -c "
+    python bench.py --full --no-cpu-baseline --no-reference-streams --no-resident-loop --steps 100 --workload binop --op add $w --tune binop_variant=$v --tune binop_lds_kb=$k 2>>$O/err | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print(json.dumps({'w': '$w', 'variant': $v, 'lds_kb': $k, 'frac': round(d['roofline']['frac'],4)}))" >> $O/ab.jsonl
   done

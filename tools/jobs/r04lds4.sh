@@ -7,7 +7,7 @@ grep -E "passed|failed" $O/pytest.log | tail -1
 for round in 1 2; do
 for w in "--workload binop --lt f64 --rt u16" "--workload binop --lt u16 --rt f64" "--workload binop --lt f64 --rt f32" "--workload binop --lt f32 --rt f64" "--workload binop --lt f64 --rt u32" "--workload binop --lt f64 --rt u8" "--workload binop --lt f64 --rt u16 --op div" "--workload evi" "--workload masked_chain" "--workload ndvi --mixed"; do
   for v in -1 0; do
-    python bench.py --no-cpu-baseline --no-reference-streams --no-resident-loop --steps 60 $w --tune binop_variant=$v 2>>$O/err | python -c "
+    python bench.py --full --no-cpu-baseline --no-reference-streams --no-resident-loop --steps 60 $w --tune binop_variant=$v 2>>$O/err | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print(json.dumps({'w': '$w', 'variant': $v, 'frac': round(d['roofline']['frac'],4), 'value': round(d['value'],2), 'verified': d.get('verified')}))" >> $O/ab.jsonl
   done

@@ -4,10 +4,10 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04m; mkdir -p $O
 cd $R
 B=$R/erased-cells_amd/liberased_cells_hip_divstage2.so
 for rep in 1 2 3; do
-  python bench.py --no-cpu-baseline --no-reference-streams --no-resident-loop > $O/bench_stage1_$rep.json 2>> $O/err
-  EC_HIP_LIB=$B python bench.py --no-cpu-baseline --no-reference-streams --no-resident-loop > $O/bench_stage2_$rep.json 2>> $O/err
+  python bench.py --full --no-cpu-baseline --no-reference-streams --no-resident-loop > $O/bench_stage1_$rep.json 2>> $O/err
+  EC_HIP_LIB=$B python bench.py --full --no-cpu-baseline --no-reference-streams --no-resident-loop > $O/bench_stage2_$rep.json 2>> $O/err
 done
-python bench.py --no-cpu-baseline --no-reference-streams --no-resident-loop --workload binop --lt u8 --rt u16 --op add > $O/bench_add.json 2>> $O/err
+python bench.py --full --no-cpu-baseline --no-reference-streams --no-resident-loop --workload binop --lt u8 --rt u16 --op add > $O/bench_add.json 2>> $O/err
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/r04m/bench_*.json")):

@@ -4,8 +4,8 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04n; mkdir -p $O
 cd $R
 B=$R/erased-cells_amd/liberased_cells_hip_fixedchunk.so
 for rep in 1 2 3; do
-  python bench.py --no-cpu-baseline --no-resident-loop --workload evi --fused > $O/evi_tile_$rep.json 2>> $O/err
-  EC_HIP_LIB=$B python bench.py --no-cpu-baseline --no-resident-loop --workload evi --fused > $O/evi_chunk_$rep.json 2>> $O/err
+  python bench.py --full --no-cpu-baseline --no-resident-loop --workload evi --fused > $O/evi_tile_$rep.json 2>> $O/err
+  EC_HIP_LIB=$B python bench.py --full --no-cpu-baseline --no-resident-loop --workload evi --fused > $O/evi_chunk_$rep.json 2>> $O/err
 done
 python - <<'PY'
 import json, glob

@@ -9,8 +9,8 @@ B=$R/erased-cells_amd/liberased_cells_hip_fusedtile.so
 for rep in 1 2; do
   for wl in "ndvi --workload ndvi --fused" "ndvimixed --workload ndvi --fused --mixed" "chain --workload masked_chain --fused"; do
     set -- $wl; key=$1; shift
-    python bench.py --no-cpu-baseline --no-resident-loop "$@" > $O/${key}_chunk_$rep.json 2>> $O/err
-    EC_HIP_LIB=$B python bench.py --no-cpu-baseline --no-resident-loop "$@" > $O/${key}_tile_$rep.json 2>> $O/err
+    python bench.py --full --no-cpu-baseline --no-resident-loop "$@" > $O/${key}_chunk_$rep.json 2>> $O/err
+    EC_HIP_LIB=$B python bench.py --full --no-cpu-baseline --no-resident-loop "$@" > $O/${key}_tile_$rep.json 2>> $O/err
   done
 done
 python - <<'PY'

@@ -8,8 +8,8 @@ python tools/write_heavy_caps.py > $O/write_heavy_caps.md 2> $O/err || tail -3 $
 for rep in 1 2; do
   for wl in "evi --workload evi" "ndvi --workload ndvi" "chain --workload masked_chain"; do
     set -- $wl; key=$1; shift
-    python bench.py --no-cpu-baseline --no-resident-loop "$@" > $O/${key}_rule_$rep.json 2>> $O/err
-    python bench.py --no-cpu-baseline --no-resident-loop "$@" --tune binop_lds_kb=0 --tune scalar_lds_kb=0 > $O/${key}_nocap_$rep.json 2>> $O/err
+    python bench.py --full --no-cpu-baseline --no-resident-loop "$@" > $O/${key}_rule_$rep.json 2>> $O/err
+    python bench.py --full --no-cpu-baseline --no-resident-loop "$@" --tune binop_lds_kb=0 --tune scalar_lds_kb=0 > $O/${key}_nocap_$rep.json 2>> $O/err
   done
 done
 python - <<'PY'

@@ -1,7 +1,7 @@
 set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04shprof; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/prof --output-format csv -- python3 /root/repo/bench.py --no-cpu-baseline --no-reference-streams --no-resident-loop --rows 2048 > $O/bench.json 2> $O/err || tail -5 $O/err
+rocprofv3 --kernel-trace --stats -d $O/prof --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-reference-streams --no-resident-loop --rows 2048 > $O/bench.json 2> $O/err || tail -5 $O/err
 cd $R
 f=$(find $O/prof -name '*kernel_stats.csv' | head -1); cp "$f" $O/kernel_stats.csv
 t=$(find $O/prof -name '*kernel_trace.csv' | head -1)

@@ -8,7 +8,7 @@ python tools/kernel_table.py > $O/kernel_table.md 2> $O/err
 grep -E "^\| (binop|masked|fused|binop_scalar)" $O/kernel_table.md | cut -c1-140
 python tools/write_heavy_caps.py > $O/write_heavy_caps.md 2>> $O/err; head -8 $O/write_heavy_caps.md
 for wl in "--workload binop --lt f32 --rt f32 --op add" "--workload masked_chain" "--workload masked_chain --fused" "--workload ndvi --fused --mixed" "--workload evi"; do
-  python bench.py --no-cpu-baseline --no-resident-loop $wl >> $O/bench.jsonl 2>> $O/err
+  python bench.py --full --no-cpu-baseline --no-resident-loop $wl >> $O/bench.jsonl 2>> $O/err
 done
 python - <<'PY'
 import json

@@ -5,7 +5,7 @@ cd $R
 for round in 1 2 3; do
   for v in A W; do
     for w in "" "--workload binop --lt u8 --rt u16 --op add" "--workload binop --lt f32 --rt f32 --op add" "--workload binop --lt f64 --rt f64 --op add" "--workload binop --lt u16 --rt u16 --op div" "--rows 2048"; do
-      EC_HIP_LIB=$R/erased-cells_amd/ab/lib$v.so python bench.py --no-cpu-baseline --no-reference-streams --no-resident-loop --steps 200 $w 2>>$O/err | python -c "
+      EC_HIP_LIB=$R/erased-cells_amd/ab/lib$v.so python bench.py --full --no-cpu-baseline --no-reference-streams --no-resident-loop --steps 200 $w 2>>$O/err | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print(json.dumps({'v': '$v', 'w': '$w', 'round': $round, 'frac': d['roofline']['frac'], 'launch_ms': d['roofline'].get('launch_ms'), 'value': d['value'], 'verified': d.get('verified')}))" >> $O/ab.jsonl
     done

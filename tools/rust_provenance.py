@@ -11,21 +11,26 @@ the source with comment pairs
 
 This tool lists the marked ranges (the PROVENANCE table of INTEGRATION.md §2 is its `--table` output) and measures, per
 crate file, difflib similarity against every file of the reference — with the marked ranges removed and with them in —
-by characters and by lines, on the non-test part of both sides (the measure the round-2 review used).
+by characters and by lines, on the non-test part of both sides (the measure the round-2 review used).  `--record` keeps
+what the tests need of the reference in tests/golden/reference_provenance.json: the line count of every reference source
+file (for the citations) and, per crate file, its SHA-256 with the similarity measured for exactly that text.
 
-    python tools/rust_provenance.py --table          # markdown table of the marked ranges
-    python tools/rust_provenance.py --similarity     # needs /root/reference
+    python tools/rust_provenance.py --table                                  # markdown table of the marked ranges
+    python tools/rust_provenance.py --reference DIR --similarity             # DIR: the erased-cells 0.1.1 source tree
+    python tools/rust_provenance.py --reference DIR --record                 # rewrite the tests' record
 """
 import argparse
 import difflib
 import glob
+import hashlib
+import json
 import os
 import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CRATE = os.path.join(ROOT, "erased-cells_amd", "rust", "erased-cells-hip", "src")
-REF = "/root/reference/src"
+RECORD = os.path.join(ROOT, "tests", "golden", "reference_provenance.json")
 OPEN = re.compile(r"^\s*// api-surface\(([^)]*)\):\s*(.*)$")
 CLOSE = re.compile(r"^\s*// end api-surface\s*$")
 
@@ -93,8 +98,18 @@ def table():
     return "\n".join(rows)
 
 
-def similarities(exhaustive=False, with_full=True):
-    refs = {os.path.relpath(p, REF): nontest(open(p).read()) for p in glob.glob(os.path.join(REF, "**", "*.rs"), recursive=True)}
+def digest(path):
+    return hashlib.sha256(open(path, "rb").read()).hexdigest()
+
+
+def reference_files(ref_root):
+    """{path relative to the reference's root ("src/..."): text} of every Rust source file of the reference"""
+    src = os.path.join(ref_root, "src")
+    return {os.path.relpath(p, ref_root): open(p).read() for p in sorted(glob.glob(os.path.join(src, "**", "*.rs"), recursive=True))}
+
+
+def similarities(ref_root, exhaustive=False, with_full=True):
+    refs = {os.path.relpath(f, "src"): nontest(t) for f, t in reference_files(ref_root).items()}
     out = []
     for p in crate_files():
         full, stripped = nontest(open(p).read()), nontest(without_marked(p))
@@ -102,20 +117,37 @@ def similarities(exhaustive=False, with_full=True):
     return out
 
 
+def record(ref_root):
+    """What tests/test_rust_provenance.py holds the crate to, measured against the reference tree at `ref_root`."""
+    rec = {"reference": "erased-cells 0.1.1 (MIT License, Copyright (c) 2023 Astraea, Inc.)",
+           "line_counts": {f: len(t.split("\n")) for f, t in reference_files(ref_root).items()},
+           "similarity": {}}
+    for name, (s, rn), _ in similarities(ref_root, with_full=False):
+        rec["similarity"][name] = {"sha256": digest(os.path.join(CRATE, name)), "marked_ranges_removed": round(s, 4),
+                                   "most_similar_reference_file": rn}
+    with open(RECORD, "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--table", action="store_true")
     ap.add_argument("--similarity", action="store_true")
+    ap.add_argument("--record", action="store_true", help=f"rewrite {os.path.relpath(RECORD, ROOT)} from --reference")
+    ap.add_argument("--reference", metavar="DIR", help="root of the reference's source tree (erased-cells 0.1.1: Cargo.toml, src/)")
     ap.add_argument("--exhaustive", action="store_true", help="character ratio against every reference file (minutes)")
     a = ap.parse_args()
-    if a.table or not a.similarity:
+    if a.table or not (a.similarity or a.record):
         print(table())
+    if (a.similarity or a.record) and not (a.reference and os.path.isdir(os.path.join(a.reference, "src"))):
+        sys.exit("--similarity and --record need --reference DIR, the reference's source tree")
     if a.similarity:
-        if not os.path.isdir(REF):
-            sys.exit("the reference tree is not present on this box")
         print("\n| crate file | most similar reference file, marked ranges removed | with them in |\n|---|---|---|")
-        for name, (s, rn), (f, fn) in similarities(a.exhaustive):
+        for name, (s, rn), (f, fn) in similarities(a.reference, a.exhaustive):
             print(f"| `src/{name}` | {s:.2f} `{rn}` | {f:.2f} `{fn}` |")
+    if a.record:
+        record(a.reference)
 
 
 if __name__ == "__main__":
