@@ -293,8 +293,7 @@ extern "C" ec_status ec_expr_source(const ec_dtype* dt, int32_t n_streams, int32
         int id = -1;
         const std::string tree = expr_fixed_tree(ea, &fm, &id);
         static const char* const kName[kFixCount] = {"NDVI", "add-mul", "EVI", "affine"};
-        bool one_width = id >= 0;
-        for (int k = 1; one_width && k < n_streams; ++k) one_width = ecl::size_of(dt[k]) == ecl::size_of(dt[0]);
+        const bool one_width = expr_fixed_width(ea, fm, id) != 0;  // the launch's own test (aliased buffers: a launch-time question)
         src = "// tree: " + (tree.empty() ? std::string("(none within the catalogue's size)") : tree) + "\n// ahead-of-time kernel: " +
               (id < 0 ? std::string("none (not in the catalogue)") : one_width ? std::string(kName[id]) : std::string(kName[id]) + " in the catalogue, but the streams differ in width: none") + "\n";
     }

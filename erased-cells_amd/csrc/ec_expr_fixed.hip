@@ -124,6 +124,16 @@ std::string expr_fixed_tree(const ExprArgs& ea, FixedMap* fm, int* id) {
     return u.out;
 }
 
+static int fixed_streams(int id) { return id == kFixNdvi ? 2 : id == kFixAffine ? 1 : 3; }
+
+int expr_fixed_width(const ExprArgs& ea, const FixedMap& fm, int id) {
+    if (id < 0) return 0;
+    const int c = static_cast<int>(ecl::size_of(ea.dt[fm.stream[0]]));
+    for (int k = 1; k < fixed_streams(id); ++k)
+        if (static_cast<int>(ecl::size_of(ea.dt[fm.stream[k]])) != c) return 0;
+    return c;
+}
+
 ec_status expr_fixed_launch(const ExprArgs& ea, size_t n, double* out, uint8_t* out_mask, hipStream_t s, bool* launched) {
     *launched = false;
     if (!tuning().expr_fixed.load()) return EC_OK;
@@ -133,19 +143,17 @@ ec_status expr_fixed_launch(const ExprArgs& ea, size_t n, double* out, uint8_t* 
     if (id < 0) return EC_OK;
     // one cell width for all the streams the tree reads (the bands of one raster), and no buffer read under two names: the catalogue's
     // S0, S1, … are distinct streams (a caller that passes one buffer twice gets the interpreter)
-    const int nstreams = id == kFixNdvi ? 2 : id == kFixAffine ? 1 : 3;
-    const size_t c = ecl::size_of(ea.dt[fm.stream[0]]);
-    for (int k = 1; k < nstreams; ++k) {
-        if (ecl::size_of(ea.dt[fm.stream[k]]) != c) return EC_OK;
+    const int c = expr_fixed_width(ea, fm, id);
+    if (c == 0) return EC_OK;
+    for (int k = 1; k < fixed_streams(id); ++k)
         for (int j = 0; j < k; ++j)
             if (ea.p[fm.stream[j]] == ea.p[fm.stream[k]]) return EC_OK;
-    }
     FixedKernel kern = nullptr;
     switch (id) {
-        case kFixNdvi: kern = fixed_kernel_of<kFixNdvi>(static_cast<int>(c)); break;
-        case kFixAddMul: kern = fixed_kernel_of<kFixAddMul>(static_cast<int>(c)); break;
-        case kFixEvi: kern = fixed_kernel_of<kFixEvi>(static_cast<int>(c)); break;
-        case kFixAffine: kern = fixed_kernel_of<kFixAffine>(static_cast<int>(c)); break;
+        case kFixNdvi: kern = fixed_kernel_of<kFixNdvi>(c); break;
+        case kFixAddMul: kern = fixed_kernel_of<kFixAddMul>(c); break;
+        case kFixEvi: kern = fixed_kernel_of<kFixEvi>(c); break;
+        case kFixAffine: kern = fixed_kernel_of<kFixAffine>(c); break;
     }
     if (!kern) return EC_OK;
     const size_t per_tile = size_t(kBlock) * kFixedU;

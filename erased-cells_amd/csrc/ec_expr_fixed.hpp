@@ -221,5 +221,8 @@ ec_status expr_fixed_launch(const ExprArgs& ea, size_t n, double* out, uint8_t* 
 int64_t expr_fixed_stat(const char* key, bool* known);
 // the canonical tree of a program ("" when it has no bounded one), with the maps; `id` = its catalogue entry or -1
 std::string expr_fixed_tree(const ExprArgs& ea, FixedMap* fm, int* id);
+// the one cell width (bytes) of the streams catalogue entry `id` reads through `fm`, or 0 when they differ: the width test of
+// expr_fixed_launch, and of the report ec_expr_source gives (streams the tree does not read do not count)
+int expr_fixed_width(const ExprArgs& ea, const FixedMap& fm, int id);
 
 }  // namespace ecd

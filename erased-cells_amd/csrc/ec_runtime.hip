@@ -12,6 +12,7 @@
 
 #include <atomic>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -121,6 +122,50 @@ static thread_local int t_cus = 256;
 int64_t expr_stat(const char* key, bool* known);  // ec_expr.hip
 void expr_jit_release();                             // ec_expr_jit.hip
 Tuning& tuning() { return g_tuning; }
+
+// The knobs of ec_tune_set and the values each accepts (include/erased_cells.h documents the same list): ec_tune_set stores a value
+// in [lo, hi] as given (a pow2 knob only its powers of two: the others are refused); one outside it is saturated to the nearer end
+// (Clamp) or refused with the knob unchanged (Refuse); a Bool knob stores value != 0.  Every bound fits an int, so an int knob never narrows.  ec_stat_get("tune.<key>") reads the same table.
+namespace {
+enum class Out { Clamp, Refuse, Bool };
+struct Knob {
+    const char* key;
+    std::atomic<int>* i;       // the knob's word: an int …
+    std::atomic<int64_t>* l;   // … or an int64_t
+    int64_t lo, hi;
+    Out out;
+    bool pow2 = false;  // accepted: the powers of two in [lo, hi] only (map_u: 1, 2, 4); any other value is refused
+};
+constexpr int64_t kMaxMiB = int64_t(1) << 20;  // 1 TiB: more than any device holds, and << 20 stays far inside 64 bits
+const Knob kKnobs[] = {
+    {"binop_variant", &g_tuning.binop_variant, nullptr, -1, 1, Out::Refuse},
+    {"reduce_bpc", &g_tuning.reduce_bpc, nullptr, 0, kMaxReduceBlocks, Out::Clamp},  // above that, reduce_cap() takes kMaxReduceBlocks anyway
+    {"reduce_shape", &g_tuning.reduce_shape, nullptr, 0, 4, Out::Refuse},
+    {"map_u", &g_tuning.map_u, nullptr, 1, 4, Out::Refuse, true},  // 1, 2 or 4
+    {"peel", &g_tuning.peel, nullptr, 0, 2, Out::Refuse},
+    {"unaligned_vector", &g_tuning.unaligned_vector, nullptr, 0, 1, Out::Bool},
+    {"fused_mixed", &g_tuning.fused_mixed, nullptr, 0, 1, Out::Bool},
+    {"mall_mb", nullptr, &g_tuning.mall_mb, 0, kMaxMiB, Out::Clamp},
+    {"inject_shard_failure", &g_tuning.inject_shard_failure, nullptr, 0, INT32_MAX, Out::Refuse},
+    {"inject_pin_refusal", &g_tuning.inject_pin_refusal, nullptr, 0, 1, Out::Bool},
+    {"expr_jit", &g_tuning.expr_jit, nullptr, 0, 2, Out::Clamp},
+    {"expr_fixed", &g_tuning.expr_fixed, nullptr, 0, 1, Out::Bool},
+    {"write_lds_kb", &g_tuning.write_lds_kb, nullptr, 0, 64, Out::Clamp},
+    {"binop_lds_kb", &g_tuning.binop_lds_kb, nullptr, -1, 64, Out::Clamp},
+    {"scalar_lds_kb", &g_tuning.scalar_lds_kb, nullptr, -1, 64, Out::Clamp},
+    {"map_lds_kb", &g_tuning.map_lds_kb, nullptr, 0, 64, Out::Clamp},
+    {"fused_lds_kb", &g_tuning.fused_lds_kb, nullptr, 0, 64, Out::Clamp},
+    {"counts_one_launch", &g_tuning.counts_one_launch, nullptr, 0, 2, Out::Clamp},
+    {"cache_force", &g_tuning.cache_force, nullptr, -1, 255, Out::Refuse},  // -1 off, else the policy bits of up to eight streams
+    {"pool_keep_mb", nullptr, &g_tuning.pool_keep_mb, 0, kMaxMiB, Out::Clamp},
+};
+const Knob* knob_of(const char* key) {
+    for (const Knob& k : kKnobs)
+        if (!std::strcmp(k.key, key)) return &k;
+    return nullptr;
+}
+}  // namespace
+
 int device_cus() { return t_cus; }
 int current_device() { return t_active; }
 
@@ -468,23 +513,9 @@ extern "C" ec_status ec_stat_get(const char* key, int64_t* value) {
     if (!std::strcmp(key, "pool_allocs")) *value = g_pool_allocs.load(std::memory_order_relaxed);
     else if (!std::strcmp(key, "binop_lds_rule_launches")) *value = g_lds_rule_launches.load(std::memory_order_relaxed);
     else if (!std::strncmp(key, "tune.", 5)) {  // the current value of a knob of ec_tune_set, so that a caller can put it back
-        const char* k = key + 5;
-        if (!std::strcmp(k, "binop_variant")) *value = g_tuning.binop_variant;
-        else if (!std::strcmp(k, "reduce_bpc")) *value = g_tuning.reduce_bpc;
-        else if (!std::strcmp(k, "reduce_shape")) *value = g_tuning.reduce_shape;
-        else if (!std::strcmp(k, "map_u")) *value = g_tuning.map_u;
-        else if (!std::strcmp(k, "peel")) *value = g_tuning.peel;
-        else if (!std::strcmp(k, "unaligned_vector")) *value = g_tuning.unaligned_vector;
-        else if (!std::strcmp(k, "fused_mixed")) *value = g_tuning.fused_mixed;
-        else if (!std::strcmp(k, "mall_mb")) *value = g_tuning.mall_mb;
-        else if (!std::strcmp(k, "expr_jit")) *value = g_tuning.expr_jit;
-        else if (!std::strcmp(k, "expr_fixed")) *value = g_tuning.expr_fixed;
-        else if (!std::strcmp(k, "write_lds_kb")) *value = g_tuning.write_lds_kb;
-        else if (!std::strcmp(k, "fused_lds_kb")) *value = g_tuning.fused_lds_kb;
-        else if (!std::strcmp(k, "counts_one_launch")) *value = g_tuning.counts_one_launch;
-        else if (!std::strcmp(k, "cache_force")) *value = g_tuning.cache_force;
-        else if (!std::strcmp(k, "pool_keep_mb")) *value = g_tuning.pool_keep_mb;
-        else return set_error(EC_ERR_ARG, "ec_stat_get: unknown knob '%s'", k);
+        const Knob* kn = knob_of(key + 5);
+        if (!kn) return set_error(EC_ERR_ARG, "ec_stat_get: unknown knob '%s'", key + 5);
+        *value = kn->i ? int64_t(kn->i->load()) : kn->l->load();
     } else if (!std::strcmp(key, "devices")) {
         std::lock_guard<std::mutex> lk(g_mu);
         *value = static_cast<int64_t>(g_devs.size());
@@ -504,30 +535,22 @@ extern "C" ec_status ec_stat_get(const char* key, int64_t* value) {
 // ------------------------------------------------------------------ tuning
 extern "C" ec_status ec_tune_set(const char* key, int64_t value) {
     if (!key) return set_error(EC_ERR_ARG, "ec_tune_set: null key");
-    if (!std::strcmp(key, "binop_variant")) g_tuning.binop_variant = static_cast<int>(value);
-    else if (!std::strcmp(key, "reduce_bpc")) g_tuning.reduce_bpc = value > 0 ? static_cast<int>(value) : 0;
-    else if (!std::strcmp(key, "reduce_shape")) g_tuning.reduce_shape = static_cast<int>(value);
-    else if (!std::strcmp(key, "map_u")) g_tuning.map_u = static_cast<int>(value);
-    else if (!std::strcmp(key, "peel")) g_tuning.peel = static_cast<int>(value);
-    else if (!std::strcmp(key, "unaligned_vector")) g_tuning.unaligned_vector = value != 0;
-    else if (!std::strcmp(key, "fused_mixed")) g_tuning.fused_mixed = static_cast<int>(value);
-    else if (!std::strcmp(key, "mall_mb")) g_tuning.mall_mb = value < 0 ? 0 : value;
-    else if (!std::strcmp(key, "inject_shard_failure")) g_tuning.inject_shard_failure = static_cast<int>(value);
-    else if (!std::strcmp(key, "inject_pin_refusal")) g_tuning.inject_pin_refusal = value != 0;
-    else if (!std::strcmp(key, "expr_fixed")) g_tuning.expr_fixed = value != 0;
-    else if (!std::strcmp(key, "write_lds_kb")) g_tuning.write_lds_kb = value < 0 ? 0 : value > 64 ? 64 : static_cast<int>(value);
-    else if (!std::strcmp(key, "fused_lds_kb")) g_tuning.fused_lds_kb = value < 0 ? 0 : value > 64 ? 64 : static_cast<int>(value);
-    else if (!std::strcmp(key, "binop_lds_kb")) g_tuning.binop_lds_kb = value < 0 ? -1 : value > 64 ? 64 : static_cast<int>(value);
-    else if (!std::strcmp(key, "scalar_lds_kb")) g_tuning.scalar_lds_kb = value < 0 ? -1 : value > 64 ? 64 : static_cast<int>(value);
-    else if (!std::strcmp(key, "map_lds_kb")) g_tuning.map_lds_kb = value < 0 ? 0 : value > 64 ? 64 : static_cast<int>(value);
-    else if (!std::strcmp(key, "counts_one_launch")) g_tuning.counts_one_launch = value < 0 ? 0 : value > 2 ? 2 : static_cast<int>(value);
-    else if (!std::strcmp(key, "cache_force")) g_tuning.cache_force = value < 0 ? -1 : static_cast<int>(value);
-    else if (!std::strcmp(key, "expr_jit")) g_tuning.expr_jit = value < 0 ? 0 : value > 2 ? 2 : static_cast<int>(value);
-    else if (!std::strcmp(key, "pool_keep_mb")) {
-        g_tuning.pool_keep_mb = value < 0 ? 0 : value;
+    const Knob* kn = knob_of(key);
+    if (!kn) return set_error(EC_ERR_ARG, "ec_tune_set: unknown key '%s'", key);
+    // the value stored is the value the launchers act on: nothing narrows through int, nothing out of range is stored as given
+    int64_t v = value;
+    if (kn->out == Out::Bool) v = value != 0;
+    else if (value < kn->lo || value > kn->hi || (kn->pow2 && (value & (value - 1)) != 0)) {
+        if (kn->out == Out::Refuse || (value >= kn->lo && value <= kn->hi))
+            return set_error(EC_ERR_ARG, "ec_tune_set: %s = %lld is outside its accepted values", key, static_cast<long long>(value));
+        v = value < kn->lo ? kn->lo : kn->hi;
+    }
+    if (kn->i) kn->i->store(static_cast<int>(v));
+    else kn->l->store(v);
+    if (kn->l == &g_tuning.pool_keep_mb) {
         std::lock_guard<std::mutex> lk(g_mu);
         for (auto& kv : g_devs)
             if (kv.second.pool) set_pool_threshold(kv.second.pool);
-    } else return set_error(EC_ERR_ARG, "ec_tune_set: unknown key '%s'", key);
+    }
     return EC_OK;
 }

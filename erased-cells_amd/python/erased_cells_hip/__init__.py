@@ -7,9 +7,10 @@
 `raster`   baseline-TIFF band reader (the reference's GDAL adaptor for the fixture shape)
 `sharded`  row-block sharding across ranks + the RCCL all-reduce for min/max and counts; `ShardGroup`: one process, all GPUs
 `wire`     serde/JSON shape of the core types (interop only; parity unpinned)
+`tuned`    `with tuned(knob=value, ...)`: knobs of ec_tune_set for a block, put back on exit
 """
 from . import _ffi, fused, raster, wire
-from ._ffi import EcError, NarrowingError, build, lib
+from ._ffi import EcError, NarrowingError, build, lib, tuned
 from .buffer import (ADD, CELL_TYPES, CT_NAMES, DIV, MUL, NP_DTYPES, SUB, CellBuffer, CellValue, DeviceMem,
                      Float32, Float64, Int8, Int16, Int32, Int64, Mask, MaskedCellBuffer, NoData, UInt8,
                      UInt16, UInt32, UInt64, ParseError, can_fit_into, cell_type_from_str, cell_type_of,

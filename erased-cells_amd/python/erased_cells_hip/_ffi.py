@@ -205,3 +205,38 @@ def check(status: int) -> None:
         L.ec_last_narrowing(C.byref(s), C.byref(d))
         raise NarrowingError(msg, s.value, d.value)
     raise EcError(status, msg)
+
+
+class tuned:
+    """`with ec.tuned(binop_variant=1, map_u=4): ...` — the knobs of `ec_tune_set` set for the block.  Each knob named is put back on exit
+    to the value `ec_stat_get("tune.<knob>")` read on entry (blocks nest); an unknown knob or a value `ec_tune_set` refuses raises EcError
+    with every knob as it was."""
+
+    def __init__(self, **knobs: int):
+        self.knobs = knobs
+        self.previous: dict = {}
+
+    def __enter__(self):
+        L, v = lib(), C.c_int64()
+        previous = {}
+        for key in self.knobs:
+            check(L.ec_stat_get(b"tune." + key.encode(), C.byref(v)))
+            previous[key] = v.value
+        self.previous = {}
+        try:
+            for key, value in self.knobs.items():
+                self.previous[key] = previous[key]
+                check(L.ec_tune_set(key.encode(), value))
+        except BaseException:
+            self._restore()
+            raise
+        return self
+
+    def __exit__(self, *exc):
+        self._restore()
+        return False
+
+    def _restore(self):
+        for key, value in reversed(list(self.previous.items())):
+            check(lib().ec_tune_set(key.encode(), value))
+        self.previous = {}

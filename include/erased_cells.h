@@ -464,15 +464,24 @@ ec_status ec_synth_fill(ec_dtype t, void *dst, size_t n, uint64_t seed, uint64_t
                         double lo, double hi, ec_stream stream);
 /* mask[i] = splitmix64(seed ^ (base+i)) % 100 >= pct_nodata */
 ec_status ec_synth_mask(uint8_t *dst, size_t n, uint64_t seed, uint64_t base, uint32_t pct_nodata, ec_stream stream);
-/* Tuning knobs (each an atomic word: may be set while other host threads launch): "pool_keep_mb" (release threshold
- * of the library's stream-ordered pools), "fused_mixed" (1, default: one-pass kernels for fused chains over mixed
- * cell types; 0: convert to the union type first), "binop_variant" (-1, default: by rule — LDS-staged for an 8-byte operand against one of <= 4 bytes on large rasters; 0 always direct narrow loads; 1 LDS-staged wherever an operand can be staged), "reduce_bpc" (workgroups per CU for reductions; 0, default: as many as are resident at once), "reduce_shape" (A/B launch shapes of min_max, 0 default),
- * "map_u" (16-B groups per lane per tile of the map kernels: 1, 2 or 4), "unaligned_vector" (1, default: vector
- * kernels at any cell offset via unaligned global access; 0: pointers that are not 16-byte aligned run the
- * one-cell-per-lane kernels), "peel" (leading-cell peel of the binop/fused kernels at odd offsets: 0 off, 1 for
- * 1-byte operands (default), 2 also for 2-byte operands).  Measurement knobs (defaults are what ships): "mall_mb",
- * "cache_force", "expr_jit", "expr_fixed", "counts_one_launch", and the occupancy caps "write_lds_kb", "binop_lds_kb", "scalar_lds_kb",
- * "map_lds_kb", "fused_lds_kb" (KiB of unused LDS reserved per workgroup of a kernel family). */
+/* Tuning knobs (each an atomic word: may be set while other host threads launch).  Accepted values in brackets; a value outside
+ * them is SATURATED to the nearer end, or REFUSED (EC_ERR_ARG, the knob unchanged) where so marked; a 0/1 switch stores
+ * value != 0.  The value ec_stat_get("tune.<knob>") reads back is the value the launchers act on.
+ * "pool_keep_mb" [0, 2^20] (MiB: release threshold of the library's stream-ordered pools); "fused_mixed" 0/1 (1, default:
+ * one-pass kernels for fused chains over mixed cell types; 0: convert to the union type first); "binop_variant" {-1, 0, 1},
+ * refused otherwise (-1, default: by rule — LDS-staged for an 8-byte operand against one of <= 4 bytes on large rasters; 0 always
+ * direct narrow loads; 1 LDS-staged wherever an operand can be staged); "reduce_bpc" [0, 4096] (workgroups per CU for reductions;
+ * 0, default: as many as are resident at once); "reduce_shape" {0 .. 4}, refused otherwise (A/B launch shapes of min_max, 0
+ * default); "map_u" {1, 2, 4}, refused otherwise (16-B groups per lane per tile of the map kernels); "unaligned_vector" 0/1 (1,
+ * default: vector kernels at any cell offset via unaligned global access; 0: pointers that are not 16-byte aligned run the
+ * one-cell-per-lane kernels); "peel" {0, 1, 2}, refused otherwise (leading-cell peel of the binop/fused kernels at odd offsets:
+ * 0 off, 1 for 1-byte operands (default), 2 also for 2-byte operands).
+ * Measurement knobs (defaults are what ships): "mall_mb" [0, 2^20] (MiB); "cache_force" [-1, 255], refused
+ * otherwise (-1 off, else the load-policy bits of every launch); "expr_jit" [0, 2]; "expr_fixed" 0/1; "counts_one_launch" [0, 2];
+ * and the occupancy caps "write_lds_kb" [0, 64], "binop_lds_kb" [-1, 64], "scalar_lds_kb" [-1, 64], "map_lds_kb" [0, 64],
+ * "fused_lds_kb" [0, 64] (KiB of unused LDS reserved per workgroup of a kernel family; -1 = the family's rule).
+ * Test hooks (not for production use): "inject_shard_failure" [0, 2^31 - 1], refused otherwise (shard index + 1 whose next job of
+ * a shard group fails with EC_ERR_HIP; 0 off); "inject_pin_refusal" 0/1 (1: every host-memory registration is treated as refused). */
 ec_status ec_tune_set(const char *key, int64_t value);
 /* Counters for tests: "pool_allocs" (ec_alloc_async calls so far, including those the library makes itself — a call
  * that leaves it unchanged allocated nothing), "devices" (initialised devices), "scratch_streams" (streams the

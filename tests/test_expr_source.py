@@ -153,3 +153,20 @@ def test_a_program_is_recognised_by_its_tree_not_by_its_step_list():
     assert _tree([U16], 0, [(ec.ADD, S(0), S(0), 0), (ec.MUL, R(0), R(0), 1)])[0] == "(* (+ S0 S0) (+ S0 S0))"
     # a long chain has no bounded tree
     assert _tree([U16], 1, [(ec.MUL, S(0), K(0), 0)] + [(ec.ADD, R(0), R(0), 0)] * 15)[0].startswith("(none")
+
+
+def test_the_report_names_the_kernel_the_launch_takes():
+    """`ec_expr_source` reports the ahead-of-time kernel by the same width test `expr_fixed_launch` applies: the widths of the streams
+    the TREE reads, not of every stream the program declares.  A dead stream of another width does not keep a program off its
+    straight-line kernel (the launch side of each case: tests/test_gpu_tuning_knobs.py::test_expr_source_and_the_launch_agree)."""
+    U8, U16, F32, F64 = ec.UInt8, ec.UInt16, ec.Float32, ec.Float64
+    ndvi = [(ec.SUB, S(0), S(1), 0), (ec.ADD, S(0), S(1), 1), (ec.DIV, R(0), R(1), 0)]
+    assert _tree([F32, F32], 0, ndvi)[1] == "NDVI"
+    assert _tree([F32, F32, F64], 0, ndvi)[1] == "NDVI", "stream 2 is never read"
+    assert _tree([U8, F32, F32], 0, [(ec.SUB, S(1), S(2), 0), (ec.ADD, S(1), S(2), 1), (ec.DIV, R(0), R(1), 0)])[1] == "NDVI", \
+        "stream 0 is never read"
+    assert _tree([F32, U16], 0, ndvi)[1].startswith("NDVI in the catalogue, but")
+    affine = [(ec.MUL, S(1), K(0), 0), (ec.ADD, R(0), K(1), 0)]
+    assert _tree([U8, F64], 2, affine)[1] == "affine"
+    assert _tree([U16, U16, U16, F64], 0, [(ec.ADD, S(0), S(1), 0), (ec.MUL, R(0), S(2), 0)])[1] == "add-mul"
+    assert _tree([U16, U16, F32, F64], 4, EVI)[1] == "EVI in the catalogue, but the streams differ in width: none"
