@@ -49,7 +49,8 @@ static ec_status launch_binop_pair(const void* l, const void* r, size_t n, doubl
         if (by_rule) lds_rule_launches().fetch_add(1, std::memory_order_relaxed);
         return check_launch(by_rule ? "binop(lds, by rule)" : "binop(lds)");
     }
-    const unsigned head = peel_head(l, sizeof(L), r, sizeof(R), n);
+    const LoadedStream st[2] = {{l, sizeof(L)}, {r, sizeof(R)}};
+    const unsigned head = peel_head(st, 2, n);
     const size_t tiles = (((n - head) >> 1) + size_t(kBlock) * U - 1) / (size_t(kBlock) * U);
     k_binop_direct<L, R, OP, U, kNtStore, kNtLoad><<<grid_for(tiles), kBlock, lds_cap(tuning().binop_lds_kb.load(), sizeof(L) == 8 && sizeof(R) == 8 ? 48 : 0), s>>>(lp, rp, out, n, head | (policy << 8));
     return check_launch("binop(direct)");
@@ -72,7 +73,8 @@ static ec_status launch_masked_pair(const void* l, const uint8_t* lm, const void
         k_masked_binop<L, R, OP, U, kNtStore, kNtLoad, true><<<grid_for(tiles), kBlock, lds_cap(tu.binop_lds_kb.load(), 0), s>>>(lp, lm, rp, rm, out, om, n, 0u);
         return check_launch("masked_binop(lds)");
     }
-    const unsigned head = peel_head(l, sizeof(L), r, sizeof(R), n);
+    const LoadedStream st[2] = {{l, sizeof(L)}, {r, sizeof(R)}};
+    const unsigned head = peel_head(st, 2, n);
     const size_t tiles = (((n - head) >> 1) + size_t(kBlock) * U - 1) / (size_t(kBlock) * U);
     const size_t stream_bytes[4] = {n * sizeof(L), l == r ? 0 : n * sizeof(R), n, lm == rm ? 0 : n};
     unsigned policy = cache_plan(stream_bytes, 4, n * sizeof(double));
@@ -91,7 +93,8 @@ static ec_status launch_scalar(const void* l, double rhs, size_t n, double* out,
         k_binop_scalar_cellwise<L, OP><<<grid_capped((n + kBlock - 1) / kBlock, 8), kBlock, 0, s>>>(lp, rhs, out, n);
         return check_launch("binop_scalar(cellwise)");
     }
-    const unsigned head = peel_head(l, sizeof(L), nullptr, 0, n);
+    const LoadedStream st[1] = {{l, sizeof(L)}};
+    const unsigned head = peel_head(st, 1, n);
     const size_t tiles = (((n - head) >> 1) + size_t(kBlock) * U - 1) / (size_t(kBlock) * U);
     const size_t stream_bytes[1] = {n * sizeof(L)};
     const unsigned policy = cache_plan(stream_bytes, 1, n * sizeof(double));

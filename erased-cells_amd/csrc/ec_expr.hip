@@ -92,47 +92,29 @@ static ec_status prepare_expr(ExprArgs& ea, bool* aligned_out, int* cls, const e
     if (pst != EC_OK) return pst;
     if (!p || (n_scalars > 0 && !scalars)) return set_error(EC_ERR_ARG, "%s: null pointer", what);
     bool aligned = true;
+    LoadedStream st[kExprMaxStreams];
     for (int k = 0; k < n_streams; ++k) {
         if (!p[k]) return set_error(EC_ERR_ARG, "%s: stream %d is null", what, k);
         ea.p[k] = p[k];
         aligned = aligned && aligned_to(p[k], 16);
+        st[k] = {p[k], ecl::size_of(dt[k])};
+        for (int j = 0; j < k && st[k].same_as < 0; ++j)
+            if (p[j] == p[k]) st[k].same_as = j;  // the same buffer again: loaded twice, its bytes count once
+        cls[k] = fused_class_index(st[k].size);
     }
     for (int k = n_streams; k < kExprMaxStreams; ++k) ea.p[k] = p[0];  // never read (class 0)
     for (int k = 0; k < n_scalars; ++k) {
         if (!ecl::valid(scalars[k].dtype)) return set_error(EC_ERR_ARG, "%s: bad dtype of scalar %d", what, k);
         ea.sc[k] = ec_value_to_f64(&scalars[k]);  // impl $trt<R: Into<CellValue>> (src/buffer.rs:346-352): widened once, here
     }
-    if (masks) {
+    if (masks)
         for (int k = 0; k < n_streams; ++k) {
-            if (!masks[k]) return set_error(EC_ERR_ARG, "%s: null mask %d", what, k);
-            bool seen = false;
-            for (int j = 0; j < ea.nmask; ++j) seen = seen || ea.m[j] == masks[k];
-            if (!seen) {
-                ea.m[ea.nmask++] = masks[k];
-                aligned = aligned && aligned_to(masks[k], 16);
-            }
+            const ec_status mst = add_mask(masks[k], k, what, ea.m, &ea.nmask, &aligned);
+            if (mst != EC_OK) return mst;
         }
-    }
     *aligned_out = aligned;
-    // peel one leading cell when that puts more of the 1-byte streams on even addresses (peel_head's rule)
-    unsigned c0 = 0, c1 = 0;
-    size_t stream_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int k = 0; k < n_streams; ++k) {
-        const size_t bytes = ecl::size_of(dt[k]);
-        c0 += peel_cost(p[k], bytes, 0);
-        c1 += peel_cost(p[k], bytes, 1);
-        cls[k] = fused_class_index(bytes);
-        stream_bytes[k] = n * bytes;
-        for (int j = 0; j < k; ++j)
-            if (p[j] == p[k]) stream_bytes[k] = 0;  // the same buffer again: its bytes count once (policy copied below)
-    }
-    for (int j = 0; j < ea.nmask; ++j) stream_bytes[4 + j] = n;
-    ea.head = (n >= 2 && tuning().peel && c1 < c0) ? 1 : 0;
-    unsigned policy = cache_plan(stream_bytes, 8, n * sizeof(double));
-    for (int k = 1; k < n_streams; ++k)
-        for (int j = 0; j < k; ++j)
-            if (p[j] == p[k]) policy = (policy & ~(1u << k)) | (((policy >> j) & 1u) << k);  // one buffer, one policy
-    ea.cacheable = static_cast<uint8_t>(policy);
+    ea.head = static_cast<uint8_t>(peel_head(st, n_streams, n));
+    ea.cacheable = static_cast<uint8_t>(stream_policy(st, ea.nmask, n));
     return EC_OK;
 }
 
@@ -165,8 +147,6 @@ static ec_status launch_expr(const ec_dtype* dt, const void* const* p, int32_t n
     if (jst != EC_OK) return jst;
     if (compiled) return check_launch("expr(compiled)");
     g_interpreted.fetch_add(1, std::memory_order_relaxed);
-    const size_t per_tile = size_t(kBlock) * kExprU;
-    const unsigned grid = grid_for((((n - ea.head) >> 1) + per_tile - 1) / per_tile);
     ExprKernel kern = nullptr;
     switch (cls[0]) {
         case 1: kern = expr_kernel<1>(cls[1], cls[2], cls[3]); break;
@@ -175,7 +155,7 @@ static ec_status launch_expr(const ec_dtype* dt, const void* const* p, int32_t n
         default: kern = expr_kernel<8>(cls[1], cls[2], cls[3]); break;
     }
     if (!kern) return set_error(EC_ERR_ARG, "%s: no kernel for stream classes %d %d %d %d", what, cls[0], cls[1], cls[2], cls[3]);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), static_cast<unsigned>(tuning().fused_lds_kb.load()) << 10, s, ea, out, out_mask, n);
+    launch_stream_tile<kExprU>(kern, ea.head, n, s, ea, out, out_mask, n);
     return check_launch("expr");
 }
 

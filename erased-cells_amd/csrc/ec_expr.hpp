@@ -17,7 +17,8 @@
 // refused and the caller evaluates a sub-tree eagerly first.
 //
 // Kernel family: k_expr<C0,C1,C2,C3>, stream load classes packed (a class 0 only after the last stream): 4 + 16 + 64 +
-// 256 = 340 kernels.  Load policy, tile shape (2 pairs per lane), two fronts, nt stores: as k_fused_any.
+// 256 = 340 kernels.  Load policy, tile grid, two fronts, nt stores and the mask phase: the frame of the one-pass kernels
+// (ec_stream_tile.hpp), shared with k_fused_any and k_expr_fixed.
 #pragma once
 
 #include "ec_fused_any.hpp"
@@ -31,10 +32,7 @@ constexpr int kRefStream0 = 0, kRefReg0 = 4, kRefScalar0 = 8, kRefEnd = 16;
 // so more cells per wave amortise the decode — but the register file costs 16 VGPRs per cell and the waves of a SIMD must
 // still cover each other's scalar-branch latency.  Measured on EVI at 16384² (profiles/r03/expr_kernel.md):
 //   2 pairs (100 VGPRs, 5 waves/SIMD) 1.070 ms;  3 pairs (3 waves/SIMD) 0.992 ms;  4 pairs (188 VGPRs, 2 waves/SIMD) 1.139 ms.
-#ifndef EC_EXPR_U
-#define EC_EXPR_U 3
-#endif
-constexpr int kExprU = EC_EXPR_U;
+constexpr int kExprU = 3;
 
 struct ExprArgs {
     const void* p[kExprMaxStreams];
@@ -189,93 +187,21 @@ __device__ __forceinline__ double expr_one_cell(const ExprArgs& ea, size_t i) {
     return o[0];
 }
 
-// AND of the distinct masks of the streams (src/masked/masked_buffer.rs:333 applied at every step of the eager chain)
-__device__ __forceinline__ void expr_mask_phase(const ExprArgs& ea, uint8_t* __restrict__ out_mask, size_t n) {
-    if (ea.nmask > 0) {
-        const size_t ngroups = n / 16;
-        const size_t stride = size_t(gridDim.x) * kBlock;
-        u32x4* __restrict__ om = reinterpret_cast<u32x4*>(out_mask);
-        for (size_t g = size_t(blockIdx.x) * kBlock + threadIdx.x; g < ngroups; g += stride) {
-            u32x4 acc = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-            for (int k = 0; k < ea.nmask; ++k) {
-                const u32x4* mk = reinterpret_cast<const u32x4*>(ea.m[k]) + g;
-                u32x4 x;
-                policy_arms<1>(ea.cacheable >> (4 + k), [&](auto bits) { x = load_vec<!(decltype(bits)::value & 1u)>(mk); });
-                acc &= x;
-            }
-            mask_store(acc, om + g);
-        }
-        if (blockIdx.x == 0)
-            for (size_t i = ngroups * 16 + threadIdx.x; i < n; i += kBlock) {
-                uint8_t acc = ld_cell(ea.m[0] + i);
-                for (int k = 1; k < ea.nmask; ++k) acc &= ld_cell(ea.m[k] + i);
-                st_cell(acc, out_mask + i);
-            }
-    }
-}
-
 template <int C0, int C1, int C2, int C3>
 __global__ __launch_bounds__(kBlock) void k_expr(ExprArgs ea, double* __restrict__ out, uint8_t* __restrict__ out_mask, size_t n) {
-    constexpr int U = kExprU;
-    constexpr int NC = 2 * U;
-    const unsigned head = ea.head;
-    const size_t npairs = (n - head) >> 1;
-    constexpr size_t TILE = size_t(kBlock) * U;
-    const size_t tile = two_front_tile();
-    const size_t base = tile * TILE + threadIdx.x;
-    const bool full = tile * TILE + TILE <= npairs;
-    D2* __restrict__ op = reinterpret_cast<D2*>(out + head);
-    const char* b0 = static_cast<const char*>(ea.p[0]) + size_t(head) * C0;
-    const char* b1 = static_cast<const char*>(ea.p[1]) + size_t(head) * C1;
-    const char* b2 = static_cast<const char*>(ea.p[2]) + size_t(head) * C2;
-    const char* b3 = static_cast<const char*>(ea.p[3]) + size_t(head) * C3;
-
-    typename raw_pair<C0>::type q0[U] = {};
-    typename raw_pair<C1>::type q1[U] = {};
-    typename raw_pair<C2>::type q2[U] = {};
-    typename raw_pair<C3>::type q3[U] = {};
-    if (full) {
-        constexpr int kStreams = (C0 != 0) + (C1 != 0) + (C2 != 0) + (C3 != 0);  // packed: the policy bits are bits 0..kStreams-1
-        policy_arms<kStreams>(ea.cacheable, [&](auto bits) {
-            constexpr unsigned B = decltype(bits)::value;
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const size_t pr = base + size_t(j) * kBlock;
-                if constexpr (C0 != 0) q0[j] = load_vec<!(B & 1u)>(reinterpret_cast<const typename raw_pair<C0>::type*>(b0) + pr);
-                if constexpr (C1 != 0) q1[j] = load_vec<!(B & 2u)>(reinterpret_cast<const typename raw_pair<C1>::type*>(b1) + pr);
-                if constexpr (C2 != 0) q2[j] = load_vec<!(B & 4u)>(reinterpret_cast<const typename raw_pair<C2>::type*>(b2) + pr);
-                if constexpr (C3 != 0) q3[j] = load_vec<!(B & 8u)>(reinterpret_cast<const typename raw_pair<C3>::type*>(b3) + pr);
-            }
-        });
-    } else {
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const size_t pr = base + size_t(j) * kBlock;
-            if (pr < npairs) {
-                if constexpr (C0 != 0) q0[j] = nt_load(reinterpret_cast<const typename raw_pair<C0>::type*>(b0) + pr);
-                if constexpr (C1 != 0) q1[j] = nt_load(reinterpret_cast<const typename raw_pair<C1>::type*>(b1) + pr);
-                if constexpr (C2 != 0) q2[j] = nt_load(reinterpret_cast<const typename raw_pair<C2>::type*>(b2) + pr);
-                if constexpr (C3 != 0) q3[j] = nt_load(reinterpret_cast<const typename raw_pair<C3>::type*>(b3) + pr);
-            }
-        }
-    }
-    double v0[NC] = {}, v1[NC] = {}, v2[NC] = {}, v3[NC] = {}, o[NC];
-    if constexpr (C0 != 0) widen_pairs<C0, U>(q0, ea.dt[0] >> 2, v0);
-    if constexpr (C1 != 0) widen_pairs<C1, U>(q1, ea.dt[1] >> 2, v1);
-    if constexpr (C2 != 0) widen_pairs<C2, U>(q2, ea.dt[2] >> 2, v2);
-    if constexpr (C3 != 0) widen_pairs<C3, U>(q3, ea.dt[3] >> 2, v3);
-    expr_run<NC, (C0 != 0) + (C1 != 0) + (C2 != 0) + (C3 != 0)>(ea, v0, v1, v2, v3, o);
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        const size_t pr = base + size_t(j) * kBlock;
-        if (full || pr < npairs) nt_store(D2{o[2 * j], o[2 * j + 1]}, op + pr);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 2) {  // the peeled head cell (lane 0) and the odd tail cell (lane 1)
-        const bool do_it = threadIdx.x == 0 ? head != 0 : ((n - head) & 1) != 0;
-        const size_t i = threadIdx.x == 0 ? 0 : n - 1;
-        if (do_it) st_cell(expr_one_cell(ea, i), out + i);
-    }
-    expr_mask_phase(ea, out_mask, n);
+    // the streams are packed (a class 0 only after the last stream): ea.cacheable's bit k is stream k's
+    stream_tile<kExprU, kExprU, C0, C1, C2, C3>(
+        ea, ea.p, ea.cacheable,
+        [&](auto np, const auto& q0, const auto& q1, const auto& q2, const auto& q3, auto& o) {
+            constexpr int NP = decltype(np)::value, NC = 2 * NP;
+            double v0[NC] = {}, v1[NC] = {}, v2[NC] = {}, v3[NC] = {};
+            if constexpr (C0 != 0) widen_pairs<C0, NP>(q0, ea.dt[0] >> 2, v0);
+            if constexpr (C1 != 0) widen_pairs<C1, NP>(q1, ea.dt[1] >> 2, v1);
+            if constexpr (C2 != 0) widen_pairs<C2, NP>(q2, ea.dt[2] >> 2, v2);
+            if constexpr (C3 != 0) widen_pairs<C3, NP>(q3, ea.dt[3] >> 2, v3);
+            expr_run<NC, (C0 != 0) + (C1 != 0) + (C2 != 0) + (C3 != 0)>(ea, v0, v1, v2, v3, o);
+        },
+        [&](size_t i) { return expr_one_cell(ea, i); }, out, out_mask, n);
 }
 
 // Any alignment: one cell per lane (the comparison path behind ec_tune_set("unaligned_vector", 0)).
@@ -284,11 +210,7 @@ __global__ __launch_bounds__(kBlock) void k_expr_cellwise(ExprArgs ea, double* _
     const size_t stride = size_t(gridDim.x) * kBlock;
     for (size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
         out[i] = expr_one_cell(ea, i);
-        if (ea.nmask > 0) {
-            uint8_t acc = ea.m[0][i];
-            for (int k = 1; k < ea.nmask; ++k) acc &= ea.m[k][i];
-            out_mask[i] = acc;
-        }
+        if (ea.nmask > 0) out_mask[i] = mask_and_cell<false>(ea, i);
     }
 }
 

@@ -131,89 +131,45 @@ __device__ __forceinline__ void fixed_run(const double (&s)[kExprMaxStreams][N],
 }
 
 // Tile shape of the compiled form (ec_expr_jit.hip): 2 pairs per lane, one workgroup per tile, two fronts, loads under the launch's
-// policy, streaming stores; the peeled head cell / odd tail cell and the masks' AND are the interpreter's code (ec_expr.hpp), on the
-// caller's own program — same cells either way.
+// policy, streaming stores — the frame of the one-pass kernels (ec_stream_tile.hpp); the peeled head cell / odd tail cell and the masks'
+// AND run the interpreter's code (ec_expr.hpp) on the caller's own program — same cells either way.
 constexpr int kFixedU = 2;
+
+// Long programs run chunk by chunk (the pair of cells of one store): a chunk's steps run and its store leaves as soon as the chunk's
+// loads are back, while the next chunk's may still be in flight — EVI 0.797 against 0.789 over the tile's four cells at once; the two-
+// and three-step programs lose half a point that way (fewer independent chains per step) and run over the whole tile
+// (profiles/r04/fixed_chunked_ab.md).
+template <typename P>
+constexpr int fixed_chunk_pairs() { return P::nsteps > 3 ? 1 : kFixedU; }
 
 template <int ID, int C>
 __global__ __launch_bounds__(kBlock) void k_expr_fixed(ExprArgs ea, FixedMap fm, double* __restrict__ out, uint8_t* __restrict__ out_mask, size_t n) {
     using P = FixedProg<ID>;
-    constexpr int U = kFixedU, NC = 2 * U, NS = P::nstreams;
-    using Raw = typename raw_pair<C>::type;
-    const unsigned head = ea.head;
-    const size_t npairs = (n - head) >> 1;
-    constexpr size_t TILE = size_t(kBlock) * U;
-    const size_t tile = two_front_tile();
-    const size_t base = tile * TILE + threadIdx.x;
-    const bool full = tile * TILE + TILE <= npairs;
-    D2* __restrict__ op = reinterpret_cast<D2*>(out + head);
-    const Raw* b[NS];
+    constexpr int NS = P::nstreams;
+    const void* p[4];
     int kind[NS];
 #pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        b[k] = reinterpret_cast<const Raw*>(static_cast<const char*>(ea.p[fm.stream[k]]) + size_t(head) * C);
-        kind[k] = ea.dt[fm.stream[k]] >> 2;
-    }
+    for (int k = 0; k < 4; ++k) p[k] = ea.p[fm.stream[k]];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) kind[k] = ea.dt[fm.stream[k]] >> 2;
     double sc[kExprMaxScalars] = {};
 #pragma unroll
     for (int k = 0; k < P::nscalars; ++k) sc[k] = ea.sc[fm.scalar[k]];
-
-    Raw q[NS][U] = {};
-    if (full) {
-        policy_arms<NS>(fm.cacheable, [&](auto bits) {
-            constexpr unsigned B = decltype(bits)::value;
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const size_t pr = base + size_t(j) * kBlock;
-                q[0][j] = load_vec<!(B & 1u)>(b[0] + pr);
-                if constexpr (NS > 1) q[1][j] = load_vec<!(B & 2u)>(b[1] + pr);
-                if constexpr (NS > 2) q[2][j] = load_vec<!(B & 4u)>(b[2] + pr);
-            }
-        });
-    } else {
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const size_t pr = base + size_t(j) * kBlock;
-            if (pr < npairs)
-#pragma unroll
-                for (int k = 0; k < NS; ++k) q[k][j] = nt_load(b[k] + pr);
-        }
-    }
     constexpr int last = P::steps[P::nsteps - 1].dst;
-    // Long programs run chunk by chunk (the pair of cells of one store): a chunk's steps run and its store leaves as soon as the chunk's
-    // loads are back, while the next chunk's may still be in flight — EVI 0.797 against 0.789 over the tile's four cells at once; the two-
-    // and three-step programs lose half a point that way (fewer independent chains per step) and run over the whole tile
-    // (profiles/r04/fixed_chunked_ab.md).
-    if constexpr (P::nsteps > 3) {
+    constexpr int C1 = NS > 1 ? C : 0, C2 = NS > 2 ? C : 0;  // the catalogue's programs read at most three streams
+    stream_tile<kFixedU, fixed_chunk_pairs<P>(), C, C1, C2, 0>(
+        ea, p, fm.cacheable,
+        [&](auto np, const auto& q0, const auto& q1, const auto& q2, const auto&, auto& o) {
+            constexpr int NC = 2 * decltype(np)::value;
+            double s[kExprMaxStreams][NC] = {}, r[kExprRegs][NC];
+            widen_pairs<C, decltype(np)::value>(q0, kind[0], s[0]);
+            if constexpr (NS > 1) widen_pairs<C, decltype(np)::value>(q1, kind[1], s[1]);
+            if constexpr (NS > 2) widen_pairs<C, decltype(np)::value>(q2, kind[2], s[2]);
+            fixed_run<P, C, NC>(s, sc, r);
 #pragma unroll
-    for (int j = 0; j < U; ++j) {
-        double s[kExprMaxStreams][2] = {}, r[kExprRegs][2];
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            const Raw one[1] = {q[k][j]};
-            widen_pairs<C, 1>(one, kind[k], s[k]);
-        }
-        fixed_run<P, C, 2>(s, sc, r);
-        const size_t pr = base + size_t(j) * kBlock;
-        if (full || pr < npairs) nt_store(D2{r[last][0], r[last][1]}, op + pr);
-    }
-    } else {
-    double s[kExprMaxStreams][NC] = {}, r[kExprRegs][NC];
-#pragma unroll
-    for (int k = 0; k < NS; ++k) widen_pairs<C, U>(q[k], kind[k], s[k]);
-    fixed_run<P, C, NC>(s, sc, r);
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        const size_t pr = base + size_t(j) * kBlock;
-        if (full || pr < npairs) nt_store(D2{r[last][2 * j], r[last][2 * j + 1]}, op + pr);
-    }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 2) {  // the peeled head cell (lane 0) and the odd tail cell (lane 1)
-        const bool do_it = threadIdx.x == 0 ? head != 0 : ((n - head) & 1) != 0;
-        const size_t i = threadIdx.x == 0 ? 0 : n - 1;
-        if (do_it) st_cell(expr_one_cell(ea, i), out + i);
-    }
-    expr_mask_phase(ea, out_mask, n);
+            for (int i = 0; i < NC; ++i) o[i] = r[last][i];
+        },
+        [&](size_t i) { return expr_one_cell(ea, i); }, out, out_mask, n);
 }
 
 // Host side (ec_expr_fixed.hip): *launched = true when the program is one of the catalogue's and its kernel was launched.

@@ -288,7 +288,7 @@ std::string expr_jit_source(const ExprArgs& ea, bool reduce) {
     }
     o += "            double q[1];\n            run<1>(a0, a1, a2, a3, c0, c1, c2, c3, c4, c5, c6, c7, q);\n"
          "            __builtin_nontemporal_store(q[0], out + i);\n        }\n    }\n";
-    if (ea.nmask > 0) {  // the AND of the distinct masks (ec_expr.hpp expr_mask_phase), 16 mask bytes per lane, its own lane map
+    if (ea.nmask > 0) {  // the AND of the distinct masks (ec_stream_tile.hpp mask_phase), 16 mask bytes per lane, its own lane map
         o += "    {\n        const unsigned long ngroups = n / 16, stride = (unsigned long)gridDim.x * 256ul;\n"
              "        for (unsigned long g = (unsigned long)blockIdx.x * 256ul + threadIdx.x; g < ngroups; g += stride) {\n"
              "            U4 acc = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};\n";

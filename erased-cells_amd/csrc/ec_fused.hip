@@ -5,42 +5,23 @@
 
 #include "ec_fused_any.hpp"
 #include "ec_lattice.hpp"
-#include "ec_runtime.hpp"
 
 using namespace ecd;
-
-// peel one leading cell when that puts more of the 1-byte operand streams on even addresses (peel_head's rule)
-static unsigned fused_head(const FusedArgs& fa, size_t n) {
-    unsigned c0 = 0, c1 = 0;
-    for (int k = 0; k < 4; ++k)
-        if (!fa.is_sc[k] && fa.alias[k] == k) {
-            c0 += peel_cost(fa.p[k], ecl::size_of(fa.dt[k]), 0);
-            c1 += peel_cost(fa.p[k], ecl::size_of(fa.dt[k]), 1);
-        }
-    return (n >= 2 && tuning().peel && c1 < c0) ? 1u : 0u;
-}
 
 // Any mix of operand cell types in one pass: the kernel is picked by the byte width of each slot's own stream
 // (0: the slot is a scalar, an alias of an earlier slot, or the unused w of a three-operand chain).
 static ec_status launch_fused_any(FusedArgs& fa, int nops, size_t n, double* out, uint8_t* out_mask, hipStream_t s) {
+    LoadedStream st[4];
     int cls[4];
     bool small = fa.o2 == EC_DIV && (fa.o1 == EC_ADD || fa.o1 == EC_SUB) && (fa.o3 == EC_ADD || fa.o3 == EC_SUB || fa.o3 == kOpNone);
-    size_t narrowest = 8;
     for (int k = 0; k < 4; ++k) {
-        const bool own = k < nops && !fa.is_sc[k] && fa.alias[k] == k;
-        const size_t bytes = own ? ecl::size_of(fa.dt[k]) : 0;
-        cls[k] = fused_class_index(bytes);
-        if (own && bytes < narrowest) narrowest = bytes;
+        if (k < nops && !fa.is_sc[k] && fa.alias[k] == k) st[k] = {fa.p[k], ecl::size_of(fa.dt[k])};
+        cls[k] = fused_class_index(st[k].size);
         if (k < nops) small = small && !fa.is_sc[k] && ecl::is_integral(fa.dt[k]) && ecl::size_of(fa.dt[k]) <= 2;
     }
     fa.small = small ? 1 : 0;
-    fa.head = static_cast<uint8_t>(fused_head(fa, n));
-    size_t stream_bytes[8];
-    for (int k = 0; k < 4; ++k) stream_bytes[k] = n * size_t(fused_class_bytes(cls[k]));  // 0: no stream of its own
-    for (int j = 0; j < 4; ++j) stream_bytes[4 + j] = j < fa.nmask ? n : 0;
-    fa.cacheable = static_cast<uint8_t>(cache_plan(stream_bytes, 8, n * sizeof(double)));
-    const size_t per_tile = size_t(kBlock) * fused_u(narrowest);
-    const unsigned grid = grid_for((((n - fa.head) >> 1) + per_tile - 1) / per_tile);
+    fa.head = static_cast<uint8_t>(peel_head(st, 4, n));
+    fa.cacheable = static_cast<uint8_t>(stream_policy(st, fa.nmask, n));
     FusedAnyKernel kern = nullptr;
     switch (cls[0]) {
         case 0: kern = fused_any_kernel<0>(cls[1], cls[2], cls[3]); break;
@@ -50,7 +31,7 @@ static ec_status launch_fused_any(FusedArgs& fa, int nops, size_t n, double* out
         default: kern = fused_any_kernel<8>(cls[1], cls[2], cls[3]); break;
     }
     if (!kern) return set_error(EC_ERR_ARG, "ec_fused: no kernel for load classes %d %d %d %d", cls[0], cls[1], cls[2], cls[3]);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), static_cast<unsigned>(tuning().fused_lds_kb.load()) << 10, s, fa, out, out_mask, n);
+    launch_stream_tile<kFusedU>(kern, fa.head, n, s, fa, out, out_mask, n);
     return check_launch("fused(any)");
 }
 
@@ -92,13 +73,8 @@ static ec_status launch_fused(int o1, int o2, int o3, const ec_dtype dt[4], cons
         aligned = aligned && aligned_to(out_mask, 16);
         for (int k = 0; k < nops; ++k) {
             if (fa.is_sc[k]) continue;  // a scalar carries no mask (masked_buffer.rs:353-364)
-            if (!masks[k]) return set_error(EC_ERR_ARG, "ec_masked_fused: null mask %d", k);
-            bool seen = false;
-            for (int j = 0; j < fa.nmask; ++j) seen = seen || fa.m[j] == masks[k];
-            if (!seen) {
-                fa.m[fa.nmask++] = masks[k];
-                aligned = aligned && aligned_to(masks[k], 16);
-            }
+            const ec_status mst = add_mask(masks[k], k, "ec_masked_fused", fa.m, &fa.nmask, &aligned);
+            if (mst != EC_OK) return mst;
         }
     }
     if (!aligned) {

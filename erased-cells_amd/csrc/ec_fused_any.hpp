@@ -32,16 +32,6 @@ constexpr int kFusedClasses = 5;  // class index -> cell bytes
 __host__ __device__ constexpr int fused_class_bytes(int idx) { return idx == 0 ? 0 : idx == 1 ? 1 : idx == 2 ? 2 : idx == 3 ? 4 : 8; }
 inline int fused_class_index(size_t bytes) { return bytes == 0 ? 0 : bytes == 1 ? 1 : bytes == 2 ? 2 : bytes == 4 ? 3 : 4; }
 
-// what a lane loads for one PAIR of cells of byte width C — always unsigned words (1-byte cells as <2 x i8> would
-// lose the non-temporal flag, ec_device.hpp)
-struct no_stream {};
-template <int C> struct raw_pair;
-template <> struct raw_pair<0> { using type = no_stream; };
-template <> struct raw_pair<1> { using type = uint16_t; };
-template <> struct raw_pair<2> { using type = uint32_t; };
-template <> struct raw_pair<4> { using type = vec<uint32_t, 2>; };
-template <> struct raw_pair<8> { using type = vec<uint32_t, 4>; };
-
 // cell kinds (dtype code >> 2: EC_U8..EC_U64 = 0..3, EC_I8..EC_I64 = 4..7, EC_F32 / EC_F64 = 8, 9)
 constexpr int kKindUnsigned = 0, kKindSigned = 1, kKindFloat = 2;
 
@@ -118,24 +108,12 @@ __device__ __forceinline__ void apply_tile(int op, const double (&a)[N], const d
     else cell_op_n<EC_DIV, true, false, N>(a, b, r);
 }
 
-__host__ __device__ constexpr int fused_any_min_class(int a, int b, int c, int d) {
-    int m = 16;
-    if (a && a < m) m = a;
-    if (b && b < m) m = b;
-    if (c && c < m) m = c;
-    if (d && d < m) m = d;
-    return m == 16 ? 8 : m;
-}
-
 // FusedArgs as the same-type kernel uses them, read this way here:
 //   dt[k]     cell type of slot k (kind = dt >> 2)
 //   alias[k]  j < k: slot k is the same buffer (and type) as slot j;  k: its own stream
 //   is_sc[k]  slot k is the scalar sc[k]
 //   small     every slot is a buffer of ≤16-bit integer cells and the chain has the NDVI shape (x ± y) / (z ± w | z):
 //             the 2-add + 6-instruction exact divide of ec_fused_kernels.hpp (proven on the whole operand square)
-#ifndef EC_FUSED_CHUNKED
-#define EC_FUSED_CHUNKED 0  // build-time A/B switch: 1 = the expression runs chunk by chunk with each chunk's store right behind it
-#endif
 
 // (x o1 y) o2 (z o3 w) for the 2 NP cells of NP loaded pairs per slot: widening by launch-uniform kind, class-0 slots filled from an earlier
 // slot or a scalar, the ops as wave-uniform switches around the cells.
@@ -209,93 +187,32 @@ __device__ __forceinline__ void fused_any_cells(const FusedArgs& fa, const typen
     }
 }
 
+// Pairs per lane per tile of k_fused_any.  2 for every mix of operand widths (tools/tune_fused_any.hip built with 1 / 2 /
+// by-narrowest-stream 4 pairs: profiles/r03/tune_fused_any_u*.log — NDVI u16 0.71 / 0.81 / 0.81 of peak, NDVI u16 + f32
+// 0.71 / 0.81 / 0.68, (u16*u16)+(f32*f32) 0.73 / 0.81 / 0.64, config 3 0.83 / 0.79 / 0.76).
+constexpr int kFusedU = 2;
+
+// The chain runs over the tile's 2 U cells at once.  Chunk by chunk — the pair of cells of one 16-byte store — with each chunk's store
+// right behind it (the form that gained 0.5-1 % in k_binop_direct's short divide and in the built-in EVI kernel) gains nothing here
+// that exceeds the run-to-run spread: NDVI u16 0.824 / 0.824 against 0.829 / 0.809, NDVI u16 + f32 0.8225 / 0.8255 against 0.8145 /
+// 0.8253, config 3 fused 0.744 / 0.770 against 0.767 / 0.766; profiles/r04/fixed_chunked_ab.md.
 template <int CX, int CY, int CZ, int CW>
 __global__ __launch_bounds__(kBlock) void k_fused_any(FusedArgs fa, double* __restrict__ out, uint8_t* __restrict__ out_mask, size_t n) {
-    constexpr int U = fused_u(size_t(fused_any_min_class(CX, CY, CZ, CW)));  // pairs per lane per tile (2: ec_fused_kernels.hpp)
-    constexpr int NC = 2 * U;
-    const unsigned head = fa.head;
-    const size_t npairs = (n - head) >> 1;
-    constexpr size_t TILE = size_t(kBlock) * U;
-    const size_t tile = two_front_tile();
-    const size_t base = tile * TILE + threadIdx.x;
     const bool has_w = fa.o3 != kOpNone;
-    const bool full = tile * TILE + TILE <= npairs;
-    D2* __restrict__ op = reinterpret_cast<D2*>(out + head);
-    // first cell of the pair grid of each stream
-    const char* bx = static_cast<const char*>(fa.p[0]) + size_t(head) * CX;
-    const char* by = static_cast<const char*>(fa.p[1]) + size_t(head) * CY;
-    const char* bz = static_cast<const char*>(fa.p[2]) + size_t(head) * CZ;
-    const char* bw = static_cast<const char*>(fa.p[3]) + size_t(head) * CW;
-
-    typename raw_pair<CX>::type rx[U] = {};
-    typename raw_pair<CY>::type ry[U] = {};
-    typename raw_pair<CZ>::type rz[U] = {};
-    typename raw_pair<CW>::type rw[U] = {};
-    if (full) {
-        // launch-uniform load policy (policy_arms, ec_device.hpp): the bits of the slots that HAVE a stream, packed
-        constexpr int kStreams = (CX != 0) + (CY != 0) + (CZ != 0) + (CW != 0);
-        constexpr int kBitY = (CX != 0), kBitZ = kBitY + (CY != 0), kBitW = kBitZ + (CZ != 0);
-        unsigned packed = 0;
-        if constexpr (CX != 0) packed |= (fa.cacheable & 1u);
-        if constexpr (CY != 0) packed |= ((fa.cacheable >> 1) & 1u) << kBitY;
-        if constexpr (CZ != 0) packed |= ((fa.cacheable >> 2) & 1u) << kBitZ;
-        if constexpr (CW != 0) packed |= ((fa.cacheable >> 3) & 1u) << kBitW;
-        policy_arms<kStreams>(packed, [&](auto bits) {
-            constexpr unsigned B = decltype(bits)::value;
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const size_t pr = base + size_t(j) * kBlock;
-                if constexpr (CX != 0) rx[j] = load_vec<!(B & 1u)>(reinterpret_cast<const typename raw_pair<CX>::type*>(bx) + pr);
-                if constexpr (CY != 0) ry[j] = load_vec<!((B >> kBitY) & 1u)>(reinterpret_cast<const typename raw_pair<CY>::type*>(by) + pr);
-                if constexpr (CZ != 0) rz[j] = load_vec<!((B >> kBitZ) & 1u)>(reinterpret_cast<const typename raw_pair<CZ>::type*>(bz) + pr);
-                if constexpr (CW != 0) rw[j] = load_vec<!((B >> kBitW) & 1u)>(reinterpret_cast<const typename raw_pair<CW>::type*>(bw) + pr);
-            }
-        });
-    } else {
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const size_t pr = base + size_t(j) * kBlock;
-            if (pr < npairs) {
-                if constexpr (CX != 0) rx[j] = nt_load(reinterpret_cast<const typename raw_pair<CX>::type*>(bx) + pr);
-                if constexpr (CY != 0) ry[j] = nt_load(reinterpret_cast<const typename raw_pair<CY>::type*>(by) + pr);
-                if constexpr (CZ != 0) rz[j] = nt_load(reinterpret_cast<const typename raw_pair<CZ>::type*>(bz) + pr);
-                if constexpr (CW != 0) rw[j] = nt_load(reinterpret_cast<const typename raw_pair<CW>::type*>(bw) + pr);
-            }
-        }
-    }
-    // Over the tile's 2 U cells at once.  (EC_FUSED_CHUNKED 1: chunk by chunk — the pair of cells of one 16-byte store — with each chunk's store
-    // right behind it, the form that gained 0.5-1 % in k_binop_direct's short divide and in the built-in EVI kernel.  Here it gains nothing
-    // that exceeds the run-to-run spread: NDVI u16 0.824 / 0.824 against 0.829 / 0.809, NDVI u16 + f32 0.8225 / 0.8255 against 0.8145 /
-    // 0.8253, config 3 fused 0.744 / 0.770 against 0.767 / 0.766; profiles/r04/fixed_chunked_ab.md.)
-#if EC_FUSED_CHUNKED
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        const typename raw_pair<CX>::type x1[1] = {rx[j]};
-        const typename raw_pair<CY>::type y1[1] = {ry[j]};
-        const typename raw_pair<CZ>::type z1[1] = {rz[j]};
-        const typename raw_pair<CW>::type w1[1] = {rw[j]};
-        double o[2];
-        fused_any_cells<CX, CY, CZ, CW, 1>(fa, x1, y1, z1, w1, has_w, o);
-        const size_t pr = base + size_t(j) * kBlock;
-        if (full || pr < npairs) nt_store(D2{o[0], o[1]}, op + pr);
-    }
-#else
-    double o[NC];
-    fused_any_cells<CX, CY, CZ, CW, U>(fa, rx, ry, rz, rw, has_w, o);
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        const size_t pr = base + size_t(j) * kBlock;
-        if (full || pr < npairs) nt_store(D2{o[2 * j], o[2 * j + 1]}, op + pr);
-    }
-#endif
-    if (blockIdx.x == 0 && threadIdx.x < 2) {  // the peeled head cell (lane 0) and the odd tail cell (lane 1)
-        const bool do_it = threadIdx.x == 0 ? head != 0 : ((n - head) & 1) != 0;
-        const size_t i = threadIdx.x == 0 ? 0 : n - 1;
-        if (do_it)
-            st_cell(fused_cell(fa, operand_cell(fa, 0, i), operand_cell(fa, 1, i), operand_cell(fa, 2, i),
-                               has_w ? operand_cell(fa, 3, i) : 0.0), out + i);
-    }
-    fused_mask_phase(fa, out_mask, n);
+    // the policy bits of the slots that HAVE a stream, packed
+    constexpr int kBitY = (CX != 0), kBitZ = kBitY + (CY != 0), kBitW = kBitZ + (CZ != 0);
+    unsigned packed = 0;
+    if constexpr (CX != 0) packed |= (fa.cacheable & 1u);
+    if constexpr (CY != 0) packed |= ((fa.cacheable >> 1) & 1u) << kBitY;
+    if constexpr (CZ != 0) packed |= ((fa.cacheable >> 2) & 1u) << kBitZ;
+    if constexpr (CW != 0) packed |= ((fa.cacheable >> 3) & 1u) << kBitW;
+    stream_tile<kFusedU, kFusedU, CX, CY, CZ, CW>(
+        fa, fa.p, packed,
+        [&](auto np, const auto& rx, const auto& ry, const auto& rz, const auto& rw, auto& o) {
+            fused_any_cells<CX, CY, CZ, CW, decltype(np)::value>(fa, rx, ry, rz, rw, has_w, o);
+        },
+        [&](size_t i) { return fused_cell(fa, operand_cell(fa, 0, i), operand_cell(fa, 1, i), operand_cell(fa, 2, i), has_w ? operand_cell(fa, 3, i) : 0.0); },
+        out, out_mask, n);
 }
 
 using FusedAnyKernel = void (*)(FusedArgs, double*, uint8_t*, size_t);

@@ -104,10 +104,22 @@ inline unsigned peel_cost(const void* p, size_t size, unsigned h) {
     const bool counts = size == 1 || (size == 2 && tuning().peel >= 2);
     return counts ? static_cast<unsigned>(size) * static_cast<unsigned>(((reinterpret_cast<uintptr_t>(p) / size) + h) & 1) : 0u;
 }
-inline unsigned peel_head(const void* l, size_t lsize, const void* r, size_t rsize, size_t n) {
+// One operand stream of a launch as the host set-up sees it: its first cell and cell width (size 0: the slot loads nothing), and
+// `same_as`, an earlier stream of the launch that reads the same buffer (-1: none).
+struct LoadedStream {
+    const void* p = nullptr;
+    size_t size = 0;
+    int same_as = -1;
+};
+// peel one leading cell when that puts more of the loaded streams' bytes on even addresses (every stream counts, a buffer loaded
+// under two names twice)
+inline unsigned peel_head(const LoadedStream* st, int count, size_t n) {
     if (n < 2 || !tuning().peel) return 0;
-    const unsigned c0 = peel_cost(l, lsize, 0) + (r ? peel_cost(r, rsize, 0) : 0);
-    const unsigned c1 = peel_cost(l, lsize, 1) + (r ? peel_cost(r, rsize, 1) : 0);
+    unsigned c0 = 0, c1 = 0;
+    for (int k = 0; k < count; ++k) {
+        c0 += peel_cost(st[k].p, st[k].size, 0);
+        c1 += peel_cost(st[k].p, st[k].size, 1);
+    }
     return c1 < c0 ? 1u : 0u;
 }
 
@@ -147,6 +159,29 @@ inline unsigned cache_plan(const size_t* bytes, int n, size_t value_out_bytes = 
         for (int k = 0; k < n && n <= 8; ++k)
             if (!taken[k] && bytes[k] > 0 && bytes[k] <= largest_taken) return 0;  // an equal (or smaller) peer does not fit: admit none
     return plan;
+}
+
+// cache_plan of a one-pass launch (ec_stream_tile.hpp): the four stream slots `st` (bit k) and the `nmask` distinct masks (bit 4 + j) of
+// n cells.  A stream that reads the buffer of an earlier one counts its bytes once and takes that stream's bit: one buffer, one policy.
+inline unsigned stream_policy(const LoadedStream (&st)[4], int nmask, size_t n) {
+    size_t bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < 4; ++k) bytes[k] = st[k].same_as < 0 ? n * st[k].size : 0;
+    for (int j = 0; j < nmask; ++j) bytes[4 + j] = n;
+    unsigned policy = cache_plan(bytes, 8, n * sizeof(double));
+    for (int k = 0; k < 4; ++k)
+        if (st[k].same_as >= 0) policy = (policy & ~(1u << k)) | (((policy >> st[k].same_as) & 1u) << k);
+    return policy;
+}
+
+// Adds the mask of buffer operand `k` to a launch's distinct masks ms[0 .. *nmask) unless it is there already (one mask shared by
+// several operands is ANDed once), and ANDs its 16-byte alignment test into *aligned.  A null mask is refused.
+inline ec_status add_mask(const uint8_t* m, int k, const char* what, const uint8_t** ms, int8_t* nmask, bool* aligned) {
+    if (!m) return set_error(EC_ERR_ARG, "%s: null mask %d", what, k);
+    for (int j = 0; j < *nmask; ++j)
+        if (ms[j] == m) return EC_OK;
+    ms[(*nmask)++] = m;
+    *aligned = *aligned && aligned_to(m, 16);
+    return EC_OK;
 }
 
 // Leading cells a reduction peels so that its 16-byte loads start 16-byte aligned (0 when the window is shorter).
