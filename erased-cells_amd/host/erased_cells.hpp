@@ -383,6 +383,25 @@ public:
         else fetch(0, n_);
         return std::string(to_string(ct_)) + "CellBuffer(" + elided(items) + ")";
     }
+    // The `window_size` = (w, h) cells at `window` = (x, y) of this buffer read as rows of `cols` cells, delivered as `size` =
+    // (width, height) cells (default: as they are; another size resamples by nearest neighbour) — the device part of
+    // read_cells(window, window_size, size, e_resample_alg) (src/gdal/rasterband.rs:82-103): one ec_window launch.
+    CellBuffer window(size_t cols, std::pair<size_t, size_t> window, std::pair<size_t, size_t> window_size,
+                      std::optional<std::pair<size_t, size_t>> size = std::nullopt) const {
+        if (cols ? n_ % cols != 0 : n_ != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
+        const auto out = size.value_or(window_size);
+        CellBuffer b(ct_, out.first * out.second);
+        check(ec_window(static_cast<ec_dtype>(ct_), ptr(), nullptr, cols, cols ? n_ / cols : 0, window.first, window.second, window_size.first,
+                        window_size.second, out.first, out.second, b.ptr(), nullptr, current_stream()));
+        return b;
+    }
+    // `tile` (window_size = (w, h) contiguous cells of this buffer's type) into the window at (x, y); nothing outside it changes.
+    void put_window(size_t cols, std::pair<size_t, size_t> window, std::pair<size_t, size_t> window_size, const CellBuffer& tile) {
+        if (cols ? n_ % cols != 0 : n_ != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
+        if (tile.ct_ != ct_ || tile.n_ != window_size.first * window_size.second) throw std::logic_error("put_window: the tile does not fit the window");
+        check(ec_window_put(static_cast<ec_dtype>(ct_), tile.ptr(), nullptr, window_size.first, window_size.second, ptr(), nullptr, cols,
+                            cols ? n_ / cols : 0, window.first, window.second, current_stream()));
+    }
     CellBuffer clone() const {
         CellBuffer b(ct_, n_);
         check(ec_copy(b.ptr(), ptr(), n_ * size_of(ct_), current_stream()));
@@ -652,6 +671,24 @@ public:
         return MaskedCellBuffer(CellBuffer::from_vec(v), Mask::new_(m));
     }
 
+    // CellBuffer::window / put_window for the cells and their mask bytes in ONE launch (read_cells_masked, rasterband.rs:104-125)
+    MaskedCellBuffer window(size_t cols, std::pair<size_t, size_t> window, std::pair<size_t, size_t> window_size,
+                            std::optional<std::pair<size_t, size_t>> size = std::nullopt) const {
+        if (cols ? len() % cols != 0 : len() != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
+        const auto out = size.value_or(window_size);
+        CellBuffer b(cell_type(), out.first * out.second);
+        Mask m(out.first * out.second);
+        check(ec_window(static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), cols, cols ? len() / cols : 0, window.first, window.second,
+                        window_size.first, window_size.second, out.first, out.second, b.ptr(), m.ptr(), current_stream()));
+        return MaskedCellBuffer(std::move(b), std::move(m));
+    }
+    void put_window(size_t cols, std::pair<size_t, size_t> window, std::pair<size_t, size_t> window_size, const MaskedCellBuffer& tile) {
+        if (cols ? len() % cols != 0 : len() != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
+        if (tile.cell_type() != cell_type() || tile.len() != window_size.first * window_size.second)
+            throw std::logic_error("put_window: the tile does not fit the window");
+        check(ec_window_put(static_cast<ec_dtype>(cell_type()), tile.buf_.ptr(), tile.mask_.ptr(), window_size.first, window_size.second, buf_.ptr(),
+                            mask_.ptr(), cols, cols ? len() / cols : 0, window.first, window.second, current_stream()));
+    }
     const CellBuffer& buffer() const { return buf_; }
     CellBuffer& buffer_mut() { return buf_; }
     const Mask& mask() const { return mask_; }

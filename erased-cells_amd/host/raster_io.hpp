@@ -55,6 +55,13 @@ inline NoData<T> nodata_from_f64(const std::optional<double>& nd, const char* ty
     return NoData<T>::new_(*v);
 }
 
+// gdal::raster::ResampleAlg: what read_cells' e_resample_alg names.  Only the default, nearest neighbour, is implemented.
+enum class ResampleAlg { NearestNeighbour, Bilinear, Cubic, CubicSpline, Lanczos, Average, Mode, Gauss };
+inline const char* to_string(ResampleAlg a) {
+    static const char* names[] = {"NearestNeighbour", "Bilinear", "Cubic", "CubicSpline", "Lanczos", "Average", "Mode", "Gauss"};
+    return names[static_cast<int>(a)];
+}
+
 class RasterBand {
     size_t width_ = 0, height_ = 0;
     CellType ct_ = CellType::UInt8;
@@ -63,6 +70,17 @@ class RasterBand {
 
     static uint16_t rd16(const std::vector<uint8_t>& d, size_t o) { uint16_t v; std::memcpy(&v, d.data() + o, 2); return v; }
     static uint32_t rd32(const std::vector<uint8_t>& d, size_t o) { uint32_t v; std::memcpy(&v, d.data() + o, 4); return v; }
+
+    std::pair<size_t, size_t> checked_window(std::pair<long long, long long> window, std::pair<size_t, size_t> window_size,
+                                             const std::optional<ResampleAlg>& alg) const {
+        if (alg && *alg != ResampleAlg::NearestNeighbour)
+            throw Error(EC_ERR_ARG, std::string("read_cells: resampling algorithm ") + to_string(*alg) + " is not supported (only NearestNeighbour)");
+        if (window.first < 0 || window.second < 0) throw Error(EC_ERR_ARG, "read_cells: negative window offset");
+        const size_t x = static_cast<size_t>(window.first), y = static_cast<size_t>(window.second);
+        if (x > width_ || window_size.first > width_ - x || y > height_ || window_size.second > height_ - y)
+            throw Error(EC_ERR_ARG, "read_cells: the window leaves the raster");
+        return {x, y};
+    }
 
 public:
     // Dataset::open(path)?.rasterband(1)
@@ -135,6 +153,20 @@ public:
         throw UnsupportedCellTypeError(to_string(ct_));
     }
     CellBuffer read_cells() const { return read_cells_rows(0, height_); }
+
+    // read_cells(window, window_size, size, e_resample_alg) (src/gdal/rasterband.rs:82-103): only the window's rows are uploaded; the
+    // rectangle is cut — or resampled to `size` by nearest neighbour — on the device by one ec_window.  `window` is signed as in the
+    // reference (isize); a negative offset is refused, as GDAL refuses a window outside the raster.
+    CellBuffer read_cells(std::pair<long long, long long> window, std::pair<size_t, size_t> window_size, std::pair<size_t, size_t> size,
+                          std::optional<ResampleAlg> e_resample_alg = std::nullopt) const {
+        const auto at = checked_window(window, window_size, e_resample_alg);
+        return read_cells_rows(at.second, window_size.second).window(width_, {at.first, 0}, window_size, size);
+    }
+    MaskedCellBuffer read_cells_masked(std::pair<long long, long long> window, std::pair<size_t, size_t> window_size,
+                                       std::pair<size_t, size_t> size, std::optional<ResampleAlg> e_resample_alg = std::nullopt) const {
+        const auto at = checked_window(window, window_size, e_resample_alg);
+        return read_cells_masked_rows(at.second, window_size.second).window(width_, {at.first, 0}, window_size, size);
+    }
 
     // read_cells_masked (src/gdal/rasterband.rs:104-125): mask from the band's nodata value.
     MaskedCellBuffer read_cells_masked_rows(size_t row0, size_t nrows) const {

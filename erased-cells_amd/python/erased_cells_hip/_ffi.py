@@ -140,6 +140,8 @@ SIGNATURES = {
     "ec_mask_not": (I32, [U8P, SZ, U8P, VP]),
     "ec_mask_counts": (I32, [U8P, SZ, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), VP]),
     "ec_mask_counts_device": (I32, [U8P, SZ, VP, VP]),
+    "ec_window": (I32, [C.c_uint8, VP, U8P] + [C.c_uint64] * 8 + [VP, U8P, VP]),
+    "ec_window_put": (I32, [C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, VP, U8P] + [C.c_uint64] * 4 + [VP]),
     "ec_synth_fill": (I32, [C.c_uint8, VP, SZ, C.c_uint64, C.c_uint64, C.c_double, C.c_double, VP]),
     "ec_synth_mask": (I32, [U8P, SZ, C.c_uint64, C.c_uint64, C.c_uint32, VP]),
     "ec_tune_set": (I32, [C.c_char_p, C.c_int64]),

@@ -19,7 +19,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import EcValue, check, lib
+from ._ffi import EC_ERR_ARG, EcError, EcValue, check, lib
 
 # CellType (src/ctype.rs:11-20; order of with_ct!, src/lib.rs:89-98)
 UInt8, UInt16, UInt32, UInt64, Int8, Int16, Int32, Int64, Float32, Float64 = range(10)
@@ -341,6 +341,17 @@ def _download(mem: DeviceMem, dtype, n: int) -> np.ndarray:
     return out
 
 
+def _window_args(n: int, cols: int, window, window_size, size):
+    """(rows, x, y, w, h, out_w, out_h) of a window call on a buffer of n cells read as rows of `cols` cells."""
+    if cols < 0 or (cols == 0 and n != 0) or (cols and n % cols):
+        raise AssertionError(f"a buffer of {n} cells is not a raster of rows of {cols} cells")
+    (x, y), (w, h) = window, window_size
+    out_w, out_h = (w, h) if size is None else size
+    if min(x, y, w, h, out_w, out_h) < 0:
+        raise EcError(EC_ERR_ARG, f"negative window: offset {(x, y)}, size {(w, h)}, output {(out_w, out_h)}")
+    return (n // cols if cols else 0), x, y, w, h, out_w, out_h
+
+
 def _scalar(x) -> CellValue:
     return CellValue.new(x)
 
@@ -414,6 +425,26 @@ class CellBuffer:
         """Contiguous window (row-block shard) of this buffer; no copy."""
         sz = NP_DTYPES[self.ct].itemsize
         return CellBuffer(self.ct, cell_len, self.mem.window(cell_offset * sz, cell_len * sz))
+
+    def window(self, cols: int, window=(0, 0), window_size=(0, 0), size=None) -> "CellBuffer":
+        """The `window_size` = (w, h) cells at `window` = (x, y) of this buffer read as a raster of rows of `cols` cells, delivered as
+        `size` = (out_w, out_h) cells (default: as they are; another size resamples by nearest neighbour) — the device part of
+        read_cells(window, window_size, size, e_resample_alg) (src/gdal/rasterband.rs:82-103).  One launch, no download."""
+        rows, x, y, w, h, ow, oh = _window_args(self.n, cols, window, window_size, size)
+        out = CellBuffer.empty(ow * oh, self.ct)
+        check(lib().ec_window(self.ct, self.mem.ptr, None, cols, rows, x, y, w, h, ow, oh, out.mem.ptr, None, _stream))
+        return out
+
+    def put_window(self, cols: int, window, tile: "CellBuffer", window_size) -> None:
+        """Writes `tile` (`window_size` = (w, h) contiguous cells of this buffer's type) into the window at `window` = (x, y) of this
+        buffer read as rows of `cols` cells.  Nothing outside the window changes."""
+        if tile.ct != self.ct:
+            raise EcError(EC_ERR_ARG, f"put_window: a {CT_NAMES[tile.ct]} tile into a {CT_NAMES[self.ct]} buffer")
+        w, h = window_size
+        rows, x, y, w, h, _, _ = _window_args(self.n, cols, window, (w, h), None)
+        if w * h != tile.n:
+            raise AssertionError(f"a tile of {tile.n} cells is not {w} x {h}")
+        check(lib().ec_window_put(self.ct, tile.mem.ptr, None, w, h, self.mem.ptr, None, cols, rows, x, y, _stream))
 
     def get(self, index: int) -> CellValue:
         if not 0 <= index < self.n:
@@ -765,6 +796,25 @@ class MaskedCellBuffer:
 
     def shard(self, cell_offset: int, cell_len: int) -> "MaskedCellBuffer":
         return MaskedCellBuffer(self._buf.shard(cell_offset, cell_len), self._mask.shard(cell_offset, cell_len))
+
+    def window(self, cols: int, window=(0, 0), window_size=(0, 0), size=None) -> "MaskedCellBuffer":
+        """CellBuffer.window for values and mask in ONE launch (read_cells_masked, src/gdal/rasterband.rs:104-125)."""
+        rows, x, y, w, h, ow, oh = _window_args(self.len(), cols, window, window_size, size)
+        out, om = CellBuffer.empty(ow * oh, self.cell_type()), Mask.empty(ow * oh)
+        check(lib().ec_window(self.cell_type(), self._buf.mem.ptr, self._mask.mem.ptr, cols, rows, x, y, w, h, ow, oh,
+                              out.mem.ptr, om.mem.ptr, _stream))
+        return MaskedCellBuffer(out, om)
+
+    def put_window(self, cols: int, window, tile: "MaskedCellBuffer", window_size) -> None:
+        """CellBuffer.put_window for values and mask in one launch."""
+        if tile.cell_type() != self.cell_type():
+            raise EcError(EC_ERR_ARG, f"put_window: a {CT_NAMES[tile.cell_type()]} tile into a {CT_NAMES[self.cell_type()]} buffer")
+        w, h = window_size
+        rows, x, y, w, h, _, _ = _window_args(self.len(), cols, window, (w, h), None)
+        if w * h != tile.len():
+            raise AssertionError(f"a tile of {tile.len()} cells is not {w} x {h}")
+        check(lib().ec_window_put(self.cell_type(), tile._buf.mem.ptr, tile._mask.mem.ptr, w, h, self._buf.mem.ptr, self._mask.mem.ptr,
+                                  cols, rows, x, y, _stream))
 
     def get(self, index: int) -> CellValue:
         return self._buf.get(index)

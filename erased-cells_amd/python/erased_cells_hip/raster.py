@@ -51,6 +51,21 @@ def nodata_from_f64(ct: int, nd: Optional[float]) -> B.NoData:
     return B.NoData.new(B.CellValue(ct, dt.type(int(nd))))  # truncation toward zero
 
 
+# GDAL's default ResampleAlg, under the names callers use for it
+NEAREST_NEIGHBOUR = ("NearestNeighbour", "nearest", "ResampleAlg.NearestNeighbour", "ResampleAlg::NearestNeighbour")
+
+
+def nearest_source_index(j: int, win: int, out: int) -> int:
+    """Window index that output index j of `out` reads when `win` cells are delivered as `out`: floor((2 j + 1) * win / (2 * out)),
+    the cell-centre rule (j + 0.5) * win / out in integers (include/erased_cells.h, ec_window)."""
+    return ((2 * j + 1) * win) // (2 * out)
+
+
+def nearest_source_indices(win: int, out: int, start: int = 0, stop: Optional[int] = None) -> list:
+    """nearest_source_index for j in [start, stop) (default: every output index)."""
+    return [nearest_source_index(j, win, out) for j in range(start, out if stop is None else stop)]
+
+
 class RasterBand:
     """`Dataset::open(path)?.rasterband(1)` for the supported TIFF subset; cells stay on the host until read."""
 
@@ -110,14 +125,38 @@ class RasterBand:
     def read_cells_rows(self, row0: int, nrows: int) -> B.CellBuffer:
         return B.CellBuffer.from_vec(self.cells[row0:row0 + nrows].ravel())
 
-    def read_cells(self) -> B.CellBuffer:
-        """RasterBandEx::read_cells (src/gdal/rasterband.rs:82-103), whole band."""
-        return self.read_cells_rows(0, self.cells.shape[0])
+    def _window(self, window, window_size, size, e_resample_alg):
+        """The four arguments of read_cells* checked: (x, y, w, h, out_w, out_h)."""
+        if window_size is None:
+            raise EcError(EC_ERR_ARG, "read_cells: a window needs a window_size")
+        if e_resample_alg is not None and str(e_resample_alg) not in NEAREST_NEIGHBOUR:
+            raise EcError(EC_ERR_ARG, f"read_cells: resampling algorithm {e_resample_alg!r} is not supported (only NearestNeighbour)")
+        (x, y), (w, h) = window, window_size
+        out_w, out_h = (w, h) if size is None else size
+        if x < 0 or y < 0:  # the reference takes isize offsets; GDAL refuses a window outside the raster
+            raise EcError(EC_ERR_ARG, f"read_cells: negative window offset {(x, y)}")
+        cols, rows = self.size()
+        if min(w, h, out_w, out_h) < 0 or x + w > cols or y + h > rows:
+            raise EcError(EC_ERR_ARG, f"read_cells: the window {(x, y)} + {(w, h)} leaves the raster of {cols} x {rows} cells")
+        return x, y, w, h, out_w, out_h
+
+    def read_cells(self, window=None, window_size=None, size=None, e_resample_alg=None) -> B.CellBuffer:
+        """RasterBandEx::read_cells(window, window_size, size, e_resample_alg) (src/gdal/rasterband.rs:82-103): `window` = (x, y),
+        `window_size` = (w, h), `size` = the delivered (width, height).  No arguments: the whole band.  With a window only its rows
+        are uploaded; the rectangle is cut (or resampled, nearest neighbour) on the device by one ec_window."""
+        if window is None:
+            return self.read_cells_rows(0, self.cells.shape[0])
+        x, y, w, h, out_w, out_h = self._window(window, window_size, size, e_resample_alg)
+        return self.read_cells_rows(y, h).window(self.size()[0], (x, 0), (w, h), (out_w, out_h))
 
     def read_cells_masked_rows(self, row0: int, nrows: int) -> B.MaskedCellBuffer:
         nd = nodata_from_f64(self.band_type(), self.no_data)
         return B.MaskedCellBuffer.from_vec_with_nodata(self.cells[row0:row0 + nrows].ravel(), nd)
 
-    def read_cells_masked(self) -> B.MaskedCellBuffer:
-        """RasterBandEx::read_cells_masked (src/gdal/rasterband.rs:104-125)."""
-        return self.read_cells_masked_rows(0, self.cells.shape[0])
+    def read_cells_masked(self, window=None, window_size=None, size=None, e_resample_alg=None) -> B.MaskedCellBuffer:
+        """RasterBandEx::read_cells_masked (src/gdal/rasterband.rs:104-125), the arguments of read_cells; values and mask of the
+        window move in one launch."""
+        if window is None:
+            return self.read_cells_masked_rows(0, self.cells.shape[0])
+        x, y, w, h, out_w, out_h = self._window(window, window_size, size, e_resample_alg)
+        return self.read_cells_masked_rows(y, h).window(self.size()[0], (x, 0), (w, h), (out_w, out_h))

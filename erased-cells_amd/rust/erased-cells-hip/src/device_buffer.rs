@@ -103,6 +103,37 @@ impl CellBuffer {
         result
     }
 
+    /// The `window_size` = (w, h) cells at `window` = (x, y) of this buffer read as a raster of rows of `cols` cells, delivered as
+    /// `size` = (width, height) cells: the window itself when `size == window_size`, otherwise resampled by nearest neighbour.
+    /// One `ec_window` launch; a window that leaves the raster is an error, not a panic.
+    pub fn window(&self, cols: usize, window: (usize, usize), window_size: (usize, usize), size: (usize, usize)) -> Result<Self> {
+        assert!(if cols == 0 { self.len == 0 } else { self.len % cols == 0 }, "{} cells are not rows of {cols} cells", self.len);
+        let rows = if cols == 0 { 0 } else { self.len / cols };
+        let cut = Self::uninit(self.ct, size.0 * size.1);
+        check(unsafe {
+            ec_window(
+                self.ct as u8, self.dev_ptr(), std::ptr::null(), cols as u64, rows as u64, window.0 as u64, window.1 as u64,
+                window_size.0 as u64, window_size.1 as u64, size.0 as u64, size.1 as u64, cut.mem.ptr(), std::ptr::null_mut(), stream(),
+            )
+        })?;
+        Ok(cut)
+    }
+
+    /// Writes `tile` (`window_size` = (w, h) contiguous cells of this buffer's cell type) into the window at `window` = (x, y)
+    /// of this buffer read as rows of `cols` cells; no cell outside the window changes.  One `ec_window_put` launch.
+    pub fn put_window(&mut self, cols: usize, window: (usize, usize), window_size: (usize, usize), tile: &Self) -> Result<()> {
+        assert!(if cols == 0 { self.len == 0 } else { self.len % cols == 0 }, "{} cells are not rows of {cols} cells", self.len);
+        assert_eq!(self.ct, tile.ct, "a {} tile does not go into a {} buffer", tile.ct, self.ct);
+        assert_eq!(tile.len, window_size.0 * window_size.1, "the tile is not {} x {} cells", window_size.0, window_size.1);
+        let rows = if cols == 0 { 0 } else { self.len / cols };
+        check(unsafe {
+            ec_window_put(
+                self.ct as u8, tile.dev_ptr(), std::ptr::null(), window_size.0 as u64, window_size.1 as u64, self.mem.ptr(),
+                std::ptr::null_mut(), cols as u64, rows as u64, window.0 as u64, window.1 as u64, stream(),
+            )
+        })
+    }
+
     /// `-self`, in the cell type the reference's scalar negation produces (`ec_neg_result_type`).
     fn negated(&self) -> Self {
         if self.len == 0 {

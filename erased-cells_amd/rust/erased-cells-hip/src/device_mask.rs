@@ -40,7 +40,7 @@ impl Mask {
         self.mem.ptr() as *const u8
     }
     /// Device pointer a kernel is about to write through (owned, in-place forms): the shadow no longer describes it.
-    fn dev_ptr_overwritten(&mut self) -> *mut u8 {
+    pub(crate) fn dev_ptr_overwritten(&mut self) -> *mut u8 {
         let p = self.dev_ptr() as *mut u8;
         self.shadow.clear();
         p

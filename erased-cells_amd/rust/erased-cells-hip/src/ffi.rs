@@ -211,6 +211,14 @@ extern "C" {
                           cell_len: *mut u64) -> ec_status;
 
     // test support: deterministic device-side inputs and tuning knobs
+    // 2-D windows of a resident raster (read_cells(window, window_size, size, e_resample_alg), src/gdal/rasterband.rs:82-125)
+    pub fn ec_window(t: ec_dtype, src: *const c_void, src_mask_or_null: *const u8, src_cols: u64, src_rows: u64, x0: u64, y0: u64,
+                     win_cols: u64, win_rows: u64, out_cols: u64, out_rows: u64, dst: *mut c_void, dst_mask_or_null: *mut u8,
+                     s: ec_stream) -> ec_status;
+    pub fn ec_window_put(t: ec_dtype, tile: *const c_void, tile_mask_or_null: *const u8, win_cols: u64, win_rows: u64,
+                         dst: *mut c_void, dst_mask_or_null: *mut u8, dst_cols: u64, dst_rows: u64, x0: u64, y0: u64,
+                         s: ec_stream) -> ec_status;
+
     pub fn ec_synth_fill(t: ec_dtype, dst: *mut c_void, n: usize, seed: u64, base: u64, lo: f64, hi: f64,
                          s: ec_stream) -> ec_status;
     pub fn ec_synth_mask(dst: *mut u8, n: usize, seed: u64, base: u64, pct_nodata: u32, s: ec_stream) -> ec_status;

@@ -51,6 +51,38 @@ impl MaskedCellBuffer {
         MaskedCellBuffer(cells, mask)
     }
 
+    /// [`CellBuffer::window`] for the cells and their mask bytes in ONE launch (`read_cells_masked` of a window).
+    pub fn window(&self, cols: usize, window: (usize, usize), window_size: (usize, usize), size: (usize, usize)) -> Result<Self> {
+        let len = self.0.len();
+        assert!(if cols == 0 { len == 0 } else { len % cols == 0 }, "{len} cells are not rows of {cols} cells");
+        let rows = if cols == 0 { 0 } else { len / cols };
+        let cells = CellBuffer::uninit(self.0.ct, size.0 * size.1);
+        let mask = Mask::uninit(size.0 * size.1);
+        check(unsafe {
+            ec_window(
+                self.0.ct as u8, self.0.dev_ptr(), self.1.dev_ptr(), cols as u64, rows as u64, window.0 as u64, window.1 as u64,
+                window_size.0 as u64, window_size.1 as u64, size.0 as u64, size.1 as u64, cells.mem.ptr(), mask.dev_ptr_mut(), stream(),
+            )
+        })?;
+        Ok(MaskedCellBuffer(cells, mask))
+    }
+
+    /// [`CellBuffer::put_window`] for the cells and their mask bytes in one launch.
+    pub fn put_window(&mut self, cols: usize, window: (usize, usize), window_size: (usize, usize), tile: &Self) -> Result<()> {
+        let len = self.0.len();
+        assert!(if cols == 0 { len == 0 } else { len % cols == 0 }, "{len} cells are not rows of {cols} cells");
+        assert_eq!(self.0.ct, tile.0.ct, "a {} tile does not go into a {} buffer", tile.0.ct, self.0.ct);
+        assert_eq!(tile.0.len(), window_size.0 * window_size.1, "the tile is not {} x {} cells", window_size.0, window_size.1);
+        let rows = if cols == 0 { 0 } else { len / cols };
+        let mask_out = self.1.dev_ptr_overwritten();
+        check(unsafe {
+            ec_window_put(
+                self.0.ct as u8, tile.0.dev_ptr(), tile.1.dev_ptr(), window_size.0 as u64, window_size.1 as u64, self.0.mem.ptr(),
+                mask_out, cols as u64, rows as u64, window.0 as u64, window.1 as u64, stream(),
+            )
+        })
+    }
+
     /// `mv(i)` gives cell `i` and its validity; both vectors are built on the host and uploaded once each.
     pub fn fill_with_mask_via<T, F>(len: usize, mv: F) -> Self
     where

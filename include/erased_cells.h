@@ -456,6 +456,30 @@ ec_status ec_mask_counts(const uint8_t *m, size_t n, uint64_t *n_true, uint64_t 
 ec_status ec_mask_counts_device(const uint8_t *m, size_t n, uint64_t *counts2_dev, ec_stream stream);
 
 /* ---------------------------------------------------------------- *
+ * 2-D windows of a raster resident on the device.
+ * ---------------------------------------------------------------- */
+/* RasterBandEx::read_cells / read_cells_masked(window, window_size, size, e_resample_alg) — src/gdal/rasterband.rs:82-125,
+ * the part behind the decoder: `src` is a row-major raster of src_cols x src_rows cells of type t on the device; the window
+ * of win_cols x win_rows cells at column x0, row y0 is written to `dst` as out_cols x out_rows contiguous cells.
+ * out == win copies the cells; any other size resamples by nearest neighbour (GDAL's default, the only algorithm), defined in
+ * integers: output column j reads window column floor((2 j + 1) * win_cols / (2 * out_cols)) — the cell-centre rule
+ * (j + 0.5) * win_cols / out_cols evaluated exactly — and rows likewise.  With both masks non-NULL the mask bytes of the same
+ * cells move in the same launch (read_cells_masked, rasterband.rs:104-125).  No allocation, asynchronous, capturable.
+ * EC_ERR_ARG, before any device work: a window that leaves the raster, src_cols * src_rows or out_cols * out_rows beyond
+ * 64 bits, exactly one mask NULL, an empty window with a non-empty output or the reverse, a resampling whose ratio
+ * arithmetic leaves 64 bits (an axis of more than 2^31 cells that is neither copied nor reduced by a whole factor).
+ * An empty window with an empty output is EC_OK and launches nothing. */
+ec_status ec_window(ec_dtype t, const void *src, const uint8_t *src_mask_or_null,
+                    uint64_t src_cols, uint64_t src_rows, uint64_t x0, uint64_t y0, uint64_t win_cols, uint64_t win_rows,
+                    uint64_t out_cols, uint64_t out_rows, void *dst, uint8_t *dst_mask_or_null, ec_stream stream);
+/* The inverse of the copying ec_window (src/gdal/rasterband.rs:82-125 read in the other direction): the contiguous tile of
+ * win_cols x win_rows cells is written into the window at (x0, y0) of the raster `dst` of dst_cols x dst_rows cells; no
+ * byte outside the window is written.  Same checks, same mask rule. */
+ec_status ec_window_put(ec_dtype t, const void *tile, const uint8_t *tile_mask_or_null, uint64_t win_cols, uint64_t win_rows,
+                        void *dst, uint8_t *dst_mask_or_null, uint64_t dst_cols, uint64_t dst_rows,
+                        uint64_t x0, uint64_t y0, ec_stream stream);
+
+/* ---------------------------------------------------------------- *
  * Test/bench support (not part of the reference surface).
  * ---------------------------------------------------------------- */
 /* x[i] = lo + splitmix64(seed ^ (base + i)) % (hi - lo + 1), t in {EC_U8, EC_U16, EC_F32}
