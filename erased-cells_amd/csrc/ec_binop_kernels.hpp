@@ -16,17 +16,17 @@
 //           is private to the wave, so no workgroup barrier is needed.
 // One workgroup per tile of U = 2 chunks per wave (1,024 cells), straight-line code,
 // grid = number of tiles (≫ 256 CUs: 262,144 workgroups at 16384²), dealt from both
-// ends of the buffer at once (two_front_tile).  Loads and stores are non-temporal:
-// every byte is touched once and the streams (2.95 GB) dwarf the 256 MiB Infinity
-// Cache.  There is no reuse between workgroups (each 128-B line is touched by exactly
-// one wave), so an XCD-aware remap has no L2 locality to win (measured: −4 %).
+// ends of the buffer at once (two_front_tile).  Stores always stream (nt_store,
+// ec_device.hpp): the f64 output (2.1 GB) dwarfs the 256 MiB Infinity Cache.  Loads are
+// non-temporal (+6 % on the divide, tune_binop_v2.log: 6270 -> 6666 GB/s) except a full
+// tile's loads of an operand stream that the host marks cacheable for the launch (policy
+// bits of `head`: cache_plan(), ec_runtime.hpp); the guarded last tile, the single head /
+// tail cells and the LDS variant always load non-temporal.  There is no reuse between
+// workgroups (each 128-B line is touched by exactly one wave), so an XCD-aware remap has
+// no L2 locality to win (measured: −4 %).
 #pragma once
 
 #include "ec_device.hpp"
-
-#ifndef EC_DIV_STAGE
-#define EC_DIV_STAGE 2  // build-time A/B switch of the short divide's tile code: 1 = the tile's 2 U quotients staged together, 2 = chunk by chunk (default)
-#endif
 
 namespace ecd {
 
@@ -34,12 +34,7 @@ constexpr int kBlock = 256;          // 4 waves
 constexpr int kWave = 64;
 constexpr int kWavesPerBlock = kBlock / kWave;
 
-template <bool NT, typename V>
-__device__ __forceinline__ void store_vec(V* p, V v) {
-    if constexpr (NT) nt_store(v, p);
-    else plain_store(v, p);
-}
-
+// a vector load in one arm of its launch's load policy (policy_arms, ec_device.hpp): NT = the stream is not kept cacheable
 template <bool NT, typename V>
 __device__ __forceinline__ V load_vec(const V* p) {
     if constexpr (NT) return nt_load(p);
@@ -54,25 +49,12 @@ __device__ __forceinline__ size_t two_front_tile() {
     return (b & 1) ? size_t(gridDim.x) - 1 - (b >> 1) : (b >> 1);
 }
 
-// Where a lane's pairs sit inside its workgroup's tile of kBlock * U pairs.  EC_WAVE_CONTIG = 0: chunk j of all four waves is one
-// contiguous run (lane = threadIdx.x, stride kBlock); 1: each wave owns U contiguous chunks (its 64 U pairs: 2 U KiB of f64 output,
-// its operand loads of the U chunks adjacent) — tools/tune_store.hip "wave-contig", +0.6 % on the 3 B-read / 8 B-write mix.
-#ifndef EC_WAVE_CONTIG
-#define EC_WAVE_CONTIG 0
-#endif
-constexpr size_t tile_stride() { return EC_WAVE_CONTIG ? size_t(kWave) : size_t(kBlock); }
-template <int U>
-__device__ __forceinline__ size_t tile_lane_offset() {
-    if constexpr (EC_WAVE_CONTIG) return size_t(threadIdx.x / kWave) * (size_t(kWave) * U) + (threadIdx.x & (kWave - 1));
-    else return threadIdx.x;
-}
-
 // ---------------------------------------------------------------------------
 // DIRECT variant: one block tile of kBlock*U pairs (2 cells each).  Pointers may sit
 // at any cell offset (under-aligned accesses, ec_device.hpp); the cell-wise kernels run
 // only when the "unaligned_vector" knob is off and a pointer is not 16-B aligned.
 // ---------------------------------------------------------------------------
-template <typename L, typename R, int OP, int U, bool NT_ST, bool NT_LD>
+template <typename L, typename R, int OP, int U>
 __device__ __forceinline__ void binop_direct_tile(const L* __restrict__ l, const R* __restrict__ r,
                                                   double* __restrict__ out, size_t npairs, size_t tile, unsigned cacheable) {
     using D2 = vec<double, 2>;
@@ -80,8 +62,7 @@ __device__ __forceinline__ void binop_direct_tile(const L* __restrict__ l, const
     constexpr bool SM = is_small_int<L>::value && is_small_int<R>::value;  // 6-instruction exact divide (ec_device.hpp)
     constexpr size_t TILE = size_t(kBlock) * U;
     D2* __restrict__ op = reinterpret_cast<D2*>(out);
-    constexpr size_t kStride = tile_stride();
-    const size_t base = tile * TILE + tile_lane_offset<U>();
+    const size_t base = tile * TILE + threadIdx.x;
     if (tile * TILE + TILE <= npairs) {
         cells<L, 2> a[U];  // 1-byte operands travel as 16-bit words so that their loads keep `nt` (ec_device.hpp)
         cells<R, 2> b[U];
@@ -89,8 +70,8 @@ __device__ __forceinline__ void binop_direct_tile(const L* __restrict__ l, const
             constexpr unsigned B = decltype(bits)::value;
 #pragma unroll
             for (int j = 0; j < U; ++j) {
-                a[j] = load_cells<NT_LD && !(B & 1u), L, 2>(l + 2 * (base + size_t(j) * kStride));
-                b[j] = load_cells<NT_LD && !(B & 2u), R, 2>(r + 2 * (base + size_t(j) * kStride));
+                a[j] = load_cells<!(B & 1u), L, 2>(l + 2 * (base + size_t(j) * kBlock));
+                b[j] = load_cells<!(B & 2u), R, 2>(r + 2 * (base + size_t(j) * kBlock));
             }
         });
         if constexpr (OP == EC_DIV && SM && !FP) {
@@ -98,14 +79,10 @@ __device__ __forceinline__ void binop_direct_tile(const L* __restrict__ l, const
             // (integer compares), and only a wave that holds a zero divisor runs the selects — 5 of the 11 vector instructions
             // per cell off the common path (with the u8 operand served from the Infinity Cache the divide is no longer fully
             // hidden behind memory: 0.4222 ms against the add's 0.4134 before this, profiles/r03/kernel_table.md)
-            // Each quotient is a chain of six dependent FP64 instructions; written cell by cell the compiler issues the chains one
-            // after the other, and with the u8 operand coming from HBM too the kernel is bound by how long a workgroup lives (its
-            // occupancy is the hardware's maximum), so those ≈ 300 cycles show: the divide ran 2 % behind the add at equal bytes
-            // (0.816 against 0.832, profiles/r04/store_policy_ab/).  Interleaved, rotating operand sets, three runs each: all 2 U
-            // chains staged together 0.819-0.823; chunk by chunk 0.827 (the add: 0.8335).
-#if EC_DIV_STAGE == 2
-            // chunk by chunk — the chunk's two chains staged, its zero test, its store — so that the first store leaves as soon as
-            // the first chunk's loads are back, while the second chunk's may still be in flight
+            // Each quotient is a chain of six dependent FP64 instructions; the chunk's two chains are staged together
+            // (div_small_int_nonzero_staged) and the tile goes chunk by chunk — the chunk's chains, its zero test, its store —
+            // so that the first store leaves as soon as the first chunk's loads are back, while the second chunk's may
+            // still be in flight (0.827 of the HBM peak, the add at equal bytes 0.8335: profiles/r04/store_policy_ab/)
 #pragma unroll
             for (int j = 0; j < U; ++j) {
                 double av[2], bv[2], q[2], y[2], e[2];
@@ -121,47 +98,28 @@ __device__ __forceinline__ void binop_direct_tile(const L* __restrict__ l, const
 #pragma unroll
                     for (int i = 0; i < 2; ++i) q[i] = bv[i] == 0.0 ? div_by_zero(av[i]) : q[i];
                 }
-                store_vec<NT_ST>(op + base + size_t(j) * kStride, D2{q[0], q[1]});
+                nt_store(D2{q[0], q[1]}, op + base + size_t(j) * kBlock);
             }
-#else
-            double av[2 * U], bv[2 * U], q[2 * U], y[2 * U], e[2 * U];
-            bool zero = false;
-#pragma unroll
-            for (int j = 0; j < U; ++j)
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    av[2 * j + k] = to_f64(a[j][k]);
-                    bv[2 * j + k] = to_f64(b[j][k]);
-                    zero = zero || b[j][k] == 0;
-                }
-            div_small_int_nonzero_staged<2 * U>(av, bv, q, y, e);
-            if (__builtin_expect(__builtin_amdgcn_ballot_w64(zero) != 0, 0)) {
-#pragma unroll
-                for (int i = 0; i < 2 * U; ++i) q[i] = bv[i] == 0.0 ? div_by_zero(av[i]) : q[i];
-            }
-#pragma unroll
-            for (int j = 0; j < U; ++j) store_vec<NT_ST>(op + base + size_t(j) * kStride, D2{q[2 * j], q[2 * j + 1]});
-#endif
         } else {
 #pragma unroll
             for (int j = 0; j < U; ++j) {  // chunk by chunk, the NaN rule tested once per chunk (cell_op_n, ec_device.hpp)
                 const double av[2] = {to_f64(a[j][0]), to_f64(a[j][1])}, bv[2] = {to_f64(b[j][0]), to_f64(b[j][1])};
                 double o[2];
                 cell_op_n<OP, FP, SM, 2>(av, bv, o);
-                store_vec<NT_ST>(op + base + size_t(j) * kStride, D2{o[0], o[1]});
+                nt_store(D2{o[0], o[1]}, op + base + size_t(j) * kBlock);
             }
         }
     } else {
 #pragma unroll
         for (int j = 0; j < U; ++j) {
-            const size_t p = base + size_t(j) * kStride;
+            const size_t p = base + size_t(j) * kBlock;
             if (p < npairs) {
-                const cells<L, 2> a = load_cells<NT_LD, L, 2>(l + 2 * p);
-                const cells<R, 2> b = load_cells<NT_LD, R, 2>(r + 2 * p);
+                const cells<L, 2> a = load_cells<true, L, 2>(l + 2 * p);
+                const cells<R, 2> b = load_cells<true, R, 2>(r + 2 * p);
                 D2 o;  // the ragged last tile: lanes diverge here anyway (p < npairs), the per-cell form is as good
                 o.x = cell_op<OP, FP, SM>(to_f64(a[0]), to_f64(b[0]));
                 o.y = cell_op<OP, FP, SM>(to_f64(a[1]), to_f64(b[1]));
-                store_vec<NT_ST>(op + p, o);
+                nt_store(o, op + p);
             }
         }
     }
@@ -175,7 +133,7 @@ __device__ __forceinline__ void binop_direct_tile(const L* __restrict__ l, const
 // even addresses (measurements and the rule: ec_runtime.hpp).  Bits 8.. of `head` carry the launch's load policy:
 // bit 8 = l, bit 9 = r (masked kernels: bit 10 = lmask, bit 11 = rmask) is loaded cacheable instead of nt
 // (cache_plan(), ec_runtime.hpp; policy_arms(), ec_device.hpp).
-template <typename L, typename R, int OP, int U, bool NT_ST, bool NT_LD>
+template <typename L, typename R, int OP, int U>
 __device__ __forceinline__ void binop_direct_body(const L* __restrict__ l, const R* __restrict__ r,
                                                   double* __restrict__ out, size_t n, unsigned head_and_policy) {
     constexpr bool FP = is_fp<L>::value || is_fp<R>::value;
@@ -189,7 +147,7 @@ __device__ __forceinline__ void binop_direct_body(const L* __restrict__ l, const
         out += head;
         n -= head;
     }
-    binop_direct_tile<L, R, OP, U, NT_ST, NT_LD>(l, r, out, n >> 1, two_front_tile(), cacheable);
+    binop_direct_tile<L, R, OP, U>(l, r, out, n >> 1, two_front_tile(), cacheable);
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
         st_cell(cell_op<OP, FP, SM>(to_f64(ld_cell(l + n - 1)), to_f64(ld_cell(r + n - 1))), out + n - 1);
 }
@@ -197,45 +155,44 @@ __device__ __forceinline__ void binop_direct_body(const L* __restrict__ l, const
 // NANRULE: cv_bin_op!'s NaN rule is compiled in.  The scalar may be any of the 10 types (widened to f64 on the host), so in general a result
 // can be a NaN; but integer cells with a FINITE scalar (non-zero for a divide) cannot produce one — finite op finite is finite or ±inf — and
 // the host then launches the form without the rule (u8 * 2.0, the reference's own example: 0.774 -> 0.80 with every byte from HBM).
-template <typename L, int OP, int U, bool NT_ST, bool NT_LD, bool NANRULE = true>
+template <typename L, int OP, int U, bool NANRULE = true>
 __device__ __forceinline__ void binop_scalar_tile(const L* __restrict__ l, double s, double* __restrict__ out,
                                                   size_t npairs, size_t tile, unsigned cacheable) {
     using D2 = vec<double, 2>;
     constexpr bool FP = NANRULE;
     constexpr size_t TILE = size_t(kBlock) * U;
     D2* __restrict__ op = reinterpret_cast<D2*>(out);
-    constexpr size_t kStride = tile_stride();
-    const size_t base = tile * TILE + tile_lane_offset<U>();
+    const size_t base = tile * TILE + threadIdx.x;
     if (tile * TILE + TILE <= npairs) {
         cells<L, 2> a[U];
         policy_arms<1>(cacheable, [&](auto bits) {
             constexpr unsigned B = decltype(bits)::value;
 #pragma unroll
-            for (int j = 0; j < U; ++j) a[j] = load_cells<NT_LD && !(B & 1u), L, 2>(l + 2 * (base + size_t(j) * kStride));
+            for (int j = 0; j < U; ++j) a[j] = load_cells<!(B & 1u), L, 2>(l + 2 * (base + size_t(j) * kBlock));
         });
 #pragma unroll
         for (int j = 0; j < U; ++j) {
             const double av[2] = {to_f64(a[j][0]), to_f64(a[j][1])}, bv[2] = {s, s};
             double o[2];
             cell_op_n<OP, FP, false, 2>(av, bv, o);
-            store_vec<NT_ST>(op + base + size_t(j) * kStride, D2{o[0], o[1]});
+            nt_store(D2{o[0], o[1]}, op + base + size_t(j) * kBlock);
         }
     } else {
 #pragma unroll
         for (int j = 0; j < U; ++j) {
-            const size_t p = base + size_t(j) * kStride;
+            const size_t p = base + size_t(j) * kBlock;
             if (p < npairs) {
-                const cells<L, 2> a = load_cells<NT_LD, L, 2>(l + 2 * p);
+                const cells<L, 2> a = load_cells<true, L, 2>(l + 2 * p);
                 D2 o;
                 o.x = cell_op<OP, FP>(to_f64(a[0]), s);
                 o.y = cell_op<OP, FP>(to_f64(a[1]), s);
-                store_vec<NT_ST>(op + p, o);
+                nt_store(o, op + p);
             }
         }
     }
 }
 
-template <typename L, int OP, int U, bool NT_ST, bool NT_LD, bool NANRULE = true>
+template <typename L, int OP, int U, bool NANRULE = true>
 __global__ __launch_bounds__(kBlock) void k_binop_scalar_direct(const L* __restrict__ l, double s,
                                                                 double* __restrict__ out, size_t n, unsigned head_and_policy) {
     const unsigned head = head_and_policy & 0xffu, cacheable = head_and_policy >> 8;
@@ -245,7 +202,7 @@ __global__ __launch_bounds__(kBlock) void k_binop_scalar_direct(const L* __restr
         out += head;
         n -= head;
     }
-    binop_scalar_tile<L, OP, U, NT_ST, NT_LD, NANRULE>(l, s, out, n >> 1, two_front_tile(), cacheable);
+    binop_scalar_tile<L, OP, U, NANRULE>(l, s, out, n >> 1, two_front_tile(), cacheable);
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) st_cell(cell_op<OP, true>(to_f64(ld_cell(l + n - 1)), s), out + n - 1);
 }
 
@@ -289,7 +246,7 @@ struct Staged {
 
 using u32x4 = vec<uint32_t, 4>;
 
-template <typename L, typename R, int OP, bool NT_ST, bool NT_LD>
+template <typename L, typename R, int OP>
 __device__ __forceinline__ void binop_lds_body(const L* __restrict__ l, const R* __restrict__ r,
                                                double* __restrict__ out, size_t n) {
     using L2 = vec<L, 2>;
@@ -313,16 +270,16 @@ __device__ __forceinline__ void binop_lds_body(const L* __restrict__ l, const R*
         typename Staged<L>::Load sl{};
         typename Staged<R>::Load sr{};
         if constexpr (SL) {
-            sl = load_vec<NT_LD>(reinterpret_cast<const typename Staged<L>::Load*>(l + cell0) + lane);
+            sl = nt_load(reinterpret_cast<const typename Staged<L>::Load*>(l + cell0) + lane);
         } else {
 #pragma unroll
-            for (int j = 0; j < kLdsChunks; ++j) a[j] = load_vec<NT_LD>(reinterpret_cast<const L2*>(l + cell0) + j * kWave + lane);
+            for (int j = 0; j < kLdsChunks; ++j) a[j] = nt_load(reinterpret_cast<const L2*>(l + cell0) + j * kWave + lane);
         }
         if constexpr (SR) {
-            sr = load_vec<NT_LD>(reinterpret_cast<const typename Staged<R>::Load*>(r + cell0) + lane);
+            sr = nt_load(reinterpret_cast<const typename Staged<R>::Load*>(r + cell0) + lane);
         } else {
 #pragma unroll
-            for (int j = 0; j < kLdsChunks; ++j) b[j] = load_vec<NT_LD>(reinterpret_cast<const R2*>(r + cell0) + j * kWave + lane);
+            for (int j = 0; j < kLdsChunks; ++j) b[j] = nt_load(reinterpret_cast<const R2*>(r + cell0) + j * kWave + lane);
         }
         if constexpr (SL) reinterpret_cast<typename Staged<L>::Load*>(slab_l[wave])[lane] = sl;
         if constexpr (SR) reinterpret_cast<typename Staged<R>::Load*>(slab_r[wave])[lane] = sr;
@@ -346,7 +303,7 @@ __device__ __forceinline__ void binop_lds_body(const L* __restrict__ l, const R*
             const double av[2] = {to_f64(a[j].x), to_f64(a[j].y)}, bv[2] = {to_f64(b[j].x), to_f64(b[j].y)};
             double o[2];
             cell_op_n<OP, FP, SM, 2>(av, bv, o);
-            store_vec<NT_ST>(o2 + j * kWave + lane, D2{o[0], o[1]});
+            nt_store(D2{o[0], o[1]}, o2 + j * kWave + lane);
         }
     }
     // ragged tail (< one wave tile): cell-wise by workgroup 0
@@ -355,16 +312,16 @@ __device__ __forceinline__ void binop_lds_body(const L* __restrict__ l, const R*
             st_cell(cell_op<OP, FP, SM>(to_f64(ld_cell(l + i)), to_f64(ld_cell(r + i))), out + i);
 }
 
-template <typename L, typename R, int OP, int U, bool NT_ST, bool NT_LD>
+template <typename L, typename R, int OP, int U>
 __global__ __launch_bounds__(kBlock) void k_binop_direct(const L* __restrict__ l, const R* __restrict__ r,
                                                          double* __restrict__ out, size_t n, unsigned head = 0) {
-    binop_direct_body<L, R, OP, U, NT_ST, NT_LD>(l, r, out, n, head);
+    binop_direct_body<L, R, OP, U>(l, r, out, n, head);
 }
 
-template <typename L, typename R, int OP, bool NT_ST, bool NT_LD>
+template <typename L, typename R, int OP>
 __global__ __launch_bounds__(kBlock) void k_binop_lds(const L* __restrict__ l, const R* __restrict__ r,
                                                       double* __restrict__ out, size_t n) {
-    binop_lds_body<L, R, OP, NT_ST, NT_LD>(l, r, out, n);
+    binop_lds_body<L, R, OP>(l, r, out, n);
 }
 
 // `&Mask & &Mask` (src/masked/mask.rs:129-140) as a block-tiled 16-B-per-lane stream.
@@ -392,13 +349,13 @@ __device__ __forceinline__ void mask_and_body(const uint8_t* __restrict__ lm, co
 // launch: the buffer op over ALL cells (masked-out cells are still computed,
 // :331) and the mask AND (:333), each with its own lane->cell mapping so both
 // streams stay 16 B per lane.
-template <typename L, typename R, int OP, int U, bool NT_ST, bool NT_LD, bool LDS>
+template <typename L, typename R, int OP, int U, bool LDS>
 __global__ __launch_bounds__(kBlock) void k_masked_binop(const L* __restrict__ l, const uint8_t* __restrict__ lm,
                                                          const R* __restrict__ r, const uint8_t* __restrict__ rm,
                                                          double* __restrict__ out, uint8_t* __restrict__ om, size_t n,
                                                          unsigned head) {
-    if constexpr (LDS) binop_lds_body<L, R, OP, NT_ST, NT_LD>(l, r, out, n);
-    else binop_direct_body<L, R, OP, U, NT_ST, NT_LD>(l, r, out, n, head);
+    if constexpr (LDS) binop_lds_body<L, R, OP>(l, r, out, n);
+    else binop_direct_body<L, R, OP, U>(l, r, out, n, head);
     mask_and_body(lm, rm, om, n, head >> 8);
 }
 

@@ -45,14 +45,14 @@ static ec_status launch_binop_pair(const void* l, const void* r, size_t n, doubl
         constexpr unsigned kStatic = kWavesPerBlock * unsigned(Staged<L>::kSlabBytes + Staged<R>::kSlabBytes);
         const int knob = tu.binop_lds_kb.load();
         const unsigned lds = knob >= 0 ? unsigned(knob) << 10 : by_rule ? 32000u - kStatic : 0u;
-        k_binop_lds<L, R, OP, kNtStore, kNtLoad><<<grid_for(tiles), kBlock, lds, s>>>(lp, rp, out, n);
+        k_binop_lds<L, R, OP><<<grid_for(tiles), kBlock, lds, s>>>(lp, rp, out, n);
         if (by_rule) lds_rule_launches().fetch_add(1, std::memory_order_relaxed);
         return check_launch(by_rule ? "binop(lds, by rule)" : "binop(lds)");
     }
     const LoadedStream st[2] = {{l, sizeof(L)}, {r, sizeof(R)}};
     const unsigned head = peel_head(st, 2, n);
     const size_t tiles = (((n - head) >> 1) + size_t(kBlock) * U - 1) / (size_t(kBlock) * U);
-    k_binop_direct<L, R, OP, U, kNtStore, kNtLoad><<<grid_for(tiles), kBlock, lds_cap(tuning().binop_lds_kb.load(), sizeof(L) == 8 && sizeof(R) == 8 ? 48 : 0), s>>>(lp, rp, out, n, head | (policy << 8));
+    k_binop_direct<L, R, OP, U><<<grid_for(tiles), kBlock, lds_cap(tuning().binop_lds_kb.load(), sizeof(L) == 8 && sizeof(R) == 8 ? 48 : 0), s>>>(lp, rp, out, n, head | (policy << 8));
     return check_launch("binop(direct)");
 }
 
@@ -70,7 +70,7 @@ static ec_status launch_masked_pair(const void* l, const uint8_t* lm, const void
     constexpr bool kCanStage = Staged<L>::value || Staged<R>::value;
     if (kCanStage && tu.binop_variant == 1) {
         const size_t tiles = (n / kLdsWaveCells + kWavesPerBlock - 1) / kWavesPerBlock;
-        k_masked_binop<L, R, OP, U, kNtStore, kNtLoad, true><<<grid_for(tiles), kBlock, lds_cap(tu.binop_lds_kb.load(), 0), s>>>(lp, lm, rp, rm, out, om, n, 0u);
+        k_masked_binop<L, R, OP, U, true><<<grid_for(tiles), kBlock, lds_cap(tu.binop_lds_kb.load(), 0), s>>>(lp, lm, rp, rm, out, om, n, 0u);
         return check_launch("masked_binop(lds)");
     }
     const LoadedStream st[2] = {{l, sizeof(L)}, {r, sizeof(R)}};
@@ -80,7 +80,7 @@ static ec_status launch_masked_pair(const void* l, const uint8_t* lm, const void
     unsigned policy = cache_plan(stream_bytes, 4, n * sizeof(double));
     if (l == r && (policy & 1u)) policy |= 2u;
     if (lm == rm && (policy & 4u)) policy |= 8u;
-    k_masked_binop<L, R, OP, U, kNtStore, kNtLoad, false><<<grid_for(tiles), kBlock, 0, s>>>(lp, lm, rp, rm, out, om, n, head | (policy << 8));
+    k_masked_binop<L, R, OP, U, false><<<grid_for(tiles), kBlock, 0, s>>>(lp, lm, rp, rm, out, om, n, head | (policy << 8));
     return check_launch("masked_binop(direct)");
 }
 
@@ -102,11 +102,11 @@ static ec_status launch_scalar(const void* l, double rhs, size_t n, double* out,
     if constexpr (!is_fp<L>::value) {
         // integer cells and a finite scalar (non-zero for a divide): no result can be a NaN — the form without the NaN rule
         if (std::isfinite(rhs) && !(OP == EC_DIV && rhs == 0.0)) {
-            k_binop_scalar_direct<L, OP, U, kNtStore, kNtLoad, false><<<grid_for(tiles), kBlock, lds, s>>>(lp, rhs, out, n, head | (policy << 8));
+            k_binop_scalar_direct<L, OP, U, false><<<grid_for(tiles), kBlock, lds, s>>>(lp, rhs, out, n, head | (policy << 8));
             return check_launch("binop_scalar(direct, no NaN possible)");
         }
     }
-    k_binop_scalar_direct<L, OP, U, kNtStore, kNtLoad><<<grid_for(tiles), kBlock, lds, s>>>(lp, rhs, out, n, head | (policy << 8));
+    k_binop_scalar_direct<L, OP, U><<<grid_for(tiles), kBlock, lds, s>>>(lp, rhs, out, n, head | (policy << 8));
     return check_launch("binop_scalar(direct)");
 }
 

@@ -200,24 +200,18 @@ template <typename V>
 __device__ __forceinline__ V nt_load(const V* p) {
     return __builtin_nontemporal_load(reinterpret_cast<const typename under_aligned<V>::type*>(p));
 }
-// Streaming stores.  EC_STORE_POLICY (build-time A/B switch, like EC_NT_STORE in ec_runtime.hpp):
-//   1  `nt`      — what rounds 1-3 shipped
-//   2  `sc1 nt`  — write-through at device scope: the L2 passes each 64-byte write on as it completes instead of keeping the line
-//                  dirty and writing it back when it is evicted.  With every operand byte coming from HBM (rotating operand sets)
-//                  the 3 B-read / 8 B-write mix runs at 0.82 of the HBM peak with these against 0.78 with `nt` alone, the same
-//                  tile shape and loads (tools/tune_store.hip, profiles/r04/tune_store_v1.log, _v2.log).
+// Streaming stores.  VALUE streams (the f64 results, converted cells: nt_store / st_cell) are stored `sc1 nt`, MASK streams
+// (mask_store) `nt`.  `sc1` is write-through at device scope: the L2 passes each 64-byte write on as it completes instead of keeping the
+// line dirty and writing it back when it is evicted.  With every operand byte coming from HBM (rotating operand sets) the 3 B-read /
+// 8 B-write mix runs at 0.82 of the HBM peak with it against 0.78 with `nt` alone, the same tile shape and loads (tools/tune_store.hip,
+// profiles/r04/tune_store_v1.log, _v2.log).  Write-through pays where the output is most of the launch's bytes and leaves the L2 in
+// 16-byte-per-lane stores; the 1 B/cell mask outputs (mask_and, mask_not, mask_from_nodata: a third to a half of their launch's bytes)
+// ran 1-2 % slower with it (profiles/r04/store_policy_ab.md) and keep `nt` alone.
 // hipcc has no source form for `sc1` on a plain store (volatile gives `sc0 sc1` on a flat store and waits for it; an atomic store
-// stops at 64 bits), so policy 2 is inline asm: one `global_store_*` by width, the address as a 64-bit VGPR pair.  `s_nop 1` behind
+// stops at 64 bits), so the value store is inline asm: one `global_store_*` by width, the address as a 64-bit VGPR pair.  `s_nop 1` behind
 // the 16-byte form: on gfx940+ a VALU write of the data registers of a store of more than 64 bits needs two wait states, and
 // the compiler's hazard recognizer does not look into asm (without it the sweep's pure-write variants stored garbage).  No memory
 // clobber: no kernel of the library reads what it stores, so the scheduler stays free to keep later loads above the store.
-//   3  `sc1 nt` for VALUE streams (the f64 results, converted cells: nt_store / st_cell), `nt` for MASK streams (mask_store): the
-//      default.  Write-through pays where the output is most of the launch's bytes and leaves the L2 in 16-byte-per-lane stores;
-//      the 1 B/cell mask outputs (mask_and, mask_not, mask_from_nodata: a third to a half of their launch's bytes) ran 1-2 % slower
-//      with it (profiles/r04/store_policy_ab.md).
-#ifndef EC_STORE_POLICY
-#define EC_STORE_POLICY 3
-#endif
 template <typename V>
 __device__ __forceinline__ void stream_store_asm(V v, V* p) {
     static_assert(sizeof(V) == 1 || sizeof(V) == 2 || sizeof(V) == 4 || sizeof(V) == 8 || sizeof(V) == 16, "store width");
@@ -234,29 +228,15 @@ __device__ __forceinline__ void stream_store_asm(V v, V* p) {
     }
 }
 template <typename V>
-__device__ __forceinline__ void nt_store(V v, V* p) {
-#if EC_STORE_POLICY >= 2
-    stream_store_asm(v, p);
-#else
-    __builtin_nontemporal_store(v, reinterpret_cast<typename under_aligned<V>::type*>(p));
-#endif
-}
+__device__ __forceinline__ void nt_store(V v, V* p) { stream_store_asm(v, p); }
 // the mask output of a launch (1 byte per cell, moved as words)
 template <typename V>
 __device__ __forceinline__ void mask_store(V v, V* p) {
-#if EC_STORE_POLICY == 2
-    stream_store_asm(v, p);
-#else
     __builtin_nontemporal_store(v, reinterpret_cast<typename under_aligned<V>::type*>(p));
-#endif
 }
 template <typename V>
 __device__ __forceinline__ V plain_load(const V* p) {
     return *reinterpret_cast<const typename under_aligned<V>::type*>(p);
-}
-template <typename V>
-__device__ __forceinline__ void plain_store(V v, V* p) {
-    *reinterpret_cast<typename under_aligned<V>::type*>(p) = v;
 }
 
 // One cell (the peeled head cell, the odd tail cell, the ragged tail of a tile grid): non-temporal like every other
@@ -265,13 +245,7 @@ __device__ __forceinline__ void plain_store(V v, V* p) {
 template <typename T>
 __device__ __forceinline__ T ld_cell(const T* p) { return __builtin_nontemporal_load(p); }
 template <typename T>
-__device__ __forceinline__ void st_cell(T v, T* p) {
-#if EC_STORE_POLICY >= 2
-    stream_store_asm(v, p);
-#else
-    __builtin_nontemporal_store(v, p);
-#endif
-}
+__device__ __forceinline__ void st_cell(T v, T* p) { stream_store_asm(v, p); }
 
 // N cells of type T as one lane loads them.  Cells of 2 bytes and more are the typed vector.  1-BYTE cells travel as
 // unsigned words (uint16_t, uint32_t, 2 or 4 dwords) and are picked apart with shifts: hipcc (ROCm 7.2) drops the

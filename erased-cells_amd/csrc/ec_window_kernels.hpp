@@ -79,7 +79,7 @@ __device__ __forceinline__ typename width_cell<W>::type slot_get(const u32x4& v,
     else return uint64_t(v[2 * k]) | (uint64_t(v[2 * k + 1]) << 32);
 }
 
-// the 16-byte store of a value stream (write-through) or of a mask stream (ec_device.hpp, EC_STORE_POLICY)
+// the 16-byte store of a value stream (write-through) or of a mask stream (nt_store / mask_store, ec_device.hpp)
 template <bool MASK_ST>
 __device__ __forceinline__ void slot_store(u32x4 v, void* p) {
     if constexpr (MASK_ST) mask_store(v, static_cast<u32x4*>(p));

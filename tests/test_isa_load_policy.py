@@ -29,7 +29,7 @@ def test_binop_kernels_carry_the_load_policy(tmp_path):
     assert not findings, "\n".join(f"{k}: {v}" for k, v in list(findings.items())[:5])
     # the headline kernel: both policies of both operand streams are present (four arms), the u8 stream included
     text = open(asm).read()
-    name = "_ZN3ecd14k_binop_directIhtLi3ELi2ELb1ELb1EEEvPKT_PKT0_Pdmj"
+    name = "_ZN3ecd14k_binop_directIhtLi3ELi2EEEvPKT_PKT0_Pdmj"
     body = text[text.index(name + ":"):]
     body = body[:body.index("s_endpgm")]
     ushort = [l for l in body.split("\n") if "global_load_ushort" in l]

@@ -221,7 +221,10 @@ __global__ __launch_bounds__(256) void k_write_tile(u32x4* __restrict__ d) {
     size_t base = size_t(blockIdx.x) * 256 * U + threadIdx.x;
     u32x4 v = {1, 2, 3, 4};
 #pragma unroll
-    for (int j = 0; j < U; ++j) store_vec<NT>(d + base + j * 256, v);
+    for (int j = 0; j < U; ++j) {
+        if constexpr (NT) nt_store(v, d + base + j * 256);  // the library's streaming store
+        else d[base + j * 256] = v;
+    }
 }
 template <int U>
 __global__ __launch_bounds__(256) void k_read_tile(const u32x4* __restrict__ s, uint32_t* sink) {
@@ -299,9 +302,9 @@ int main(int argc, char** argv) {
         add("lds2 add U2 wave-private slab, dword/dwordx2 loads, perm2", b11, [=]() { k_lds2<1, true, EC_ADD, 2><<<unsigned(n / 1024), 256>>>(a, b, out, n); });
     }
     add("LIB k_binop_direct div U2 nt/nt (library kernel, same buffers)", b11, [=]() {
-        k_binop_direct<uint8_t, uint16_t, EC_DIV, 2, true, true><<<unsigned((n / 2 + 511) / 512), 256>>>(a, b, out, n); });
+        k_binop_direct<uint8_t, uint16_t, EC_DIV, 2><<<unsigned((n / 2 + 511) / 512), 256>>>(a, b, out, n); });
     add("LIB k_binop_direct add U2 nt/nt (library kernel, same buffers)", b11, [=]() {
-        k_binop_direct<uint8_t, uint16_t, EC_ADD, 2, true, true><<<unsigned((n / 2 + 511) / 512), 256>>>(a, b, out, n); });
+        k_binop_direct<uint8_t, uint16_t, EC_ADD, 2><<<unsigned((n / 2 + 511) / 512), 256>>>(a, b, out, n); });
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));

@@ -42,7 +42,7 @@ template <typename L, typename R, int OP, int U>
 static void one(const char* name, const void* l, const void* r, double* out, size_t n) {
     const size_t tiles = ((n >> 1) + size_t(kBlock) * U - 1) / (size_t(kBlock) * U);
     const float ms = timed([&] {
-        k_binop_direct<L, R, OP, U, true, true><<<unsigned(tiles), kBlock>>>(static_cast<const L*>(l), static_cast<const R*>(r), out, n, 0u);
+        k_binop_direct<L, R, OP, U><<<unsigned(tiles), kBlock>>>(static_cast<const L*>(l), static_cast<const R*>(r), out, n, 0u);
     });
     const double bpc = sizeof(L) + sizeof(R) + 8;
     printf("%-34s U=%d  %.4f ms  %.1f Gcells/s  %.3f of 8 TB/s\n", name, U, ms, n / (ms * 1e-3) / 1e9, bpc * n / (ms * 1e-3) / 1e9 / 8000);

@@ -141,7 +141,7 @@ static void L1v() {
 template <typename L, typename R, int OP>
 static void Lib() {  // the library kernel as shipped, for reference
     const size_t tiles = ((gn >> 1) + size_t(kBlock) * 2 - 1) / (size_t(kBlock) * 2);
-    k_binop_direct<L, R, OP, 2, true, true><<<unsigned(tiles), kBlock>>>(static_cast<const L*>(ga), static_cast<const R*>(gb), gout, gn, 0u);
+    k_binop_direct<L, R, OP, 2><<<unsigned(tiles), kBlock>>>(static_cast<const L*>(ga), static_cast<const R*>(gb), gout, gn, 0u);
 }
 
 static double checksum() {

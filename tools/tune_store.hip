@@ -731,13 +731,13 @@ int main(int argc, char** argv) {
 #elif EC_STORE_SWEEP == 4
     WG(4, false, false) WG(4, false, true) WG(1, false, true) WG(4, true, false) WG(4, true, true) WG(1, true, false) WG(1, true, true)
     vs.push_back(Variant{"sca LIB k_binop_scalar_direct<u8, Mul, 2> (the library's kernel, its own stores), all loads nt",
-                         [=](int i) { k_binop_scalar_direct<uint8_t, EC_MUL, 2, true, true><<<unsigned((n / 2 + 511) / 512), 256>>>(a[i % SETS], 2.0, out[i & 1], n, 0u); }, 9.0 * double(n), false, {}});
+                         [=](int i) { k_binop_scalar_direct<uint8_t, EC_MUL, 2><<<unsigned((n / 2 + 511) / 512), 256>>>(a[i % SETS], 2.0, out[i & 1], n, 0u); }, 9.0 * double(n), false, {}});
     vs.push_back(Variant{"sca LIB k_binop_scalar_direct<u8, Mul, 2>, operand cacheable (policy bit 0)",
-                         [=](int i) { k_binop_scalar_direct<uint8_t, EC_MUL, 2, true, true><<<unsigned((n / 2 + 511) / 512), 256>>>(a[i % SETS], 2.0, out[i & 1], n, 1u << 8); }, 9.0 * double(n), false, {}});
+                         [=](int i) { k_binop_scalar_direct<uint8_t, EC_MUL, 2><<<unsigned((n / 2 + 511) / 512), 256>>>(a[i % SETS], 2.0, out[i & 1], n, 1u << 8); }, 9.0 * double(n), false, {}});
     vs.push_back(Variant{"sca library-shaped tile, NaN rule per cell (cell_op<Mul, true>)", [=](int i) { k_scalar_lib_shape<true><<<unsigned(n / 1024), 256>>>(a[i % SETS], 2.0, out[i & 1], n); }, 9.0 * double(n), false, {}});
     vs.push_back(Variant{"sca library-shaped tile, no NaN rule (cell_op<Mul, false>)", [=](int i) { k_scalar_lib_shape<false><<<unsigned(n / 1024), 256>>>(a[i % SETS], 2.0, out[i & 1], n); }, 9.0 * double(n), false, {}});
     vs.push_back(Variant{"mix LIB k_binop_direct<u8, u16, Add, 2> (the library's kernel), all loads nt",
-                         [=](int i) { k_binop_direct<uint8_t, uint16_t, EC_ADD, 2, true, true><<<unsigned((n / 2 + 511) / 512), 256>>>(a[i % SETS], b[i % SETS], out[i & 1], n, 0u); }, 11.0 * double(n), false, {}});
+                         [=](int i) { k_binop_direct<uint8_t, uint16_t, EC_ADD, 2><<<unsigned((n / 2 + 511) / 512), 256>>>(a[i % SETS], b[i % SETS], out[i & 1], n, 0u); }, 11.0 * double(n), false, {}});
 #elif EC_STORE_SWEEP == 5
     ST(2, 4, false, 4, 1, 1, 0, true)
     ST(2, 4, false, 1, 1, 1, 0, true)
@@ -791,7 +791,7 @@ int main(int argc, char** argv) {
     SW(8, 1, 4, 8) SW(8, 1, 4, 12) SW(8, 1, 4, 16) SW(8, 1, 4, 24)
     SW(8, 4, 1, 48) SW(8, 4, 1, 32)
     vs.push_back(Variant{"sca LIB k_binop_scalar_direct<u8, Mul, 2> without the NaN rule (what the library launches), all loads nt",
-                         [=](int i) { k_binop_scalar_direct<uint8_t, EC_MUL, 2, true, true, false><<<unsigned((n / 2 + 511) / 512), 256>>>(a[i % SETS], 2.0, out[i & 1], n, 0u); }, 9.0 * double(n), false, {}});
+                         [=](int i) { k_binop_scalar_direct<uint8_t, EC_MUL, 2, false><<<unsigned((n / 2 + 511) / 512), 256>>>(a[i % SETS], 2.0, out[i & 1], n, 0u); }, 9.0 * double(n), false, {}});
 #elif EC_STORE_SWEEP == 8
     ST(2, 4, false, 4, 1, 1, 0, true)
 #define M8(WAVES, LDSKB, CLOBBER)                                                                                                      \
@@ -807,7 +807,7 @@ int main(int argc, char** argv) {
     M8(4, 32, true) M8(2, 16, true)
     MW(4, 4, 4, 32) MW(4, 4, 4, 24)
     vs.push_back(Variant{"mix LIB k_binop_direct<u8, u16, Add, 2> (the library's kernel), all loads nt",
-                         [=](int i) { k_binop_direct<uint8_t, uint16_t, EC_ADD, 2, true, true><<<unsigned((n / 2 + 511) / 512), 256>>>(a[i % SETS], b[i % SETS], out[i & 1], n, 0u); }, 11.0 * double(n), false, {}});
+                         [=](int i) { k_binop_direct<uint8_t, uint16_t, EC_ADD, 2><<<unsigned((n / 2 + 511) / 512), 256>>>(a[i % SETS], b[i % SETS], out[i & 1], n, 0u); }, 11.0 * double(n), false, {}});
 #elif EC_STORE_SWEEP == 3
     SWEEP3
 #else
