@@ -128,13 +128,13 @@ extern "C" ec_status ec_comm_init_all(const int32_t* devices, int32_t n, ec_comm
         for (int j = 0; j < i; ++j)
             if (devices[i] == devices[j])
                 return set_error(EC_ERR_ARG, "ec_comm_init_all: device %d listed twice (RCCL needs one rank per GPU)", int(devices[i]));
-    int32_t before = -1;
-    const bool had = ec_get_device(&before) == EC_OK;
-    for (int i = 0; i < n; ++i) {  // every device of the clique gets its runtime state
-        ec_status st = ec_init(devices[i]);
-        if (st != EC_OK) return st;
+    {   // every device of the clique gets its runtime state; the caller is back on its own device afterwards, also when one fails
+        DeviceScope scope;
+        for (int i = 0; i < n; ++i) {
+            ec_status st = ec_init(devices[i]);
+            if (st != EC_OK) return st;
+        }
     }
-    if (had) (void)ec_set_device(before);
     const Rccl* R = rccl("ec_comm_init_all");
     if (!R) return EC_ERR_RCCL;
     std::vector<ncclComm_t> cs(n, nullptr);

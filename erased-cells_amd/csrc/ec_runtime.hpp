@@ -76,6 +76,25 @@ std::atomic<int64_t>& lds_rule_launches();  // binop launches that took the LDS-
 ec_status check_launch(const char* what);
 ec_status check_hip(hipError_t e, const char* what);
 
+// Work on other devices from a thread that may have one of its own: remembers the calling thread's library device, if it has
+// one, and puts it back on destruction if it changed — on every path out of the scope, and without touching the thread's last
+// error text, so a failure inside the scope is still the one the caller reads.
+class DeviceScope {
+    int32_t before_ = -1;
+    const bool had_;
+
+public:
+    DeviceScope() : had_(ec_get_device(&before_) == EC_OK) {}
+    DeviceScope(const DeviceScope&) = delete;
+    DeviceScope& operator=(const DeviceScope&) = delete;
+    ~DeviceScope() {
+        if (!had_ || current_device() == before_) return;
+        const std::string keep = last_error_text();
+        (void)ec_set_device(before_);
+        (void)set_error_text(EC_OK, keep);
+    }
+};
+
 // May the vector kernels run on these pointers?  Their loads and stores are declared under-aligned
 // (ec_device.hpp nt_load/nt_store), so the answer is yes at any cell offset unless the
 // "unaligned_vector" knob is turned off.

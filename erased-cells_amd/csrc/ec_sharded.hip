@@ -24,13 +24,15 @@
 // communicators are aborted (ncclCommAbort) so that no stream waits for the missing rank, and every later call returns
 // EC_ERR_RCCL.  Every wave of every kernel launched here finishes on its own (no persistent kernels), so destroying a
 // group only has to wait for its streams.
+//
+// The pieces: Worker and Latch (ec_worker.hpp: plain C++, so host/test_worker_queue.cpp runs the queue handshake under a thread
+// sanitizer); DeviceScope (ec_runtime.hpp) puts the caller's device back; check_col / copy_col / take check and copy the per-shard
+// pointer columns (the table of what is checked is at them); StreamCols holds the columns of the one-pass calls and gathers a
+// shard's operands; check_program parses an expression program on the calling thread; reduce_phased is the one phased reduction.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
 #include <cstring>
-#include <deque>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -42,75 +44,9 @@
 #include "ec_hostpipe.hpp"
 #include "ec_lattice.hpp"
 #include "ec_runtime.hpp"
+#include "ec_worker.hpp"
 
 using namespace ecd;
-
-namespace {
-
-// How long a launch thread polls its queue after a job before it goes to sleep on the condition variable.
-constexpr auto kWorkerSpin = std::chrono::microseconds(60);
-
-struct Worker {
-    int device = -1;
-    std::thread th;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<std::function<void()>> q;
-    std::atomic<int> pending{0};      // jobs in q (read by the polling worker without the lock)
-    std::atomic<bool> sleeping{false};
-    bool stop = false;
-
-    void run() {
-        (void)ec_set_device(device);  // for the life of the thread
-        for (;;) {
-            std::function<void()> job;
-            if (pending.load(std::memory_order_acquire) == 0) {  // poll, then sleep
-                const auto until = std::chrono::steady_clock::now() + kWorkerSpin;
-                while (pending.load(std::memory_order_acquire) == 0 && std::chrono::steady_clock::now() < until) __builtin_ia32_pause();
-            }
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                if (q.empty()) {
-                    sleeping.store(true, std::memory_order_release);
-                    cv.wait(lk, [&] { return stop || !q.empty(); });
-                    sleeping.store(false, std::memory_order_release);
-                    if (q.empty()) return;  // stop requested and drained
-                }
-                job = std::move(q.front());
-                q.pop_front();
-                pending.fetch_sub(1, std::memory_order_acq_rel);
-            }
-            job();
-        }
-    }
-    void post(std::function<void()> job) {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            q.push_back(std::move(job));
-            pending.fetch_add(1, std::memory_order_acq_rel);
-        }
-        // a polling worker sees `pending`; only a sleeping one needs the wake-up.  (The worker sets `sleeping` under
-        // `mu` after finding the queue empty, so a job pushed before that is found, one pushed after sees the flag.)
-        if (sleeping.load(std::memory_order_acquire)) cv.notify_one();
-    }
-};
-
-struct Latch {
-    std::mutex mu;
-    std::condition_variable cv;
-    int left;
-    explicit Latch(int n) : left(n) {}
-    void arrive() {
-        std::lock_guard<std::mutex> lk(mu);
-        if (--left == 0) cv.notify_all();
-    }
-    void wait() {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return left == 0; });
-    }
-};
-
-}  // namespace
 
 struct ec_shard_group {
     int n = 0;
@@ -151,16 +87,9 @@ ec_status take_deferred(ec_shard_group* g) {
 
 // fn(0) on the caller's thread with the group's device bound (groups of one shard have no launch threads)
 ec_status run_inline(ec_shard_group* g, const ShardFn& fn) {
-    int32_t before = -1;
-    const bool had = ec_get_device(&before) == EC_OK;
-    ec_status st = ec_set_device(g->devices[0]);
-    if (st == EC_OK) st = fn(0);
-    if (had && before != g->devices[0]) {
-        const std::string keep = last_error_text();
-        (void)ec_set_device(before);
-        if (st != EC_OK) set_error_text(st, keep);
-    }
-    return st;
+    DeviceScope scope;
+    const ec_status st = ec_set_device(g->devices[0]);
+    return st == EC_OK ? fn(0) : st;
 }
 
 // fn(i) on every shard's launch thread, concurrently; waits for all; every status is collected, the first failing one
@@ -212,16 +141,61 @@ ec_status check_group(const ec_shard_group* g, const char* what) {
     return EC_OK;
 }
 
-// n[i] cells at p[i] for every shard: no null pointer where there are cells (checked on the calling thread, before
-// any fan-out: a shard that failed alone would otherwise leave the others inside a collective)
-ec_status check_shard_ptrs(const ec_shard_group* g, const char* what, const char* name, const void* const* p, const size_t* n) {
+// ---- the per-shard pointer columns of a call: col[i] is shard i's pointer, n[i] its cell count
+// A CHECKED column has no null pointer where there are cells: it is refused on the calling thread, before any fan-out (a shard
+// that failed alone would otherwise leave the others inside a collective).  What each entry point checks, in this order; the
+// element-wise calls also copy their columns (they return before the launch threads read them):
+//   ec_sharded_binop              l, r, out
+//   ec_sharded_masked_binop       l, r, lmask, rmask, out, out_mask
+//   ec_sharded_convert            src, dst
+//   ec_sharded_mask_from_nodata   p, mask
+//   ec_sharded_fused              p[k] of every operand with a column, out.  NOT masks[k] and out_mask: they are copied
+//                                 unchecked, a null per-shard mask reaches ec_masked_fused as it is
+//   ec_sharded_expr               p[k] and (masked) masks[k] stream by stream, out, (masked) out_mask
+//   ec_sharded_min_max            p, (masked) masks                            — read in place, as are the next two
+//   ec_sharded_expr_min_max       p[k] and (masked) masks[k] stream by stream  — copied, for StreamCols::gather
+//   ec_sharded_counts             masks
+//   ec_sharded_alloc / _free / _upload / _download: no column is checked
+template <typename P>
+ec_status check_col(const ec_shard_group* g, const char* what, const char* name, const P* col, const size_t* n) {
     for (int i = 0; i < g->n; ++i)
-        if (n[i] > 0 && !p[i]) return set_error(EC_ERR_ARG, "%s: %s[%d] is null with n[%d] = %zu", what, name, i, i, n[i]);
+        if (n[i] > 0 && !col[i]) return set_error(EC_ERR_ARG, "%s: %s[%d] is null with n[%d] = %zu", what, name, i, i, n[i]);
     return EC_OK;
 }
 
 template <typename P>
-std::vector<P> copy_n(const P* a, int n) { return std::vector<P>(a, a + n); }
+std::vector<P> copy_col(const ec_shard_group* g, const P* col) { return std::vector<P>(col, col + g->n); }
+
+// check and copy in one step; `*st` is sticky: after a refusal nothing more is checked or copied, so a run of takes ends in one test
+template <typename P>
+std::vector<P> take(const ec_shard_group* g, const char* what, const char* name, const P* col, const size_t* n, ec_status* st) {
+    if (*st == EC_OK) *st = check_col(g, what, name, col, n);
+    return *st == EC_OK ? copy_col(g, col) : std::vector<P>();
+}
+
+// The columns of a one-pass call over up to 4 operand slots (ec_sharded_fused, ec_sharded_expr, ec_sharded_expr_min_max): an
+// empty vector is a slot without a column (a scalar operand of a fused chain, a stream past the program's, an unmasked call).
+struct StreamCols {
+    std::vector<const void*> p[4];
+    std::vector<const uint8_t*> m[4];
+    std::vector<size_t> n;
+    std::vector<double*> out;
+    std::vector<uint8_t*> om;  // empty: no out_mask
+
+    // shard i's operand and mask pointers, null where the slot has no column
+    void gather(int i, const void* pi[4], const uint8_t* mi[4]) const {
+        for (int k = 0; k < 4; ++k) {
+            pi[k] = p[k].empty() ? nullptr : p[k][i];
+            mi[k] = m[k].empty() ? nullptr : m[k][i];
+        }
+    }
+};
+
+// the program: parsed once, on the calling thread (no device needed), so that a malformed one is refused before anything is posted
+ec_status check_program(const ec_dtype* dt, int32_t n_streams, int32_t n_scalars, const ec_expr_step* steps, int32_t n_steps) {
+    size_t len = 0;
+    return ec_expr_source(dt, n_streams, n_scalars, steps, n_steps, nullptr, nullptr, 0, &len);
+}
 
 void poison(ec_shard_group* g) {
     g->poisoned.store(true, std::memory_order_release);
@@ -259,6 +233,30 @@ ec_status exchange(ec_shard_group* g, bool is_keys) {
     });
 }
 
+enum class Combine { keys, counts };  // element-wise MAX of {~key(min), key(max)}; SUM of {n_true, n_false}
+
+// A reduction over the group, call_mu held by the caller.  Phase 1: `local(i)` reduces shard i to payload_dev[i][0..1] (an empty
+// shard contributes the idempotent payload: the sentinels (T::MAX, T::MIN) of src/buffer.rs:170, zero counts).  A failure that an
+// earlier fire-and-forget call left behind comes first (its output may feed this reduction), then a failure of phase 1 — nothing
+// has been enqueued on any communicator.  Only then the exchange; without communicators the host words are folded here.
+ec_status reduce_phased(ec_shard_group* g, const ShardFn& local, Combine kind, int64_t out[2]) {
+    ec_status st = for_each_shard(g, local);
+    const std::string keep = last_error_text();
+    const ec_status deferred = take_deferred(g);
+    if (deferred != EC_OK) return deferred;
+    if (st != EC_OK) return set_error_text(st, keep);
+    if ((st = exchange(g, kind == Combine::keys)) != EC_OK) return st;
+    for (int w = 0; w < 2; ++w) {
+        out[w] = g->payload_host[0][w];
+        for (int i = 1; g->comms.empty() && i < g->n; ++i) {
+            const int64_t v = g->payload_host[i][w];
+            if (kind == Combine::counts) out[w] = static_cast<int64_t>(static_cast<uint64_t>(out[w]) + static_cast<uint64_t>(v));
+            else if (v > out[w]) out[w] = v;
+        }
+    }
+    return EC_OK;
+}
+
 }  // namespace
 
 extern "C" ec_status ec_shard_group_create(const int32_t* devices, int32_t n, uint32_t flags, ec_shard_group** out) {
@@ -271,8 +269,7 @@ extern "C" ec_status ec_shard_group_create(const int32_t* devices, int32_t n, ui
                 if (devices[i] == devices[j])
                     return set_error(EC_ERR_ARG, "ec_shard_group_create: device %d listed twice (RCCL needs one rank per GPU; "
                                                  "EC_GROUP_HOST_COMBINE allows it)", int(devices[i]));
-    int32_t before = -1;
-    const bool had = ec_get_device(&before) == EC_OK;
+    DeviceScope scope;
     std::unique_ptr<ec_shard_group> g(new ec_shard_group);
     g->n = n;
     g->flags = flags;
@@ -301,14 +298,15 @@ extern "C" ec_status ec_shard_group_create(const int32_t* devices, int32_t n, ui
     if (st == EC_OK && n > 1) {
         for (int i = 0; i < n; ++i) {
             Worker* w = new Worker;
-            w->device = devices[i];
             g->workers.push_back(w);
-            w->th = std::thread([w] { w->run(); });
+            w->th = std::thread([w, device = devices[i]] {
+                (void)ec_set_device(device);  // for the life of the thread
+                w->run();
+            });
         }
     }
-    const std::string keep = last_error_text();
-    if (had) (void)ec_set_device(before);
     if (st != EC_OK) {
+        const std::string keep = last_error_text();  // why the creation failed, whatever the clean-up has to say
         (void)ec_shard_group_destroy(g.release());
         return set_error_text(st, keep);
     }
@@ -319,17 +317,11 @@ extern "C" ec_status ec_shard_group_create(const int32_t* devices, int32_t n, ui
 extern "C" ec_status ec_shard_group_destroy(ec_shard_group* g) {
     if (!g) return EC_OK;
     for (Worker* w : g->workers) {
-        {
-            std::lock_guard<std::mutex> lk(w->mu);
-            w->stop = true;
-        }
-        w->cv.notify_one();
-        if (w->th.joinable()) w->th.join();
+        w->stop_and_join();  // runs what is still queued
         delete w;
     }
     g->workers.clear();
-    int32_t before = -1;
-    const bool had = ec_get_device(&before) == EC_OK;
+    DeviceScope scope;
     for (int i = 0; i < g->n; ++i) {
         if (ec_set_device(g->devices[i]) != EC_OK) continue;
         if (g->streams[i]) (void)hipStreamSynchronize(g->streams[i]);
@@ -338,7 +330,6 @@ extern "C" ec_status ec_shard_group_destroy(ec_shard_group* g) {
         if (g->payload_host[i]) (void)hipHostFree(g->payload_host[i]);
         if (g->streams[i]) (void)ec_stream_destroy(g->streams[i]);
     }
-    if (had) (void)ec_set_device(before);
     delete g;
     return EC_OK;
 }
@@ -437,11 +428,13 @@ extern "C" ec_status ec_sharded_binop(ec_shard_group* g, ec_op op, ec_dtype lt, 
     if (!l || !r || !n || !out) return set_error(EC_ERR_ARG, "ec_sharded_binop: null argument");
     if (op < EC_ADD || op > EC_DIV) return set_error(EC_ERR_ARG, "ec_sharded_binop: bad op");
     if (!ecl::valid(lt) || !ecl::valid(rt)) return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_sharded_binop: bad dtype");
-    if ((st = check_shard_ptrs(g, "ec_sharded_binop", "l", l, n)) != EC_OK) return st;
-    if ((st = check_shard_ptrs(g, "ec_sharded_binop", "r", r, n)) != EC_OK) return st;
-    if ((st = check_shard_ptrs(g, "ec_sharded_binop", "out", reinterpret_cast<const void* const*>(out), n)) != EC_OK) return st;
+    const char* what = "ec_sharded_binop";
+    auto lv = take(g, what, "l", l, n, &st);
+    auto rv = take(g, what, "r", r, n, &st);
+    auto ov = take(g, what, "out", out, n, &st);
+    if (st != EC_OK) return st;
     std::lock_guard<std::mutex> lk(g->call_mu);
-    return post_each_shard(g, [g, op, lt, rt, l = copy_n(l, g->n), r = copy_n(r, g->n), n = copy_n(n, g->n), out = copy_n(out, g->n)](int i) {
+    return post_each_shard(g, [g, op, lt, rt, l = std::move(lv), r = std::move(rv), n = copy_col(g, n), out = std::move(ov)](int i) {
         return ec_binop(op, lt, l[i], rt, r[i], n[i], out[i], g->streams[i]);
     });
 }
@@ -455,15 +448,16 @@ extern "C" ec_status ec_sharded_masked_binop(ec_shard_group* g, ec_op op, ec_dty
     if (op < EC_ADD || op > EC_DIV) return set_error(EC_ERR_ARG, "ec_sharded_masked_binop: bad op");
     if (!ecl::valid(lt) || !ecl::valid(rt)) return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_sharded_masked_binop: bad dtype");
     const char* what = "ec_sharded_masked_binop";
-    if ((st = check_shard_ptrs(g, what, "l", l, n)) != EC_OK) return st;
-    if ((st = check_shard_ptrs(g, what, "r", r, n)) != EC_OK) return st;
-    if ((st = check_shard_ptrs(g, what, "lmask", reinterpret_cast<const void* const*>(lmask), n)) != EC_OK) return st;
-    if ((st = check_shard_ptrs(g, what, "rmask", reinterpret_cast<const void* const*>(rmask), n)) != EC_OK) return st;
-    if ((st = check_shard_ptrs(g, what, "out", reinterpret_cast<const void* const*>(out), n)) != EC_OK) return st;
-    if ((st = check_shard_ptrs(g, what, "out_mask", reinterpret_cast<const void* const*>(out_mask), n)) != EC_OK) return st;
+    auto lv = take(g, what, "l", l, n, &st);
+    auto rv = take(g, what, "r", r, n, &st);
+    auto lmv = take(g, what, "lmask", lmask, n, &st);
+    auto rmv = take(g, what, "rmask", rmask, n, &st);
+    auto ov = take(g, what, "out", out, n, &st);
+    auto omv = take(g, what, "out_mask", out_mask, n, &st);
+    if (st != EC_OK) return st;
     std::lock_guard<std::mutex> lk(g->call_mu);
-    return post_each_shard(g, [g, op, lt, rt, l = copy_n(l, g->n), lm = copy_n(lmask, g->n), r = copy_n(r, g->n), rm = copy_n(rmask, g->n),
-                               n = copy_n(n, g->n), out = copy_n(out, g->n), om = copy_n(out_mask, g->n)](int i) {
+    return post_each_shard(g, [g, op, lt, rt, l = std::move(lv), lm = std::move(lmv), r = std::move(rv), rm = std::move(rmv),
+                               n = copy_col(g, n), out = std::move(ov), om = std::move(omv)](int i) {
         return ec_masked_binop(op, lt, l[i], lm[i], rt, r[i], rm[i], n[i], out[i], om[i], g->streams[i]);
     });
 }
@@ -475,10 +469,11 @@ extern "C" ec_status ec_sharded_convert(ec_shard_group* g, ec_dtype st_, const v
     if (!ecl::valid(st_) || !ecl::valid(dt)) return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_sharded_convert: bad dtype");
     if (!ec_can_fit_into(st_, dt)) return ec_convert(st_, nullptr, dt, nullptr, 0, nullptr);  // EC_ERR_NARROWING, before any device work
     if (!src || !dst || !n) return set_error(EC_ERR_ARG, "ec_sharded_convert: null argument");
-    if ((st = check_shard_ptrs(g, "ec_sharded_convert", "src", src, n)) != EC_OK) return st;
-    if ((st = check_shard_ptrs(g, "ec_sharded_convert", "dst", dst, n)) != EC_OK) return st;
+    auto sv = take(g, "ec_sharded_convert", "src", src, n, &st);
+    auto dv = take(g, "ec_sharded_convert", "dst", dst, n, &st);
+    if (st != EC_OK) return st;
     std::lock_guard<std::mutex> lk(g->call_mu);
-    return post_each_shard(g, [g, st_, dt, src = copy_n(src, g->n), dst = copy_n(dst, g->n), n = copy_n(n, g->n)](int i) {
+    return post_each_shard(g, [g, st_, dt, src = std::move(sv), dst = std::move(dv), n = copy_col(g, n)](int i) {
         return ec_convert(st_, src[i], dt, dst[i], n[i], g->streams[i]);
     });
 }
@@ -489,12 +484,13 @@ extern "C" ec_status ec_sharded_mask_from_nodata(ec_shard_group* g, ec_dtype t, 
     if (st != EC_OK) return st;
     if (!p || !n || !mask) return set_error(EC_ERR_ARG, "ec_sharded_mask_from_nodata: null argument");
     if (!ecl::valid(t)) return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_sharded_mask_from_nodata: bad dtype");
-    if ((st = check_shard_ptrs(g, "ec_sharded_mask_from_nodata", "p", p, n)) != EC_OK) return st;
-    if ((st = check_shard_ptrs(g, "ec_sharded_mask_from_nodata", "mask", reinterpret_cast<const void* const*>(mask), n)) != EC_OK) return st;
+    auto pv = take(g, "ec_sharded_mask_from_nodata", "p", p, n, &st);
+    auto mv = take(g, "ec_sharded_mask_from_nodata", "mask", mask, n, &st);
+    if (st != EC_OK) return st;
     const bool has_nd = nd_or_null != nullptr;
     const ec_value nd = has_nd ? *nd_or_null : ec_value{};
     std::lock_guard<std::mutex> lk(g->call_mu);
-    return post_each_shard(g, [g, t, has_nd, nd, p = copy_n(p, g->n), n = copy_n(n, g->n), mask = copy_n(mask, g->n)](int i) {
+    return post_each_shard(g, [g, t, has_nd, nd, p = std::move(pv), n = copy_col(g, n), mask = std::move(mv)](int i) {
         return ec_mask_from_nodata(t, p[i], n[i], has_nd ? &nd : nullptr, mask[i], g->streams[i]);
     });
 }
@@ -508,16 +504,11 @@ extern "C" ec_status ec_sharded_fused(ec_shard_group* g, ec_op o1, ec_op o2, ec_
     if ((masks_or_null != nullptr) != (out_mask_or_null != nullptr))
         return set_error(EC_ERR_ARG, "ec_sharded_fused: masks and out_mask go together");
     const int nops = o3 == static_cast<ec_op>(-1) ? 3 : 4;
-    struct Call {
+    struct Call : StreamCols {
         ec_op o1, o2, o3;
         ec_dtype dt[4];
-        bool has_p[4], has_m[4], masked, has_sc;
-        std::vector<const void*> p[4];
-        std::vector<const uint8_t*> m[4];
+        bool masked, has_sc;
         ec_value sc[4];
-        std::vector<size_t> n;
-        std::vector<double*> out;
-        std::vector<uint8_t*> om;
     };
     auto c = std::make_shared<Call>();
     c->o1 = o1; c->o2 = o2; c->o3 = o3;
@@ -525,27 +516,21 @@ extern "C" ec_status ec_sharded_fused(ec_shard_group* g, ec_op o1, ec_op o2, ec_
     c->has_sc = scalars_or_null != nullptr;
     for (int k = 0; k < 4; ++k) {
         c->dt[k] = dt[k];
-        c->has_p[k] = k < nops && p[k] != nullptr;
-        c->has_m[k] = c->has_p[k] && masks_or_null && masks_or_null[k] != nullptr;
-        if (c->has_p[k]) {
-            if ((st = check_shard_ptrs(g, "ec_sharded_fused", "p[k]", p[k], n)) != EC_OK) return st;
-            c->p[k] = copy_n(p[k], g->n);
-        }
-        if (c->has_m[k]) c->m[k] = copy_n(masks_or_null[k], g->n);
         c->sc[k] = scalars_or_null ? scalars_or_null[k] : ec_value{};
+        if (k >= nops || !p[k]) continue;  // no pointer array: operand k is the scalar scalars[k]
+        c->p[k] = take(g, "ec_sharded_fused", "p[k]", p[k], n, &st);
+        if (st != EC_OK) return st;
+        if (masks_or_null && masks_or_null[k]) c->m[k] = copy_col(g, masks_or_null[k]);  // unchecked (see the table)
     }
-    if ((st = check_shard_ptrs(g, "ec_sharded_fused", "out", reinterpret_cast<const void* const*>(out), n)) != EC_OK) return st;
-    c->n = copy_n(n, g->n);
-    c->out = copy_n(out, g->n);
-    if (out_mask_or_null) c->om = copy_n(out_mask_or_null, g->n);
+    c->out = take(g, "ec_sharded_fused", "out", out, n, &st);
+    if (st != EC_OK) return st;
+    c->n = copy_col(g, n);
+    if (out_mask_or_null) c->om = copy_col(g, out_mask_or_null);  // unchecked
     std::lock_guard<std::mutex> lk(g->call_mu);
     return post_each_shard(g, [g, c](int i) {
         const void* pi[4];
         const uint8_t* mi[4];
-        for (int k = 0; k < 4; ++k) {
-            pi[k] = c->has_p[k] ? c->p[k][i] : nullptr;  // no pointer array: operand k is the scalar scalars[k]
-            mi[k] = c->has_m[k] ? c->m[k][i] : nullptr;
-        }
+        c->gather(i, pi, mi);
         const ec_value* sc = c->has_sc ? c->sc : nullptr;
         if (c->masked) return ec_masked_fused(c->o1, c->o2, c->o3, c->dt, pi, mi, sc, c->n[i], c->out[i], c->om[i], g->streams[i]);
         return ec_fused(c->o1, c->o2, c->o3, c->dt, pi, sc, c->n[i], c->out[i], g->streams[i]);
@@ -564,21 +549,13 @@ extern "C" ec_status ec_sharded_expr(ec_shard_group* g, const ec_dtype* dt, cons
     if (n_streams < 1 || n_streams > 4 || n_scalars < 0 || n_scalars > 8 || n_steps < 1 || n_steps > 16)
         return set_error(EC_ERR_ARG, "ec_sharded_expr: %d streams (1..4), %d scalars (0..8), %d steps (1..16)", int(n_streams), int(n_scalars), int(n_steps));
     if ((masks_or_null != nullptr) != (out_mask_or_null != nullptr)) return set_error(EC_ERR_ARG, "ec_sharded_expr: masks and out_mask go together");
-    {   // the program: parsed once here (no device needed), so that a malformed one is refused before anything is posted
-        size_t len = 0;
-        if ((st = ec_expr_source(dt, n_streams, n_scalars, steps, n_steps, nullptr, nullptr, 0, &len)) != EC_OK) return st;
-    }
-    struct Call {
+    if ((st = check_program(dt, n_streams, n_scalars, steps, n_steps)) != EC_OK) return st;
+    struct Call : StreamCols {
         int32_t ns, nsc, nst;
         ec_dtype dt[4];
         ec_value sc[8];
         ec_expr_step steps[16];
         bool masked;
-        std::vector<const void*> p[4];
-        std::vector<const uint8_t*> m[4];
-        std::vector<size_t> n;
-        std::vector<double*> out;
-        std::vector<uint8_t*> om;
     };
     auto c = std::make_shared<Call>();
     c->ns = n_streams; c->nsc = n_scalars; c->nst = n_steps;
@@ -586,30 +563,21 @@ extern "C" ec_status ec_sharded_expr(ec_shard_group* g, const ec_dtype* dt, cons
     for (int k = 0; k < n_streams; ++k) {
         c->dt[k] = dt[k];
         if (!p[k] || (c->masked && !masks_or_null[k])) return set_error(EC_ERR_ARG, "ec_sharded_expr: stream %d has no pointer array", k);
-        if ((st = check_shard_ptrs(g, "ec_sharded_expr", "p[k]", p[k], n)) != EC_OK) return st;
-        c->p[k] = copy_n(p[k], g->n);
-        if (c->masked) {
-            if ((st = check_shard_ptrs(g, "ec_sharded_expr", "masks[k]", reinterpret_cast<const void* const*>(masks_or_null[k]), n)) != EC_OK) return st;
-            c->m[k] = copy_n(masks_or_null[k], g->n);
-        }
+        c->p[k] = take(g, "ec_sharded_expr", "p[k]", p[k], n, &st);
+        if (c->masked) c->m[k] = take(g, "ec_sharded_expr", "masks[k]", masks_or_null[k], n, &st);
+        if (st != EC_OK) return st;  // before the next stream's own refusal
     }
     for (int k = 0; k < n_scalars; ++k) c->sc[k] = scalars[k];
     for (int k = 0; k < n_steps; ++k) c->steps[k] = steps[k];
-    if ((st = check_shard_ptrs(g, "ec_sharded_expr", "out", reinterpret_cast<const void* const*>(out), n)) != EC_OK) return st;
-    c->n = copy_n(n, g->n);
-    c->out = copy_n(out, g->n);
-    if (out_mask_or_null) {
-        if ((st = check_shard_ptrs(g, "ec_sharded_expr", "out_mask", reinterpret_cast<const void* const*>(out_mask_or_null), n)) != EC_OK) return st;
-        c->om = copy_n(out_mask_or_null, g->n);
-    }
+    c->out = take(g, "ec_sharded_expr", "out", out, n, &st);
+    if (out_mask_or_null) c->om = take(g, "ec_sharded_expr", "out_mask", out_mask_or_null, n, &st);
+    if (st != EC_OK) return st;
+    c->n = copy_col(g, n);
     std::lock_guard<std::mutex> lk(g->call_mu);
     return post_each_shard(g, [g, c](int i) {
-        const void* pi[4] = {nullptr, nullptr, nullptr, nullptr};
-        const uint8_t* mi[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (int k = 0; k < c->ns; ++k) {
-            pi[k] = c->p[k][i];
-            if (c->masked) mi[k] = c->m[k][i];
-        }
+        const void* pi[4];
+        const uint8_t* mi[4];
+        c->gather(i, pi, mi);
         if (c->masked) return ec_masked_expr(c->dt, pi, mi, c->ns, c->sc, c->nsc, c->steps, c->nst, c->n[i], c->out[i], c->om[i], g->streams[i]);
         return ec_expr(c->dt, pi, c->ns, c->sc, c->nsc, c->steps, c->nst, c->n[i], c->out[i], g->streams[i]);
     });
@@ -625,10 +593,7 @@ extern "C" ec_status ec_sharded_host_expr(ec_shard_group* g, const ec_dtype* dt,
     ec_status st = check_group(g, "ec_sharded_host_expr");
     if (st != EC_OK) return st;
     if (!dt || !p_host || !steps || !out_host) return set_error(EC_ERR_ARG, "ec_sharded_host_expr: null argument");
-    {   // the program, once, on the calling thread
-        size_t len = 0;
-        if ((st = ec_expr_source(dt, n_streams, n_scalars, steps, n_steps, nullptr, nullptr, 0, &len)) != EC_OK) return st;
-    }
+    if ((st = check_program(dt, n_streams, n_scalars, steps, n_steps)) != EC_OK) return st;
     for (int k = 0; k < n_streams; ++k)
         if (!p_host[k]) return set_error(EC_ERR_ARG, "ec_sharded_host_expr: stream %d is null", k);
     // everything a shard's pipeline would refuse is refused here, on the calling thread, before a page is locked
@@ -678,26 +643,14 @@ extern "C" ec_status ec_sharded_min_max(ec_shard_group* g, ec_dtype t, const voi
     if (st != EC_OK) return st;
     if (!p || !n || !mn || !mx) return set_error(EC_ERR_ARG, "ec_sharded_min_max: null argument");
     if (!ecl::valid(t)) return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_sharded_min_max: bad dtype");
-    if ((st = check_shard_ptrs(g, "ec_sharded_min_max", "p", p, n)) != EC_OK) return st;
-    if (masks_or_null && (st = check_shard_ptrs(g, "ec_sharded_min_max", "masks", reinterpret_cast<const void* const*>(masks_or_null), n)) != EC_OK) return st;
+    if ((st = check_col(g, "ec_sharded_min_max", "p", p, n)) != EC_OK) return st;
+    if (masks_or_null && (st = check_col(g, "ec_sharded_min_max", "masks", masks_or_null, n)) != EC_OK) return st;
     std::lock_guard<std::mutex> lk(g->call_mu);
-    // phase 1: local reductions everywhere (an empty shard contributes the idempotent sentinels (T::MAX, T::MIN): src/buffer.rs:170)
-    st = for_each_shard(g, [&](int i) {
+    int64_t keys[2];
+    st = reduce_phased(g, [&](int i) {
         return ec_min_max_keys(t, p[i], masks_or_null ? masks_or_null[i] : nullptr, n[i], g->payload_dev[i], g->streams[i]);
-    });
-    const std::string keep = last_error_text();
-    const ec_status deferred = take_deferred(g);  // an earlier fire-and-forget call that failed: its output may feed this reduction
-    if (deferred != EC_OK) return deferred;
-    if (st != EC_OK) return set_error_text(st, keep);  // nothing was enqueued on any communicator
-    st = exchange(g, true);
-    if (st != EC_OK) return st;
-    int64_t keys[2] = {g->payload_host[0][0], g->payload_host[0][1]};
-    if (g->comms.empty())  // host combine: element-wise MAX of {~key(min), key(max)}
-        for (int i = 1; i < g->n; ++i) {
-            if (g->payload_host[i][0] > keys[0]) keys[0] = g->payload_host[i][0];
-            if (g->payload_host[i][1] > keys[1]) keys[1] = g->payload_host[i][1];
-        }
-    return ec_min_max_decode(t, keys, mn, mx);
+    }, Combine::keys, keys);
+    return st == EC_OK ? ec_min_max_decode(t, keys, mn, mx) : st;
 }
 
 // min_max of an expression program's result over the whole sharded raster, without the raster: ec_expr_min_max_keys per shard
@@ -710,38 +663,23 @@ extern "C" ec_status ec_sharded_expr_min_max(ec_shard_group* g, const ec_dtype* 
     ec_status st = check_group(g, "ec_sharded_expr_min_max");
     if (st != EC_OK) return st;
     if (!dt || !p || !steps || !n || !mn || !mx || (n_scalars > 0 && !scalars)) return set_error(EC_ERR_ARG, "ec_sharded_expr_min_max: null argument");
-    {   // the program, once, on the calling thread
-        size_t len = 0;
-        if ((st = ec_expr_source(dt, n_streams, n_scalars, steps, n_steps, nullptr, nullptr, 0, &len)) != EC_OK) return st;
-    }
+    if ((st = check_program(dt, n_streams, n_scalars, steps, n_steps)) != EC_OK) return st;
+    StreamCols c;  // operand and mask columns only
     for (int k = 0; k < n_streams; ++k) {
         if (!p[k] || (masks_or_null && !masks_or_null[k])) return set_error(EC_ERR_ARG, "ec_sharded_expr_min_max: stream %d has no pointer array", k);
-        if ((st = check_shard_ptrs(g, "ec_sharded_expr_min_max", "p[k]", p[k], n)) != EC_OK) return st;
-        if (masks_or_null && (st = check_shard_ptrs(g, "ec_sharded_expr_min_max", "masks[k]", reinterpret_cast<const void* const*>(masks_or_null[k]), n)) != EC_OK) return st;
+        c.p[k] = take(g, "ec_sharded_expr_min_max", "p[k]", p[k], n, &st);
+        if (masks_or_null) c.m[k] = take(g, "ec_sharded_expr_min_max", "masks[k]", masks_or_null[k], n, &st);
+        if (st != EC_OK) return st;
     }
     std::lock_guard<std::mutex> lk(g->call_mu);
-    st = for_each_shard(g, [&](int i) {
-        const void* pi[4] = {nullptr, nullptr, nullptr, nullptr};
-        const uint8_t* mi[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (int k = 0; k < n_streams; ++k) {
-            pi[k] = p[k][i];
-            if (masks_or_null) mi[k] = masks_or_null[k][i];
-        }
+    int64_t keys[2];
+    st = reduce_phased(g, [&](int i) {
+        const void* pi[4];
+        const uint8_t* mi[4];
+        c.gather(i, pi, mi);
         return ec_expr_min_max_keys(dt, pi, masks_or_null ? mi : nullptr, n_streams, scalars, n_scalars, steps, n_steps, n[i], g->payload_dev[i], g->streams[i]);
-    });
-    const std::string keep = last_error_text();
-    const ec_status deferred = take_deferred(g);
-    if (deferred != EC_OK) return deferred;
-    if (st != EC_OK) return set_error_text(st, keep);
-    st = exchange(g, true);
-    if (st != EC_OK) return st;
-    int64_t keys[2] = {g->payload_host[0][0], g->payload_host[0][1]};
-    if (g->comms.empty())
-        for (int i = 1; i < g->n; ++i) {
-            if (g->payload_host[i][0] > keys[0]) keys[0] = g->payload_host[i][0];
-            if (g->payload_host[i][1] > keys[1]) keys[1] = g->payload_host[i][1];
-        }
-    return ec_min_max_decode(EC_F64, keys, mn, mx);
+    }, Combine::keys, keys);
+    return st == EC_OK ? ec_min_max_decode(EC_F64, keys, mn, mx) : st;
 }
 
 extern "C" ec_status ec_sharded_counts(ec_shard_group* g, const uint8_t* const* masks, const size_t* n, uint64_t* n_true,
@@ -749,24 +687,14 @@ extern "C" ec_status ec_sharded_counts(ec_shard_group* g, const uint8_t* const* 
     ec_status st = check_group(g, "ec_sharded_counts");
     if (st != EC_OK) return st;
     if (!masks || !n || !n_true || !n_false) return set_error(EC_ERR_ARG, "ec_sharded_counts: null argument");
-    if ((st = check_shard_ptrs(g, "ec_sharded_counts", "masks", reinterpret_cast<const void* const*>(masks), n)) != EC_OK) return st;
+    if ((st = check_col(g, "ec_sharded_counts", "masks", masks, n)) != EC_OK) return st;
     std::lock_guard<std::mutex> lk(g->call_mu);
-    st = for_each_shard(g, [&](int i) {
+    int64_t sums[2];
+    st = reduce_phased(g, [&](int i) {
         return ec_mask_counts_device(masks[i], n[i], reinterpret_cast<uint64_t*>(g->payload_dev[i]), g->streams[i]);
-    });
-    const std::string keep = last_error_text();
-    const ec_status deferred = take_deferred(g);
-    if (deferred != EC_OK) return deferred;
-    if (st != EC_OK) return set_error_text(st, keep);
-    st = exchange(g, false);
+    }, Combine::counts, sums);
     if (st != EC_OK) return st;
-    uint64_t a = static_cast<uint64_t>(g->payload_host[0][0]), b = static_cast<uint64_t>(g->payload_host[0][1]);
-    if (g->comms.empty())
-        for (int i = 1; i < g->n; ++i) {
-            a += static_cast<uint64_t>(g->payload_host[i][0]);
-            b += static_cast<uint64_t>(g->payload_host[i][1]);
-        }
-    *n_true = a;
-    *n_false = b;
+    *n_true = static_cast<uint64_t>(sums[0]);
+    *n_false = static_cast<uint64_t>(sums[1]);
     return EC_OK;
 }
