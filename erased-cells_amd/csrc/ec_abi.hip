@@ -39,6 +39,19 @@ static ec_status fetch_result(const Scratch& sc, int words, hipStream_t s) {
     // call against 15.1 µs — hipStreamSynchronize's own wait is the faster one; profiles/r04/sync_result_latency.txt.)
     return check_hip(hipStreamSynchronize(s), "hipStreamSynchronize");
 }
+// The synchronous-result prologue of ec_min_max, ec_first_difference and ec_mask_counts: takes the stream's turn at its result
+// words, has `run(sc, words)` queue the kernels whose last one writes `nwords` words there, waits, and leaves them in `host`.
+template <typename Run>
+static ec_status sync_result(hipStream_t s, int nwords, int64_t (&host)[2], Run run) {
+    Scratch sc;
+    ec_status st = get_scratch(s, &sc);
+    if (st != EC_OK) return st;
+    std::lock_guard<std::mutex> turn(*sc.mu);  // the pinned result words are per stream: host threads sharing it take turns
+    st = run(sc, result_words(sc));            // the last kernel writes the pinned words
+    if (st == EC_OK) st = fetch_result(sc, nwords, s);
+    if (st == EC_OK) std::memcpy(host, sc.host, nwords * sizeof(int64_t));
+    return st;
+}
 
 // Workgroups of `kernel` (BLOCK threads, no dynamic LDS) that fit on one CU at a time, at most `want`.
 template <typename K>
@@ -51,13 +64,16 @@ static int resident_per_cu(K kernel, int block, int want) {
     return nb < want ? nb : want;
 }
 
-// Workgroups a reduction launches at most: `per_cu` per CU (the launch shape's own default: as many as are resident
-// at once, so the grid runs as one round) unless "reduce_bpc" overrides it; never more than the finalize kernels read.
-static int reduce_cap(int per_cu) {
-    const int knob = tuning().reduce_bpc;
-    const long cap = long(device_cus()) * (knob > 0 ? knob : per_cu);
-    return static_cast<int>(cap < kMaxReduceBlocks ? cap : kMaxReduceBlocks);
+// reduce_plan (ec_reduce_plan.hpp) of a launch on this thread's device under the current knobs.  `p0`: stream 0's first cell;
+// `residue1`: see reduce_plan; `stream_bytes`: what cache_plan() decides the load policy from.
+static unsigned residue(const void* p, size_t mod) { return static_cast<unsigned>(reinterpret_cast<uintptr_t>(p) % mod); }
+static ReducePlan plan_reduction(const void* p0, unsigned residue1, size_t cell_size, size_t n, const ReduceShape& shape,
+                                 const size_t* stream_bytes, int nstreams) {
+    return reduce_plan(residue(p0, 16), residue1, cell_size, n, shape, device_cus(), tuning().reduce_bpc, tuning().unaligned_vector != 0,
+                       cache_plan(stream_bytes, nstreams));
 }
+// first difference and mask counts: the default shape, its cell-wise branch inside the same kernel
+constexpr ReduceShape kScanShape = {kRBlock, kReduceU, 4, kRBlock, 4};
 
 static inline hipStream_t S(ec_stream s) { return static_cast<hipStream_t>(s); }
 
@@ -134,45 +150,39 @@ static ec_status launch_min_max(const void* p, const uint8_t* mask, size_t n, in
     const T* tp = static_cast<const T*>(p);
     unsigned grid = 0;
     if (n > 0) {
-        const bool al = aligned16(p, p, p) && (!mask || aligned_to(mask, 16 / sizeof(T)));
-        const int cap = reduce_cap(8);  // the cell-wise kernel: 256-thread workgroups
-        if (al) {
-            const unsigned head = reduce_head(p, sizeof(T), n);
-            const size_t groups = (n - head) / (16 / sizeof(T));
-            // launch shape: 512 threads x 8 loads in flight by default; "reduce_shape" selects the A/B alternatives
-            auto launch = [&](auto u_tag, auto block_tag, int per_cu) {
-                constexpr int U = decltype(u_tag)::value, BLOCK = decltype(block_tag)::value;
-                // as many workgroups per CU as are resident at once (the masked kernels of some types need more than
-                // 64 VGPRs and fit 3, not 4, of these workgroups on a CU): the grid then runs as ONE round
-                static const int resident[2] = {resident_per_cu(k_min_max_partials<T, false, U, BLOCK>, BLOCK, per_cu),
-                                                resident_per_cu(k_min_max_partials<T, true, U, BLOCK>, BLOCK, per_cu)};
-                const int cap2 = reduce_cap(resident[mask ? 1 : 0]);
-                size_t tiles = (groups + size_t(BLOCK) * U - 1) / (size_t(BLOCK) * U);
-                if (tiles < 1) tiles = 1;
-                grid = static_cast<unsigned>(tiles < size_t(cap2) ? tiles : size_t(cap2));
-                int64_t* direct = grid == 1 ? keys2_dev : nullptr;  // one workgroup: it writes the result itself
-                const size_t stream_bytes[2] = {n * sizeof(T), mask ? n : 0};
-                const unsigned hp = head | (cache_plan(stream_bytes, 2) << 8);  // leading cells + load policy
-                if (mask) k_min_max_partials<T, true, U, BLOCK><<<grid, BLOCK, 0, s>>>(tp, mask, n, sc.dev, hp, direct);
-                else k_min_max_partials<T, false, U, BLOCK><<<grid, BLOCK, 0, s>>>(tp, nullptr, n, sc.dev, hp, direct);
-                return direct != nullptr;
-            };
-            using std::integral_constant;
-            bool direct = false;
-            switch (tuning().reduce_shape) {
-                case 1: direct = launch(integral_constant<int, 16>{}, integral_constant<int, 512>{}, 4); break;
-                case 2: direct = launch(integral_constant<int, 8>{}, integral_constant<int, 256>{}, 8); break;
-                case 3: direct = launch(integral_constant<int, 8>{}, integral_constant<int, 1024>{}, 2); break;
-                case 4: direct = launch(integral_constant<int, 4>{}, integral_constant<int, 512>{}, 4); break;
-                default: direct = launch(integral_constant<int, kReduceU>{}, integral_constant<int, kRBlock>{}, 4); break;
+        const size_t stream_bytes[2] = {n * sizeof(T), mask ? n : 0};
+        // launch shape: 512 threads x 8 loads in flight by default; "reduce_shape" selects the A/B alternatives
+        auto launch = [&](auto u_tag, auto block_tag, int per_cu) {
+            constexpr int U = decltype(u_tag)::value, BLOCK = decltype(block_tag)::value;
+            // as many workgroups per CU as are resident at once (the masked kernels of some types need more than
+            // 64 VGPRs and fit 3, not 4, of these workgroups on a CU): the grid then runs as ONE round.  (Probed once per type and
+            // shape, also when the plan then picks the cell-wise kernel — "unaligned_vector" off — which has no use for the answer.)
+            static const int resident[2] = {resident_per_cu(k_min_max_partials<T, false, U, BLOCK>, BLOCK, per_cu),
+                                            resident_per_cu(k_min_max_partials<T, true, U, BLOCK>, BLOCK, per_cu)};
+            const ReduceShape shape = {BLOCK, U, resident[mask ? 1 : 0], kBlock, 8};  // the cell-wise kernel: 256-thread workgroups
+            const ReducePlan pl = plan_reduction(p, mask ? residue(mask, 16 / sizeof(T)) : 0u, sizeof(T), n, shape, stream_bytes, 2);
+            grid = pl.grid;
+            int64_t* direct = pl.aligned && pl.single ? keys2_dev : nullptr;  // one workgroup: it writes the result itself
+            if (!pl.aligned) {
+                if (mask) k_min_max_partials_cellwise<T, true><<<grid, kBlock, 0, s>>>(tp, mask, n, sc.dev);
+                else k_min_max_partials_cellwise<T, false><<<grid, kBlock, 0, s>>>(tp, nullptr, n, sc.dev);
+            } else if (mask) {
+                k_min_max_partials<T, true, U, BLOCK><<<grid, BLOCK, 0, s>>>(tp, mask, n, sc.dev, pl.head_policy, direct);
+            } else {
+                k_min_max_partials<T, false, U, BLOCK><<<grid, BLOCK, 0, s>>>(tp, nullptr, n, sc.dev, pl.head_policy, direct);
             }
-            if (direct) return check_launch("min_max(single workgroup)");
-        } else {
-            size_t blocks = (n + kBlock - 1) / kBlock;
-            grid = static_cast<unsigned>(blocks < size_t(cap) ? blocks : size_t(cap));
-            if (mask) k_min_max_partials_cellwise<T, true><<<grid, kBlock, 0, s>>>(tp, mask, n, sc.dev);
-            else k_min_max_partials_cellwise<T, false><<<grid, kBlock, 0, s>>>(tp, nullptr, n, sc.dev);
+            return direct != nullptr;
+        };
+        using std::integral_constant;
+        bool direct = false;
+        switch (tuning().reduce_shape) {
+            case 1: direct = launch(integral_constant<int, 16>{}, integral_constant<int, 512>{}, 4); break;
+            case 2: direct = launch(integral_constant<int, 8>{}, integral_constant<int, 256>{}, 8); break;
+            case 3: direct = launch(integral_constant<int, 8>{}, integral_constant<int, 1024>{}, 2); break;
+            case 4: direct = launch(integral_constant<int, 4>{}, integral_constant<int, 512>{}, 4); break;
+            default: direct = launch(integral_constant<int, kReduceU>{}, integral_constant<int, kRBlock>{}, 4); break;
         }
+        if (direct) return check_launch("min_max(single workgroup)");
         st = check_launch("min_max(partials)");
         if (st != EC_OK) return st;
     }
@@ -412,30 +422,22 @@ extern "C" ec_status ec_min_max(ec_dtype t, const void* p, const uint8_t* mask_o
                                 ec_stream stream) {
     EC_REQUIRE_INIT();
     if (!mn || !mx || (n > 0 && !p)) return set_error(EC_ERR_ARG, "ec_min_max: null pointer");
-    Scratch sc;
-    ec_status st = get_scratch(S(stream), &sc);
+    int64_t keys2[2];
+    ec_status st = sync_result(S(stream), 2, keys2, [&](const Scratch&, int64_t* words) {
+        return dispatch_min_max(t, p, mask_or_null, n, words, S(stream));
+    });
     if (st != EC_OK) return st;
-    std::lock_guard<std::mutex> turn(*sc.mu);  // the pinned result words are per stream: host threads sharing it take turns
-    st = dispatch_min_max(t, p, mask_or_null, n, result_words(sc), S(stream));  // the last kernel writes the pinned words
-    if (st != EC_OK) return st;
-    st = fetch_result(sc, 2, S(stream));
-    if (st != EC_OK) return st;
-    return ec_min_max_decode(t, sc.host, mn, mx);
+    return ec_min_max_decode(t, keys2, mn, mx);
 }
 
 // =================================================================== Ord / Eq
 template <typename W>
 static ec_status first_diff_w(const void* l, const void* r, size_t n, const Scratch& sc, hipStream_t s, unsigned* grid_out) {
-    const int cap = reduce_cap(4);
-    const bool al = aligned16(l, r, r);
-    const unsigned head = al ? reduce_head(l, sizeof(W), n) : 0u;
-    size_t tiles = al ? ((n - head) / (16 / sizeof(W)) + size_t(kRBlock) * kReduceU - 1) / (size_t(kRBlock) * kReduceU) : (n + kRBlock - 1) / kRBlock;
-    if (tiles < 1) tiles = 1;
-    const unsigned grid = static_cast<unsigned>(tiles < size_t(cap) ? tiles : size_t(cap));
     const size_t stream_bytes[2] = {n * sizeof(W), n * sizeof(W)};
-    k_first_diff_partials<W, kReduceU><<<grid, kRBlock, 0, s>>>(static_cast<const W*>(l), static_cast<const W*>(r), n,
-                                                               reinterpret_cast<uint64_t*>(sc.dev), al, head | (cache_plan(stream_bytes, 2) << 8));
-    *grid_out = grid;
+    const ReducePlan pl = plan_reduction(l, residue(r, 16), sizeof(W), n, kScanShape, stream_bytes, 2);
+    k_first_diff_partials<W, kReduceU><<<pl.grid, kRBlock, 0, s>>>(static_cast<const W*>(l), static_cast<const W*>(r), n,
+                                                                  reinterpret_cast<uint64_t*>(sc.dev), pl.aligned, pl.head_policy);
+    *grid_out = pl.grid;
     return check_launch("first_diff(partials)");
 }
 
@@ -445,25 +447,23 @@ extern "C" ec_status ec_first_difference(ec_dtype t, const void* l, const void* 
     if (!index || (n > 0 && (!l || !r))) return set_error(EC_ERR_ARG, "ec_first_difference: null pointer");
     *index = n;
     if (n == 0) return EC_OK;
-    Scratch sc;
-    ec_status st = get_scratch(S(stream), &sc);
+    int64_t word[2];
+    ec_status st = sync_result(S(stream), 1, word, [&](const Scratch& sc, int64_t* words) {
+        unsigned grid = 0;
+        ec_status st2;
+        switch (ecl::size_of(t)) {
+            case 1: st2 = first_diff_w<uint8_t>(l, r, n, sc, S(stream), &grid); break;
+            case 2: st2 = first_diff_w<uint16_t>(l, r, n, sc, S(stream), &grid); break;
+            case 4: st2 = first_diff_w<uint32_t>(l, r, n, sc, S(stream), &grid); break;
+            default: st2 = first_diff_w<uint64_t>(l, r, n, sc, S(stream), &grid); break;
+        }
+        if (st2 != EC_OK) return st2;
+        k_first_diff_finalize<<<1, kFinalizeBlock, 0, S(stream)>>>(reinterpret_cast<const uint64_t*>(sc.dev), static_cast<int>(grid),
+                                                           reinterpret_cast<uint64_t*>(words));
+        return check_launch("first_diff(finalize)");
+    });
     if (st != EC_OK) return st;
-    std::lock_guard<std::mutex> turn(*sc.mu);
-    unsigned grid = 0;
-    switch (ecl::size_of(t)) {
-        case 1: st = first_diff_w<uint8_t>(l, r, n, sc, S(stream), &grid); break;
-        case 2: st = first_diff_w<uint16_t>(l, r, n, sc, S(stream), &grid); break;
-        case 4: st = first_diff_w<uint32_t>(l, r, n, sc, S(stream), &grid); break;
-        default: st = first_diff_w<uint64_t>(l, r, n, sc, S(stream), &grid); break;
-    }
-    if (st != EC_OK) return st;
-    k_first_diff_finalize<<<1, kFinalizeBlock, 0, S(stream)>>>(reinterpret_cast<const uint64_t*>(sc.dev), static_cast<int>(grid),
-                                                       reinterpret_cast<uint64_t*>(result_words(sc)));
-    st = check_launch("first_diff(finalize)");
-    if (st != EC_OK) return st;
-    st = fetch_result(sc, 1, S(stream));
-    if (st != EC_OK) return st;
-    const uint64_t first = static_cast<uint64_t>(sc.host[0]);
+    const uint64_t first = static_cast<uint64_t>(word[0]);
     *index = first == ~0ull ? n : first;
     return EC_OK;
 }
@@ -581,13 +581,10 @@ extern "C" ec_status ec_mask_counts_device(const uint8_t* m, size_t n, uint64_t*
     if (st != EC_OK) return st;
     unsigned grid = 0;
     if (n > 0) {
-        const int cap = reduce_cap(4);
-        const bool al = aligned_to(m, 16);
-        const unsigned head = al ? reduce_head(m, 1, n) : 0u;
-        size_t tiles = al ? ((n - head) / 16 + size_t(kRBlock) * kReduceU - 1) / (size_t(kRBlock) * kReduceU) : (n + kRBlock - 1) / kRBlock;
-        if (tiles < 1) tiles = 1;
-        grid = static_cast<unsigned>(tiles < size_t(cap) ? tiles : size_t(cap));
-        uint64_t* direct = grid == 1 ? counts2_dev : nullptr;  // one workgroup: it writes the result itself
+        const size_t stream_bytes[1] = {n};
+        const ReducePlan pl = plan_reduction(m, 0u, 1, n, kScanShape, stream_bytes, 1);
+        grid = pl.grid;
+        uint64_t* direct = pl.single ? counts2_dev : nullptr;  // one workgroup: it writes the result itself
         // more workgroups: the last one to add its count to the stream's accumulator word writes the result (one launch) — for masks below
         // 2^29 cells.  Measured, rotating masks, every byte from HBM (profiles/r04/mask_counts_one_launch.md): 4096² 9.5 -> 7.5 µs, 16384²
         // 49.5 -> 47.7 µs, but 32768² 158.4 -> 166.7 µs: the 1,024 returning atomics on one address queue behind the channel's reads when
@@ -595,9 +592,8 @@ extern "C" ec_status ec_mask_counts_device(const uint8_t* m, size_t n, uint64_t*
         // `counts_one_launch`: 0 never, 1 (default) below 2^29 cells, 2 always (below 2^40: ticket and sum share a 64-bit word).
         const int one = tuning().counts_one_launch.load();
         uint64_t* acc = (!direct && ((one == 1 && n < (size_t(1) << 29)) || (one >= 2 && n < (size_t(1) << 40)))) ? reinterpret_cast<uint64_t*>(sc.dev_acc()) : nullptr;
-        const size_t stream_bytes[1] = {n};
-        k_mask_count_partials<kReduceU><<<grid, kRBlock, 0, S(stream)>>>(m, n, reinterpret_cast<uint64_t*>(sc.dev), al,
-                                                                        head | (cache_plan(stream_bytes, 1) << 8), direct, acc, counts2_dev);
+        k_mask_count_partials<kReduceU><<<grid, kRBlock, 0, S(stream)>>>(m, n, reinterpret_cast<uint64_t*>(sc.dev), pl.aligned, pl.head_policy,
+                                                                        direct, acc, counts2_dev);
         st = check_launch("mask_counts(partials)");
         if (st != EC_OK || direct || acc) return st;
     }
@@ -608,16 +604,13 @@ extern "C" ec_status ec_mask_counts_device(const uint8_t* m, size_t n, uint64_t*
 extern "C" ec_status ec_mask_counts(const uint8_t* m, size_t n, uint64_t* n_true, uint64_t* n_false, ec_stream stream) {
     EC_REQUIRE_INIT();
     if (!n_true || !n_false) return set_error(EC_ERR_ARG, "ec_mask_counts: null pointer");
-    Scratch sc;
-    ec_status st = get_scratch(S(stream), &sc);
+    int64_t counts2[2];
+    ec_status st = sync_result(S(stream), 2, counts2, [&](const Scratch&, int64_t* words) {
+        return ec_mask_counts_device(m, n, reinterpret_cast<uint64_t*>(words), stream);
+    });
     if (st != EC_OK) return st;
-    std::lock_guard<std::mutex> turn(*sc.mu);
-    st = ec_mask_counts_device(m, n, reinterpret_cast<uint64_t*>(result_words(sc)), stream);
-    if (st != EC_OK) return st;
-    st = fetch_result(sc, 2, S(stream));
-    if (st != EC_OK) return st;
-    *n_true = static_cast<uint64_t>(sc.host[0]);
-    *n_false = static_cast<uint64_t>(sc.host[1]);
+    *n_true = static_cast<uint64_t>(counts2[0]);
+    *n_false = static_cast<uint64_t>(counts2[1]);
     return EC_OK;
 }
 

@@ -1,18 +1,23 @@
-// ec_reduce_kernels.hpp — min/max and mask counts (gfx950).
+// ec_reduce_kernels.hpp — min/max, first difference and mask counts (gfx950).
 //
 //   min_max  BufferOps::min_max, src/buffer.rs:169-173 (masked:
 //            src/masked/masked_buffer.rs:208-217), order src/value.rs:248-265,
 //            sentinels (T::MAX, T::MIN) src/ctype.rs:158-179 — finite for floats.
 //   counts   Mask::counts, src/masked/mask.rs:72-80.
+//   first difference  impl Ord / PartialEq for CellBuffer, src/buffer.rs:373-436.
 //
-// Plan: read-only stream at 16 B per lane, U loads in flight per lane; each lane
-// folds into register accumulators (packed 16-bit min/max for u16/i16), then a
-// wavefront shuffle-reduce (DPP/ds_bpermute via __shfl_xor, 6 steps), then the
-// four waves of the block combine through 64 B of LDS and lane 0 writes the
-// block's partial.  A one-block finalize kernel folds the partials (≤ 8 per CU)
-// and writes the two order-preserving int64 keys {~key(min), key(max)} — the
-// form a MAX all-reduce over shards needs.  No atomics, so the result is
-// deterministic and needs no zero-initialised memory.
+// Plan: read-only stream at 16 B per lane, U loads in flight per lane; each lane folds into register accumulators
+// (packed 16-bit min/max for u16/i16).  Each of the three partials kernels keeps its own scan (head | policy word, peeled
+// head cells, grid-stride tile loop, tail cells): one shared scan frame was tried and cost two min/max kernels a
+// waves-per-SIMD step (profiles/r08/reduce_frame.md).  What they share, written once below:
+//   block_fold    a wavefront shuffle-reduce (DPP/ds_bpermute via __shfl_xor, 6 steps), then the waves of the block
+//                 combine through one LDS word (or {min, max} pair) per wave behind ONE barrier; thread 0 holds the result
+//                 and writes the block's partial.
+//   finalize_fold the one-block finalize kernels: fold the partials (≤ 8 per CU) and write the result words — for
+//                 min/max the two order-preserving int64 keys {~key(min), key(max)}, the form a MAX all-reduce over
+//                 shards needs.
+// No atomics in min/max and first difference, so the result is deterministic and needs no zero-initialised memory (the
+// one-launch form of the counts adds integers: order-free).  What the host decides per launch: ec_reduce_plan.hpp.
 #pragma once
 
 #include <type_traits>
@@ -54,21 +59,38 @@ __device__ __forceinline__ int64_t acc_to_i64(A a) {
     else return static_cast<int64_t>(a);
 }
 
-__device__ __forceinline__ int64_t wave_min_i64(int64_t v) {
+// ---- fold primitives.  A fold operator combines two values of one type; FoldMinMax carries {min, max} as one pair so
+// that both travel through block_fold behind the same barrier.
+using K2 = vec<int64_t, 2>;  // {min key, max key}
+struct FoldMin { template <typename V> __device__ __forceinline__ V operator()(V a, V b) const { return b < a ? b : a; } };
+struct FoldSum { template <typename V> __device__ __forceinline__ V operator()(V a, V b) const { return a + b; } };
+struct FoldMinMax {
+    __device__ __forceinline__ K2 operator()(K2 a, K2 b) const { return K2{b.x < a.x ? b.x : a.x, b.y > a.y ? b.y : a.y}; }
+};
+
+template <typename V>
+__device__ __forceinline__ V lane_xor(V v, int off) {
+    if constexpr (std::is_same<V, K2>::value) return K2{__shfl_xor(v.x, off, 64), __shfl_xor(v.y, off, 64)};
+    else return __shfl_xor(v, off, 64);
+}
+template <typename V, typename Op>
+__device__ __forceinline__ V wave_fold(V v, Op op) {
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        int64_t o = __shfl_xor(v, off, 64);
-        v = o < v ? o : v;
-    }
+    for (int off = 32; off >= 1; off >>= 1) v = op(v, lane_xor(v, off));
     return v;
 }
-__device__ __forceinline__ int64_t wave_max_i64(int64_t v) {
+// Folds v over the workgroup: true in thread 0, whose v is then the block's result (every other thread's v is scrap).
+template <int BLOCK, typename V, typename Op>
+__device__ __forceinline__ bool block_fold(V& v, Op op) {
+    constexpr int WAVES = BLOCK / kWave;
+    __shared__ V s_wave[WAVES];
+    v = wave_fold(v, op);
+    if ((threadIdx.x & (kWave - 1)) == 0) s_wave[threadIdx.x / kWave] = v;
+    __syncthreads();
+    if (threadIdx.x != 0) return false;
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        int64_t o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
+    for (int w = 1; w < WAVES; ++w) v = op(v, s_wave[w]);
+    return true;
 }
 
 // ---- 1-byte cells: gfx950 has no packed 8-bit min/max, so the four cells of a dword are folded as two packed
@@ -132,7 +154,6 @@ struct ByteFold {
 // the finalize launch (0.81 of 8 TB/s); round 1's 256 threads x 4 loads x 8/CU took 43.3 µs, one tile per workgroup
 // 42.4, and single-launch forms (write-through partials + relaxed ticket, the last workgroup folds) 41.6 at best.
 constexpr int kRBlock = 512;
-constexpr int kRWaves = kRBlock / kWave;
 
 // partials[2*b] = min key, partials[2*b+1] = max key of block b (int64 order keys).
 template <typename T, bool MASKED, int U, int BLOCK = kRBlock>
@@ -234,24 +255,14 @@ __global__ __launch_bounds__(BLOCK) void k_min_max_partials(const T* __restrict_
         for (size_t i = ngroups * CPL + threadIdx.x; i < n; i += BLOCK) fold_cell(static_cast<ptrdiff_t>(i));
         for (unsigned h = threadIdx.x; h < head; h += BLOCK) fold_cell(-static_cast<ptrdiff_t>(h) - 1);  // the peeled cells
     }
-    int64_t kmin = wave_min_i64(acc_to_i64<A>(amin));
-    int64_t kmax = wave_max_i64(acc_to_i64<A>(amax));
-    __shared__ int64_t s_min[(BLOCK / kWave)], s_max[(BLOCK / kWave)];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) { s_min[wave] = kmin; s_max[wave] = kmax; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < (BLOCK / kWave); ++w) {
-            kmin = s_min[w] < kmin ? s_min[w] : kmin;
-            kmax = s_max[w] > kmax ? s_max[w] : kmax;
-        }
+    K2 k = {acc_to_i64<A>(amin), acc_to_i64<A>(amax)};
+    if (block_fold<BLOCK>(k, FoldMinMax{})) {
         if (keys2_if_single) {
-            keys2_if_single[0] = ~kmin;
-            keys2_if_single[1] = kmax;
+            keys2_if_single[0] = ~k.x;
+            keys2_if_single[1] = k.y;
         } else {
-            partials[2 * size_t(blockIdx.x)] = kmin;
-            partials[2 * size_t(blockIdx.x) + 1] = kmax;
+            partials[2 * size_t(blockIdx.x)] = k.x;
+            partials[2 * size_t(blockIdx.x) + 1] = k.y;
         }
     }
 }
@@ -269,19 +280,10 @@ __global__ __launch_bounds__(kBlock) void k_min_max_partials_cellwise(const T* _
         amin = key < amin ? key : amin;
         amax = key > amax ? key : amax;
     }
-    int64_t kmin = wave_min_i64(acc_to_i64<A>(amin));
-    int64_t kmax = wave_max_i64(acc_to_i64<A>(amax));
-    __shared__ int64_t s_min[kWavesPerBlock], s_max[kWavesPerBlock];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) { s_min[wave] = kmin; s_max[wave] = kmax; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kWavesPerBlock; ++w) {
-            kmin = s_min[w] < kmin ? s_min[w] : kmin;
-            kmax = s_max[w] > kmax ? s_max[w] : kmax;
-        }
-        partials[2 * size_t(blockIdx.x)] = kmin;
-        partials[2 * size_t(blockIdx.x) + 1] = kmax;
+    K2 k = {acc_to_i64<A>(amin), acc_to_i64<A>(amax)};
+    if (block_fold<kBlock>(k, FoldMinMax{})) {
+        partials[2 * size_t(blockIdx.x)] = k.x;
+        partials[2 * size_t(blockIdx.x) + 1] = k.y;
     }
 }
 
@@ -289,57 +291,36 @@ __global__ __launch_bounds__(kBlock) void k_min_max_partials_cellwise(const T* _
 // issues all its loads up front (≤ 4, independent), so the launch costs one memory latency instead of a chain
 // of them — a 256-thread loop took 4.7 µs, a tenth of a 1 B/cell pass over 16384² cells.
 constexpr int kFinalizeBlock = 1024;
-constexpr int kFinalizeWaves = kFinalizeBlock / kWave;
 constexpr int kFinalizeMaxParts = 4096;
 constexpr int kFinalizePer = kFinalizeMaxParts / kFinalizeBlock;
+
+// The body of a finalize kernel.  Its fold is described by the partials' type V (one word, or the K2 pair as one 16-byte
+// load), the fold's identity (what a slot beyond nparts holds), the operator, and `write`, which thread 0 calls with the result.
+template <typename V, typename Op, typename Write>
+__device__ __forceinline__ void finalize_fold(const V* __restrict__ partials, int nparts, V identity, Op op, Write write) {
+    V v[kFinalizePer];
+#pragma unroll
+    for (int j = 0; j < kFinalizePer; ++j) {  // every load of the block is in flight before the first combine
+        const int i = threadIdx.x + j * kFinalizeBlock;
+        v[j] = i < nparts ? partials[i] : identity;
+    }
+    V acc = identity;
+#pragma unroll
+    for (int j = 0; j < kFinalizePer; ++j) acc = op(acc, v[j]);
+    if (block_fold<kFinalizeBlock>(acc, op)) write(acc);
+}
 
 // keys2 = {~min, max}: a MAX reduction over shards of both words is the global answer.
 __global__ __launch_bounds__(kFinalizeBlock) void k_min_max_finalize(const int64_t* __restrict__ partials, int nparts,
                                                                       int64_t sentinel_min, int64_t sentinel_max,
                                                                       int64_t* __restrict__ keys2) {
-    using K2 = vec<int64_t, 2>;
-    const K2* __restrict__ pp = reinterpret_cast<const K2*>(partials);
-    K2 v[kFinalizePer];
-#pragma unroll
-    for (int j = 0; j < kFinalizePer; ++j) {  // every load of the block is in flight before the first compare
-        const int i = threadIdx.x + j * kFinalizeBlock;
-        v[j] = i < nparts ? pp[i] : K2{sentinel_min, sentinel_max};
-    }
-    int64_t kmin = sentinel_min, kmax = sentinel_max;
-#pragma unroll
-    for (int j = 0; j < kFinalizePer; ++j) {
-        kmin = v[j].x < kmin ? v[j].x : kmin;
-        kmax = v[j].y > kmax ? v[j].y : kmax;
-    }
-    kmin = wave_min_i64(kmin);
-    kmax = wave_max_i64(kmax);
-    __shared__ int64_t s_min[kFinalizeWaves], s_max[kFinalizeWaves];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) { s_min[wave] = kmin; s_max[wave] = kmax; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < kFinalizeWaves; ++w) {
-            kmin = s_min[w] < kmin ? s_min[w] : kmin;
-            kmax = s_max[w] > kmax ? s_max[w] : kmax;
-        }
-        keys2[0] = ~kmin;
-        keys2[1] = kmax;
-    }
+    finalize_fold(reinterpret_cast<const K2*>(partials), nparts, K2{sentinel_min, sentinel_max}, FoldMinMax{},
+                  [=](K2 k) { keys2[0] = ~k.x; keys2[1] = k.y; });
 }
 
 // ---- first differing cell of two buffers (impl Ord / PartialEq for CellBuffer, src/buffer.rs:373-436).
 // Equality under the reference's total order is bit equality for every cell type, so the scan works
 // on raw cell words of width W; the ordering of the first differing pair is decided by the caller.
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        uint64_t o = __shfl_xor(v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
 template <typename W, int U>
 __global__ __launch_bounds__(kRBlock) void k_first_diff_partials(const W* __restrict__ l, const W* __restrict__ r, size_t n,
                                                                 uint64_t* __restrict__ partials, bool aligned,
@@ -408,47 +389,15 @@ __global__ __launch_bounds__(kRBlock) void k_first_diff_partials(const W* __rest
         for (size_t i = size_t(blockIdx.x) * kRBlock + threadIdx.x; i < n && first == ~0ull; i += stride)
             if (ld_cell(l + i) != ld_cell(r + i)) first = i;
     }
-    first = wave_min_u64(first);
-    __shared__ uint64_t s_first[kRWaves];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) s_first[wave] = first;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kRWaves; ++w) first = s_first[w] < first ? s_first[w] : first;
-        partials[blockIdx.x] = first;
-    }
+    if (block_fold<kRBlock>(first, FoldMin{})) partials[blockIdx.x] = first;
 }
 
 __global__ __launch_bounds__(kFinalizeBlock) void k_first_diff_finalize(const uint64_t* __restrict__ partials, int nparts,
                                                                          uint64_t* __restrict__ result) {
-    uint64_t v[kFinalizePer];
-#pragma unroll
-    for (int j = 0; j < kFinalizePer; ++j) {
-        const int i = threadIdx.x + j * kFinalizeBlock;
-        v[j] = i < nparts ? partials[i] : ~0ull;
-    }
-    uint64_t first = ~0ull;
-#pragma unroll
-    for (int j = 0; j < kFinalizePer; ++j) first = v[j] < first ? v[j] : first;
-    first = wave_min_u64(first);
-    __shared__ uint64_t s_first[kFinalizeWaves];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) s_first[wave] = first;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < kFinalizeWaves; ++w) first = s_first[w] < first ? s_first[w] : first;
-        result[0] = first;
-    }
+    finalize_fold(partials, nparts, ~uint64_t(0), FoldMin{}, [=](uint64_t first) { result[0] = first; });
 }
 
 // ---- Mask::counts: bytes are 0/1, so the count of true cells is the byte sum.
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 template <int U>
 __global__ __launch_bounds__(kRBlock) void k_mask_count_partials(const uint8_t* __restrict__ m, size_t n,
                                                                 uint64_t* __restrict__ partials, bool aligned, unsigned head,
@@ -498,13 +447,7 @@ __global__ __launch_bounds__(kRBlock) void k_mask_count_partials(const uint8_t* 
         const size_t stride = size_t(gridDim.x) * kRBlock;
         for (size_t i = size_t(blockIdx.x) * kRBlock + threadIdx.x; i < n; i += stride) cnt += ld_cell(m + i) & 1;
     }
-    cnt = wave_sum_u64(cnt);
-    __shared__ uint64_t s_cnt[kRWaves];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) s_cnt[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kRWaves; ++w) cnt += s_cnt[w];
+    if (block_fold<kRBlock>(cnt, FoldSum{})) {
         if (counts2_if_single) {  // one-workgroup grid: this IS the result (see k_min_max_partials)
             counts2_if_single[0] = cnt;
             counts2_if_single[1] = n_total - cnt;
@@ -528,26 +471,7 @@ __global__ __launch_bounds__(kRBlock) void k_mask_count_partials(const uint8_t* 
 
 __global__ __launch_bounds__(kFinalizeBlock) void k_mask_count_finalize(const uint64_t* __restrict__ partials, int nparts,
                                                                          uint64_t n, uint64_t* __restrict__ counts2) {
-    uint64_t v[kFinalizePer];
-#pragma unroll
-    for (int j = 0; j < kFinalizePer; ++j) {
-        const int i = threadIdx.x + j * kFinalizeBlock;
-        v[j] = i < nparts ? partials[i] : 0ull;
-    }
-    uint64_t cnt = 0;
-#pragma unroll
-    for (int j = 0; j < kFinalizePer; ++j) cnt += v[j];
-    cnt = wave_sum_u64(cnt);
-    __shared__ uint64_t s_cnt[kFinalizeWaves];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) s_cnt[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < kFinalizeWaves; ++w) cnt += s_cnt[w];
-        counts2[0] = cnt;
-        counts2[1] = n - cnt;
-    }
+    finalize_fold(partials, nparts, uint64_t(0), FoldSum{}, [=](uint64_t cnt) { counts2[0] = cnt; counts2[1] = n - cnt; });
 }
 
 }  // namespace ecd

@@ -11,6 +11,7 @@
 #include <mutex>
 #include <string>
 
+#include "ec_reduce_plan.hpp"  // kReduceU, kMaxReduceBlocks
 #include "erased_cells.h"
 
 namespace ecd {
@@ -18,8 +19,6 @@ namespace ecd {
 // Compile-time launch shape of the binary-arithmetic kernels; chosen from the
 // A/B runs recorded in profiles/ (tools/tune_binop.hip).
 constexpr int kBinopU = 2;         // chunks of 128 cells per wave per tile (U = 2 beats 8 by ≈6 %: tune_binop_v4/v5.log)
-constexpr int kReduceU = 8;   // 16-byte loads in flight per lane of a reduction tile (ec_reduce_kernels.hpp)
-constexpr int kMaxReduceBlocks = 4096;
 
 struct Tuning;
 Tuning& tuning();
@@ -193,13 +192,6 @@ inline ec_status add_mask(const uint8_t* m, int k, const char* what, const uint8
     ms[(*nmask)++] = m;
     *aligned = *aligned && aligned_to(m, 16);
     return EC_OK;
-}
-
-// Leading cells a reduction peels so that its 16-byte loads start 16-byte aligned (0 when the window is shorter).
-inline unsigned reduce_head(const void* p, size_t cell_size, size_t n) {
-    if (!tuning().unaligned_vector) return 0;
-    const size_t h = ((16 - reinterpret_cast<uintptr_t>(p) % 16) % 16) / cell_size;
-    return h <= n ? static_cast<unsigned>(h) : 0u;
 }
 
 // Element-wise kernels: one workgroup per tile.

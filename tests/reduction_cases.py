@@ -24,14 +24,15 @@ from oracle.eco import NP_DTYPES
 # ---- kernel geometry, restated
 WAVE = 64                    # kWave, ec_binop_kernels.hpp
 SHAPES = {0: (512, 8), 1: (512, 16), 2: (256, 8), 3: (1024, 8), 4: (512, 4)}   # reduce_shape -> (BLOCK, U): ec_abi.hip launch_min_max
-RBLOCK, RU = 512, 8          # k_first_diff_partials / k_mask_count_partials: kRBlock (ec_reduce_kernels.hpp), kReduceU (ec_runtime.hpp)
+RBLOCK, RU = 512, 8          # k_first_diff_partials / k_mask_count_partials: kRBlock (ec_reduce_kernels.hpp), kReduceU (ec_reduce_plan.hpp); kScanShape, ec_abi.hip
 CELLWISE_BLOCK = 256         # k_min_max_partials_cellwise: kBlock (ec_binop_kernels.hpp), at most 8 workgroups per CU (ec_abi.hip launch_min_max)
 CELLWISE_PER_CU = 8
-FINALIZE_BLOCK = 1024        # kFinalizeBlock, ec_reduce_kernels.hpp: four load slots per thread
-MAX_PARTS = 4096             # kMaxReduceBlocks (ec_runtime.hpp) = kFinalizeMaxParts (ec_reduce_kernels.hpp): the grid's hard cap
+FINALIZE_BLOCK = 1024        # kFinalizeBlock, ec_reduce_kernels.hpp (finalize_fold): four load slots per thread
+MAX_PARTS = 4096             # kMaxReduceBlocks (ec_reduce_plan.hpp, reduce_cap) = kFinalizeMaxParts (ec_reduce_kernels.hpp): the grid's hard cap
 JIT_BLOCK, JIT_U, JIT_PER_CU = 256, 4, 8   # generated reduce kernel: 256 threads, 4 PAIRS per lane per tile, grid <= 8 per CU (ec_expr_jit.hip)
 # Nothing pins these to the product but the GPU test: it plants at the cells these constants name and fails if the kernels drift only
-# where a class then misses its place — re-read the three sources when a launch shape changes.  JIT_U is the library's default;
+# where a class then misses its place — re-read the sources when a launch shape changes: the cell geometry is that of the three
+# partials kernels (ec_reduce_kernels.hpp), the grid is reduce_plan's (ec_reduce_plan.hpp), the shapes are the launchers' (ec_abi.hip).  JIT_U is the library's default;
 # the GPU test refuses to run with EC_EXPR_REDUCE_U set to anything else.
 DECOY_STRIDE = 997           # a prime: the hidden cells walk through every slot, lane and in-flight load of any launch shape
 
