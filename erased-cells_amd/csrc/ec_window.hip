@@ -4,24 +4,10 @@
 
 #include "ec_lattice.hpp"
 #include "ec_runtime.hpp"
+#include "ec_window_checks.hpp"
 #include "ec_window_kernels.hpp"
 
 namespace ecd {
-
-static bool mul_overflows(uint64_t a, uint64_t b) { return a != 0 && b > UINT64_MAX / a; }
-
-// the raster, the window in it and the pair of masks, shared by both entry points; *empty: nothing to move
-static ec_status check_window(const char* what, ec_dtype t, uint64_t cols, uint64_t rows, uint64_t x0, uint64_t y0, uint64_t w, uint64_t h,
-                              const void* mask_a, const void* mask_b) {
-    if (!ecl::valid(t)) return set_error(EC_ERR_UNSUPPORTED_TYPE, "%s: bad dtype %d", what, int(t));
-    if (mul_overflows(cols, rows))
-        return set_error(EC_ERR_ARG, "%s: a raster of %llu x %llu cells overflows 64 bits", what, (unsigned long long)cols, (unsigned long long)rows);
-    if (x0 > cols || w > cols - x0 || y0 > rows || h > rows - y0)
-        return set_error(EC_ERR_ARG, "%s: the window (%llu, %llu) + %llu x %llu leaves the raster of %llu x %llu cells", what, (unsigned long long)x0,
-                         (unsigned long long)y0, (unsigned long long)w, (unsigned long long)h, (unsigned long long)cols, (unsigned long long)rows);
-    if ((mask_a == nullptr) != (mask_b == nullptr)) return set_error(EC_ERR_ARG, "%s: one mask without the other", what);
-    return EC_OK;
-}
 
 // Nearest neighbour along one axis (WindowAxis, ec_window_kernels.hpp); false if the kernel's 64-bit numerator could overflow.
 static bool make_axis(uint64_t win, uint64_t out, WindowAxis* a) {
@@ -83,15 +69,9 @@ using namespace ecd;
 extern "C" ec_status ec_window(ec_dtype t, const void* src, const uint8_t* src_mask_or_null, uint64_t src_cols, uint64_t src_rows, uint64_t x0,
                                uint64_t y0, uint64_t win_cols, uint64_t win_rows, uint64_t out_cols, uint64_t out_rows, void* dst,
                                uint8_t* dst_mask_or_null, ec_stream stream) {
-    ec_status st = check_window("ec_window", t, src_cols, src_rows, x0, y0, win_cols, win_rows, src_mask_or_null, dst_mask_or_null);
-    if (st != EC_OK) return st;
-    const bool win_empty = win_cols == 0 || win_rows == 0, out_empty = out_cols == 0 || out_rows == 0;
-    if (win_empty != out_empty)
-        return set_error(EC_ERR_ARG, "ec_window: a window of %llu x %llu cells cannot be read at %llu x %llu", (unsigned long long)win_cols,
-                         (unsigned long long)win_rows, (unsigned long long)out_cols, (unsigned long long)out_rows);
-    if (win_empty) return EC_OK;
-    if (mul_overflows(out_cols, out_rows)) return set_error(EC_ERR_ARG, "ec_window: an output of %llu x %llu cells overflows 64 bits", (unsigned long long)out_cols, (unsigned long long)out_rows);
-    if (!src || !dst) return set_error(EC_ERR_ARG, "ec_window: null pointer");
+    bool nothing = false;
+    ec_status st = check_cut("ec_window", t, src, src_mask_or_null, src_cols, src_rows, x0, y0, win_cols, win_rows, out_cols, out_rows, dst, dst_mask_or_null, &nothing);
+    if (st != EC_OK || nothing) return st;
     const bool resample = out_cols != win_cols || out_rows != win_rows;
     WindowAxis ax, ay;
     if (resample && !(make_axis(win_cols, out_cols, &ax) && make_axis(win_rows, out_rows, &ay)))

@@ -113,6 +113,25 @@ struct ParseError : Error {  // Error::ParseError (ctype.rs:37)
     explicit ParseError(const std::string& s) : Error(EC_ERR_ARG, "Unable to parse " + s + " as a CellType") {}
 };
 
+// gdal::raster::ResampleAlg: what read_cells' e_resample_alg names, in GDAL's order — the numbers are the GRIORA_* ones ec_window_resample
+// takes.  window() has NearestNeighbour, Bilinear and Average; RasterBand::read_cells (raster_io.hpp) only the default, nearest neighbour.
+enum class ResampleAlg { NearestNeighbour, Bilinear, Cubic, CubicSpline, Lanczos, Average, Mode, Gauss };
+inline const char* to_string(ResampleAlg a) {
+    static const char* names[] = {"NearestNeighbour", "Bilinear", "Cubic", "CubicSpline", "Lanczos", "Average", "Mode", "Gauss"};
+    return names[static_cast<int>(a)];
+}
+
+// ec_window, or ec_window_resample when `alg` names another algorithm than the default (one it lacks is refused there, by number)
+inline ec_status window_call(const std::optional<ResampleAlg>& alg, ec_dtype t, const void* src, const uint8_t* src_mask, uint64_t cols, uint64_t rows,
+                             std::pair<size_t, size_t> window, std::pair<size_t, size_t> window_size, std::pair<size_t, size_t> out, void* dst,
+                             uint8_t* dst_mask, ec_stream stream) {
+    if (!alg || *alg == ResampleAlg::NearestNeighbour)
+        return ec_window(t, src, src_mask, cols, rows, window.first, window.second, window_size.first, window_size.second, out.first, out.second, dst,
+                         dst_mask, stream);
+    return ec_window_resample(static_cast<int32_t>(*alg), t, src, src_mask, cols, rows, window.first, window.second, window_size.first,
+                              window_size.second, out.first, out.second, dst, dst_mask, stream);
+}
+
 inline void check(ec_status st) {
     if (st == EC_OK) return;
     if (st == EC_ERR_NARROWING) {
@@ -384,15 +403,16 @@ public:
         return std::string(to_string(ct_)) + "CellBuffer(" + elided(items) + ")";
     }
     // The `window_size` = (w, h) cells at `window` = (x, y) of this buffer read as rows of `cols` cells, delivered as `size` =
-    // (width, height) cells (default: as they are; another size resamples by nearest neighbour) — the device part of
-    // read_cells(window, window_size, size, e_resample_alg) (src/gdal/rasterband.rs:82-103): one ec_window launch.
+    // (width, height) cells (default: as they are; another size resamples by `alg`: nearest neighbour by default, Bilinear and Average by
+    // the rule of ec_window_resample) — the device part of read_cells(window, window_size, size, e_resample_alg)
+    // (src/gdal/rasterband.rs:82-103): one launch.
     CellBuffer window(size_t cols, std::pair<size_t, size_t> window, std::pair<size_t, size_t> window_size,
-                      std::optional<std::pair<size_t, size_t>> size = std::nullopt) const {
+                      std::optional<std::pair<size_t, size_t>> size = std::nullopt, std::optional<ResampleAlg> alg = std::nullopt) const {
         if (cols ? n_ % cols != 0 : n_ != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
         const auto out = size.value_or(window_size);
         CellBuffer b(ct_, out.first * out.second);
-        check(ec_window(static_cast<ec_dtype>(ct_), ptr(), nullptr, cols, cols ? n_ / cols : 0, window.first, window.second, window_size.first,
-                        window_size.second, out.first, out.second, b.ptr(), nullptr, current_stream()));
+        check(window_call(alg, static_cast<ec_dtype>(ct_), ptr(), nullptr, cols, cols ? n_ / cols : 0, window, window_size, out, b.ptr(), nullptr,
+                          current_stream()));
         return b;
     }
     // `tile` (window_size = (w, h) contiguous cells of this buffer's type) into the window at (x, y); nothing outside it changes.
@@ -673,13 +693,13 @@ public:
 
     // CellBuffer::window / put_window for the cells and their mask bytes in ONE launch (read_cells_masked, rasterband.rs:104-125)
     MaskedCellBuffer window(size_t cols, std::pair<size_t, size_t> window, std::pair<size_t, size_t> window_size,
-                            std::optional<std::pair<size_t, size_t>> size = std::nullopt) const {
+                            std::optional<std::pair<size_t, size_t>> size = std::nullopt, std::optional<ResampleAlg> alg = std::nullopt) const {
         if (cols ? len() % cols != 0 : len() != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
         const auto out = size.value_or(window_size);
         CellBuffer b(cell_type(), out.first * out.second);
         Mask m(out.first * out.second);
-        check(ec_window(static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), cols, cols ? len() / cols : 0, window.first, window.second,
-                        window_size.first, window_size.second, out.first, out.second, b.ptr(), m.ptr(), current_stream()));
+        check(window_call(alg, static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), cols, cols ? len() / cols : 0, window, window_size, out,
+                          b.ptr(), m.ptr(), current_stream()));
         return MaskedCellBuffer(std::move(b), std::move(m));
     }
     void put_window(size_t cols, std::pair<size_t, size_t> window, std::pair<size_t, size_t> window_size, const MaskedCellBuffer& tile) {

@@ -55,13 +55,6 @@ inline NoData<T> nodata_from_f64(const std::optional<double>& nd, const char* ty
     return NoData<T>::new_(*v);
 }
 
-// gdal::raster::ResampleAlg: what read_cells' e_resample_alg names.  Only the default, nearest neighbour, is implemented.
-enum class ResampleAlg { NearestNeighbour, Bilinear, Cubic, CubicSpline, Lanczos, Average, Mode, Gauss };
-inline const char* to_string(ResampleAlg a) {
-    static const char* names[] = {"NearestNeighbour", "Bilinear", "Cubic", "CubicSpline", "Lanczos", "Average", "Mode", "Gauss"};
-    return names[static_cast<int>(a)];
-}
-
 class RasterBand {
     size_t width_ = 0, height_ = 0;
     CellType ct_ = CellType::UInt8;

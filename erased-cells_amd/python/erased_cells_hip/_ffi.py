@@ -17,6 +17,8 @@ CSRC = os.path.join(AMD_DIR, "csrc")
 
 EC_OK, EC_ERR_NARROWING, EC_ERR_UNSUPPORTED_TYPE, EC_ERR_LENGTH, EC_ERR_HIP, EC_ERR_RCCL, EC_ERR_ARG, \
     EC_ERR_NOT_INITIALIZED = range(8)
+EC_RESAMPLE_NEAREST, EC_RESAMPLE_BILINEAR, EC_RESAMPLE_AVERAGE = 0, 1, 5  # ec_resample: GDAL's GRIORA_* numbers
+EC_WINDOW_MAX_REDUCTION = 64
 
 
 class _Payload(C.Union):
@@ -141,6 +143,7 @@ SIGNATURES = {
     "ec_mask_counts": (I32, [U8P, SZ, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), VP]),
     "ec_mask_counts_device": (I32, [U8P, SZ, VP, VP]),
     "ec_window": (I32, [C.c_uint8, VP, U8P] + [C.c_uint64] * 8 + [VP, U8P, VP]),
+    "ec_window_resample": (I32, [I32, C.c_uint8, VP, U8P] + [C.c_uint64] * 8 + [VP, U8P, VP]),
     "ec_window_put": (I32, [C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, VP, U8P] + [C.c_uint64] * 4 + [VP]),
     "ec_synth_fill": (I32, [C.c_uint8, VP, SZ, C.c_uint64, C.c_uint64, C.c_double, C.c_double, VP]),
     "ec_synth_mask": (I32, [U8P, SZ, C.c_uint64, C.c_uint64, C.c_uint32, VP]),

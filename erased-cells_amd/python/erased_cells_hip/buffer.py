@@ -19,7 +19,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import EC_ERR_ARG, EcError, EcValue, check, lib
+from ._ffi import EC_ERR_ARG, EC_RESAMPLE_AVERAGE, EC_RESAMPLE_BILINEAR, EcError, EcValue, check, lib
 
 # CellType (src/ctype.rs:11-20; order of with_ct!, src/lib.rs:89-98)
 UInt8, UInt16, UInt32, UInt64, Int8, Int16, Int32, Int64, Float32, Float64 = range(10)
@@ -352,6 +352,24 @@ def _window_args(n: int, cols: int, window, window_size, size):
     return (n // cols if cols else 0), x, y, w, h, out_w, out_h
 
 
+# the names gdal::raster::ResampleAlg gives the algorithms ec_window_resample has (None: GDAL's default, nearest neighbour)
+RESAMPLE_ALGS = {"Bilinear": EC_RESAMPLE_BILINEAR, "Average": EC_RESAMPLE_AVERAGE}
+
+
+def _resample_alg(resample):
+    """None for `resample` None / "NearestNeighbour" (ec_window), the ec_resample number of "Bilinear" / "Average"; any other name is refused"""
+    if resample is None or resample == "NearestNeighbour":
+        return None
+    if resample not in RESAMPLE_ALGS:
+        raise EcError(EC_ERR_ARG, f"window: resampling algorithm {resample!r} is not one of NearestNeighbour, Bilinear, Average")
+    return RESAMPLE_ALGS[resample]
+
+
+def _cut(alg, *args) -> None:
+    """ec_window(*args), or ec_window_resample(alg, *args) when `alg` (_resample_alg) names an algorithm"""
+    check(lib().ec_window(*args, _stream) if alg is None else lib().ec_window_resample(alg, *args, _stream))
+
+
 def _scalar(x) -> CellValue:
     return CellValue.new(x)
 
@@ -426,13 +444,15 @@ class CellBuffer:
         sz = NP_DTYPES[self.ct].itemsize
         return CellBuffer(self.ct, cell_len, self.mem.window(cell_offset * sz, cell_len * sz))
 
-    def window(self, cols: int, window=(0, 0), window_size=(0, 0), size=None) -> "CellBuffer":
+    def window(self, cols: int, window=(0, 0), window_size=(0, 0), size=None, resample=None) -> "CellBuffer":
         """The `window_size` = (w, h) cells at `window` = (x, y) of this buffer read as a raster of rows of `cols` cells, delivered as
-        `size` = (out_w, out_h) cells (default: as they are; another size resamples by nearest neighbour) — the device part of
+        `size` = (out_w, out_h) cells (default: as they are; another size resamples by `resample`: None or "NearestNeighbour",
+        "Bilinear", "Average" — the rule of each is in include/erased_cells.h) — the device part of
         read_cells(window, window_size, size, e_resample_alg) (src/gdal/rasterband.rs:82-103).  One launch, no download."""
+        alg = _resample_alg(resample)
         rows, x, y, w, h, ow, oh = _window_args(self.n, cols, window, window_size, size)
         out = CellBuffer.empty(ow * oh, self.ct)
-        check(lib().ec_window(self.ct, self.mem.ptr, None, cols, rows, x, y, w, h, ow, oh, out.mem.ptr, None, _stream))
+        _cut(alg, self.ct, self.mem.ptr, None, cols, rows, x, y, w, h, ow, oh, out.mem.ptr, None)
         return out
 
     def put_window(self, cols: int, window, tile: "CellBuffer", window_size) -> None:
@@ -797,12 +817,13 @@ class MaskedCellBuffer:
     def shard(self, cell_offset: int, cell_len: int) -> "MaskedCellBuffer":
         return MaskedCellBuffer(self._buf.shard(cell_offset, cell_len), self._mask.shard(cell_offset, cell_len))
 
-    def window(self, cols: int, window=(0, 0), window_size=(0, 0), size=None) -> "MaskedCellBuffer":
-        """CellBuffer.window for values and mask in ONE launch (read_cells_masked, src/gdal/rasterband.rs:104-125)."""
+    def window(self, cols: int, window=(0, 0), window_size=(0, 0), size=None, resample=None) -> "MaskedCellBuffer":
+        """CellBuffer.window for values and mask in ONE launch (read_cells_masked, src/gdal/rasterband.rs:104-125).  "Bilinear" and
+        "Average" weigh the valid cells of a footprint only; an output cell without one is invalid and holds 0."""
+        alg = _resample_alg(resample)
         rows, x, y, w, h, ow, oh = _window_args(self.len(), cols, window, window_size, size)
         out, om = CellBuffer.empty(ow * oh, self.cell_type()), Mask.empty(ow * oh)
-        check(lib().ec_window(self.cell_type(), self._buf.mem.ptr, self._mask.mem.ptr, cols, rows, x, y, w, h, ow, oh,
-                              out.mem.ptr, om.mem.ptr, _stream))
+        _cut(alg, self.cell_type(), self._buf.mem.ptr, self._mask.mem.ptr, cols, rows, x, y, w, h, ow, oh, out.mem.ptr, om.mem.ptr)
         return MaskedCellBuffer(out, om)
 
     def put_window(self, cols: int, window, tile: "MaskedCellBuffer", window_size) -> None:

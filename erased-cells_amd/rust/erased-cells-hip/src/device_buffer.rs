@@ -25,6 +25,15 @@ pub struct CellBuffer {
     pub(crate) mem: DeviceMem,
 }
 
+/// The resampling algorithms of [`CellBuffer::window_resampled`], numbered as GDAL's `GRIORA_*` (`ec_resample`).
+#[repr(i32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum ResampleAlg {
+    NearestNeighbour = EC_RESAMPLE_NEAREST,
+    Bilinear = EC_RESAMPLE_BILINEAR,
+    Average = EC_RESAMPLE_AVERAGE,
+}
+
 impl CellBuffer {
     pub fn new<T: CellEncoding>(data: Vec<T>) -> Self {
         Self::from_host(&data)
@@ -113,6 +122,24 @@ impl CellBuffer {
         check(unsafe {
             ec_window(
                 self.ct as u8, self.dev_ptr(), std::ptr::null(), cols as u64, rows as u64, window.0 as u64, window.1 as u64,
+                window_size.0 as u64, window_size.1 as u64, size.0 as u64, size.1 as u64, cut.mem.ptr(), std::ptr::null_mut(), stream(),
+            )
+        })?;
+        Ok(cut)
+    }
+
+    /// [`CellBuffer::window`] with a resampling algorithm: `Bilinear` and `Average` by the rule of `ec_window_resample`
+    /// (include/erased_cells.h), `NearestNeighbour` as `window` itself.  One `ec_window_resample` launch; an average that reduces an
+    /// axis by more than `EC_WINDOW_MAX_REDUCTION` is an error, chain calls for it.
+    pub fn window_resampled(
+        &self, cols: usize, window: (usize, usize), window_size: (usize, usize), size: (usize, usize), alg: ResampleAlg,
+    ) -> Result<Self> {
+        assert!(if cols == 0 { self.len == 0 } else { self.len % cols == 0 }, "{} cells are not rows of {cols} cells", self.len);
+        let rows = if cols == 0 { 0 } else { self.len / cols };
+        let cut = Self::uninit(self.ct, size.0 * size.1);
+        check(unsafe {
+            ec_window_resample(
+                alg as i32, self.ct as u8, self.dev_ptr(), std::ptr::null(), cols as u64, rows as u64, window.0 as u64, window.1 as u64,
                 window_size.0 as u64, window_size.1 as u64, size.0 as u64, size.1 as u64, cut.mem.ptr(), std::ptr::null_mut(), stream(),
             )
         })?;

@@ -34,6 +34,12 @@ pub const EC_ADD: ec_op = 0;
 pub const EC_SUB: ec_op = 1;
 pub const EC_MUL: ec_op = 2;
 pub const EC_DIV: ec_op = 3;
+/// `ec_resample`: GDAL's `GRIORA_*` numbers of the algorithms `ec_window_resample` has (it takes them as an `i32`).
+pub const EC_RESAMPLE_NEAREST: i32 = 0;
+pub const EC_RESAMPLE_BILINEAR: i32 = 1;
+pub const EC_RESAMPLE_AVERAGE: i32 = 5;
+/// An average reduces an axis by at most this factor per call; chain calls for more.
+pub const EC_WINDOW_MAX_REDUCTION: u64 = 64;
 
 /// Mirrors `ec_value`: tag + 8-byte payload, 16 bytes.
 #[repr(C)]
@@ -215,6 +221,9 @@ extern "C" {
     pub fn ec_window(t: ec_dtype, src: *const c_void, src_mask_or_null: *const u8, src_cols: u64, src_rows: u64, x0: u64, y0: u64,
                      win_cols: u64, win_rows: u64, out_cols: u64, out_rows: u64, dst: *mut c_void, dst_mask_or_null: *mut u8,
                      s: ec_stream) -> ec_status;
+    pub fn ec_window_resample(alg: i32, t: ec_dtype, src: *const c_void, src_mask_or_null: *const u8, src_cols: u64, src_rows: u64,
+                              x0: u64, y0: u64, win_cols: u64, win_rows: u64, out_cols: u64, out_rows: u64, dst: *mut c_void,
+                              dst_mask_or_null: *mut u8, s: ec_stream) -> ec_status;
     pub fn ec_window_put(t: ec_dtype, tile: *const c_void, tile_mask_or_null: *const u8, win_cols: u64, win_rows: u64,
                          dst: *mut c_void, dst_mask_or_null: *mut u8, dst_cols: u64, dst_rows: u64, x0: u64, y0: u64,
                          s: ec_stream) -> ec_status;

@@ -11,7 +11,7 @@
 use crate::device::stream;
 use crate::error::{check, must, Result};
 use crate::ffi::*;
-use crate::{BufferOps, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Mask, NoData};
+use crate::{BufferOps, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Mask, NoData, ResampleAlg};
 use std::fmt::{Debug, Formatter};
 use std::ops::{Add, Div, Mul, Neg, Sub};
 
@@ -61,6 +61,25 @@ impl MaskedCellBuffer {
         check(unsafe {
             ec_window(
                 self.0.ct as u8, self.0.dev_ptr(), self.1.dev_ptr(), cols as u64, rows as u64, window.0 as u64, window.1 as u64,
+                window_size.0 as u64, window_size.1 as u64, size.0 as u64, size.1 as u64, cells.mem.ptr(), mask.dev_ptr_mut(), stream(),
+            )
+        })?;
+        Ok(MaskedCellBuffer(cells, mask))
+    }
+
+    /// [`CellBuffer::window_resampled`] for the cells and their mask bytes in ONE launch: only the valid cells of a footprint carry
+    /// weight; an output cell whose footprint has none is invalid and holds 0.
+    pub fn window_resampled(
+        &self, cols: usize, window: (usize, usize), window_size: (usize, usize), size: (usize, usize), alg: ResampleAlg,
+    ) -> Result<Self> {
+        let len = self.0.len();
+        assert!(if cols == 0 { len == 0 } else { len % cols == 0 }, "{len} cells are not rows of {cols} cells");
+        let rows = if cols == 0 { 0 } else { len / cols };
+        let cells = CellBuffer::uninit(self.0.ct, size.0 * size.1);
+        let mask = Mask::uninit(size.0 * size.1);
+        check(unsafe {
+            ec_window_resample(
+                alg as i32, self.0.ct as u8, self.0.dev_ptr(), self.1.dev_ptr(), cols as u64, rows as u64, window.0 as u64, window.1 as u64,
                 window_size.0 as u64, window_size.1 as u64, size.0 as u64, size.1 as u64, cells.mem.ptr(), mask.dev_ptr_mut(), stream(),
             )
         })?;

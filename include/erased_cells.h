@@ -461,7 +461,7 @@ ec_status ec_mask_counts_device(const uint8_t *m, size_t n, uint64_t *counts2_de
 /* RasterBandEx::read_cells / read_cells_masked(window, window_size, size, e_resample_alg) — src/gdal/rasterband.rs:82-125,
  * the part behind the decoder: `src` is a row-major raster of src_cols x src_rows cells of type t on the device; the window
  * of win_cols x win_rows cells at column x0, row y0 is written to `dst` as out_cols x out_rows contiguous cells.
- * out == win copies the cells; any other size resamples by nearest neighbour (GDAL's default, the only algorithm), defined in
+ * out == win copies the cells; any other size resamples by nearest neighbour (GDAL's default; ec_window_resample has the others), defined in
  * integers: output column j reads window column floor((2 j + 1) * win_cols / (2 * out_cols)) — the cell-centre rule
  * (j + 0.5) * win_cols / out_cols evaluated exactly — and rows likewise.  With both masks non-NULL the mask bytes of the same
  * cells move in the same launch (read_cells_masked, rasterband.rs:104-125).  No allocation, asynchronous, capturable.
@@ -478,6 +478,40 @@ ec_status ec_window(ec_dtype t, const void *src, const uint8_t *src_mask_or_null
 ec_status ec_window_put(ec_dtype t, const void *tile, const uint8_t *tile_mask_or_null, uint64_t win_cols, uint64_t win_rows,
                         void *dst, uint8_t *dst_mask_or_null, uint64_t dst_cols, uint64_t dst_rows,
                         uint64_t x0, uint64_t y0, ec_stream stream);
+/* The e_resample_alg of read_cells(window, window_size, size, e_resample_alg) — src/gdal/rasterband.rs:37-43, 82-125 — with
+ * GDAL's GRIORA_* numbers.  ec_window_resample takes it as an int32_t, as every enumeration crosses this ABI (ec_op). */
+typedef enum { EC_RESAMPLE_NEAREST = 0, EC_RESAMPLE_BILINEAR = 1, EC_RESAMPLE_AVERAGE = 5 } ec_resample;
+/* An average reduces an axis by at most this factor per call (win <= EC_WINDOW_MAX_REDUCTION * out): a lane walks its
+ * footprint in a fixed order, which is what makes the answer unique, and 65 x 65 taps bound its run time.  Chain calls for
+ * more, as overview pyramids do. */
+enum { EC_WINDOW_MAX_REDUCTION = 64 };
+/* ec_window with a resampling algorithm (src/gdal/rasterband.rs:82-125): same arguments and contract after `alg` — no
+ * allocation, asynchronous, capturable, output of type t, every check before any device work.  EC_RESAMPLE_NEAREST is
+ * ec_window; out == win on both axes is the copy whatever `alg` is; any `alg` but the three above is EC_ERR_ARG naming it
+ * (GDAL's Cubic 2, CubicSpline 3, Lanczos 4, Mode 6, Gauss 7 among them).
+ * The rule, in integers and individually rounded f64 operations (no FMA), so every cell has one right answer.  Along one
+ * axis output index j of `out` over `win` cells has taps (c, w) — window index c, integer weight w > 0 — in ascending order:
+ *   AVERAGE   win and out divided by their gcd; lo = j * win, hi = lo + win; c = lo / out .. (hi - 1) / out, w = min((c + 1)
+ *             * out, hi) - max(c * out, lo): the overlap with cell c in units of 1 / out cell.  A whole factor is the block mean.
+ *   BILINEAR  cell centres, clamped to the WINDOW: t = (2 j + 1) * win + out, k = t / (2 out), f = t % (2 out); taps (k - 1,
+ *             2 out - f), (k, f), each index clamped into [0, win - 1], a tap of weight 0 dropped (never read), two taps on
+ *             one cell kept as two.
+ * Output cell (i, j), ytaps from the row axis, xtaps from the column axis:
+ *   acc = 0.0; wsum = 0 (exact, 64 bits)
+ *   for (y, wy) in ytaps:  racc = 0.0; rw = 0
+ *       for (x, wx) in xtaps:  if no mask or mask[y, x] != 0:  racc = racc + double(wx) * double(cell[y, x]);  rw += wx
+ *       acc = acc + double(wy) * racc;  wsum += wy * rw
+ *   wsum == 0: value of all-zero bits, out mask 0;  otherwise r = acc / double(wsum), out mask 1
+ * f64 takes r, f32 (float)r to nearest even, the integer types trunc(r + copysign(0.5, r)) saturated to the type's range as
+ * Rust's `as` does.  double(cell) of a 64-bit integer is the rounding conversion.  A masked-out cell contributes nothing,
+ * whatever it holds.
+ * EC_ERR_ARG: everything ec_window refuses; an average beyond EC_WINDOW_MAX_REDUCTION on an axis; axis arithmetic beyond
+ * 64 bits (win * out for the average, 2 * out * win + out for bilinear); a total weight beyond 64 bits (4 * out_cols *
+ * out_rows for bilinear). */
+ec_status ec_window_resample(int32_t alg /* an ec_resample */, ec_dtype t, const void *src, const uint8_t *src_mask_or_null,
+                             uint64_t src_cols, uint64_t src_rows, uint64_t x0, uint64_t y0,
+                             uint64_t win_cols, uint64_t win_rows, uint64_t out_cols, uint64_t out_rows,
+                             void *dst, uint8_t *dst_mask_or_null, ec_stream stream);
 
 /* ---------------------------------------------------------------- *
  * Test/bench support (not part of the reference surface).
