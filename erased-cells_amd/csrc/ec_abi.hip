@@ -53,25 +53,6 @@ static ec_status sync_result(hipStream_t s, int nwords, int64_t (&host)[2], Run 
     return st;
 }
 
-// Workgroups of `kernel` (BLOCK threads, no dynamic LDS) that fit on one CU at a time, at most `want`.
-template <typename K>
-static int resident_per_cu(K kernel, int block, int want) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, 0) != hipSuccess || nb < 1) {
-        (void)hipGetLastError();
-        return want;
-    }
-    return nb < want ? nb : want;
-}
-
-// reduce_plan (ec_reduce_plan.hpp) of a launch on this thread's device under the current knobs.  `p0`: stream 0's first cell;
-// `residue1`: see reduce_plan; `stream_bytes`: what cache_plan() decides the load policy from.
-static unsigned residue(const void* p, size_t mod) { return static_cast<unsigned>(reinterpret_cast<uintptr_t>(p) % mod); }
-static ReducePlan plan_reduction(const void* p0, unsigned residue1, size_t cell_size, size_t n, const ReduceShape& shape,
-                                 const size_t* stream_bytes, int nstreams) {
-    return reduce_plan(residue(p0, 16), residue1, cell_size, n, shape, device_cus(), tuning().reduce_bpc, tuning().unaligned_vector != 0,
-                       cache_plan(stream_bytes, nstreams));
-}
 // first difference and mask counts: the default shape, its cell-wise branch inside the same kernel
 constexpr ReduceShape kScanShape = {kRBlock, kReduceU, 4, kRBlock, 4};
 

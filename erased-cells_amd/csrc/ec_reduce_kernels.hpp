@@ -73,6 +73,23 @@ __device__ __forceinline__ V lane_xor(V v, int off) {
     if constexpr (std::is_same<V, K2>::value) return K2{__shfl_xor(v.x, off, 64), __shfl_xor(v.y, off, 64)};
     else return __shfl_xor(v, off, 64);
 }
+// The partial of the stats kernels (ec_stats_kernels.hpp): 48 bytes, which a finalize thread loads as three 16-byte words.
+// a, b, c are the three moment words of ec_moments' union; FoldMoments<KIND> knows what they hold.
+struct alignas(16) Moments {
+    uint64_t count;
+    int64_t kmin, kmax;  // order keys, as K2
+    uint64_t a, b, c;
+};
+__device__ __forceinline__ Moments lane_xor(const Moments& v, int off) {
+    Moments r;
+    r.count = __shfl_xor(v.count, off, 64);
+    r.kmin = __shfl_xor(v.kmin, off, 64);
+    r.kmax = __shfl_xor(v.kmax, off, 64);
+    r.a = __shfl_xor(v.a, off, 64);
+    r.b = __shfl_xor(v.b, off, 64);
+    r.c = __shfl_xor(v.c, off, 64);
+    return r;
+}
 template <typename V, typename Op>
 __device__ __forceinline__ V wave_fold(V v, Op op) {
 #pragma unroll
@@ -310,8 +327,9 @@ __device__ __forceinline__ void finalize_fold(const V* __restrict__ partials, in
     if (block_fold<kFinalizeBlock>(acc, op)) write(acc);
 }
 
-// keys2 = {~min, max}: a MAX reduction over shards of both words is the global answer.
-__global__ __launch_bounds__(kFinalizeBlock) void k_min_max_finalize(const int64_t* __restrict__ partials, int nparts,
+// keys2 = {~min, max}: a MAX reduction over shards of both words is the global answer.  (The three finalize kernels are no
+// templates, and more than one translation unit includes this header: internal linkage.)
+static __global__ __launch_bounds__(kFinalizeBlock) void k_min_max_finalize(const int64_t* __restrict__ partials, int nparts,
                                                                       int64_t sentinel_min, int64_t sentinel_max,
                                                                       int64_t* __restrict__ keys2) {
     finalize_fold(reinterpret_cast<const K2*>(partials), nparts, K2{sentinel_min, sentinel_max}, FoldMinMax{},
@@ -392,7 +410,7 @@ __global__ __launch_bounds__(kRBlock) void k_first_diff_partials(const W* __rest
     if (block_fold<kRBlock>(first, FoldMin{})) partials[blockIdx.x] = first;
 }
 
-__global__ __launch_bounds__(kFinalizeBlock) void k_first_diff_finalize(const uint64_t* __restrict__ partials, int nparts,
+static __global__ __launch_bounds__(kFinalizeBlock) void k_first_diff_finalize(const uint64_t* __restrict__ partials, int nparts,
                                                                          uint64_t* __restrict__ result) {
     finalize_fold(partials, nparts, ~uint64_t(0), FoldMin{}, [=](uint64_t first) { result[0] = first; });
 }
@@ -469,7 +487,7 @@ __global__ __launch_bounds__(kRBlock) void k_mask_count_partials(const uint8_t* 
     }
 }
 
-__global__ __launch_bounds__(kFinalizeBlock) void k_mask_count_finalize(const uint64_t* __restrict__ partials, int nparts,
+static __global__ __launch_bounds__(kFinalizeBlock) void k_mask_count_finalize(const uint64_t* __restrict__ partials, int nparts,
                                                                          uint64_t n, uint64_t* __restrict__ counts2) {
     finalize_fold(partials, nparts, uint64_t(0), FoldSum{}, [=](uint64_t cnt) { counts2[0] = cnt; counts2[1] = n - cnt; });
 }

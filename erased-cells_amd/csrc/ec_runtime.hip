@@ -216,7 +216,7 @@ ec_status get_scratch(hipStream_t s, Scratch* out) {
         ScratchEntry e;
         auto own = std::make_shared<ScratchOwner>();
         own->device = t_active;
-        ec_status st = check_hip(hipMalloc(reinterpret_cast<void**>(&own->dev), (2 * kMaxReduceBlocks + 8) * sizeof(int64_t)),
+        ec_status st = check_hip(hipMalloc(reinterpret_cast<void**>(&own->dev), kScratchWords * sizeof(int64_t)),
                                  "hipMalloc(scratch)");
         if (st != EC_OK) return st;
         // the accumulator words (Scratch::dev_acc) start at zero; every kernel that uses one leaves it at zero again

@@ -210,21 +210,46 @@ inline unsigned grid_capped(size_t blocks, int bpc) {
 // partials are ordered by the stream itself; `mu` serialises the synchronous-result entry points (ec_min_max,
 // ec_mask_counts, ec_first_difference), which read `host` after waiting for the stream — two host threads sharing
 // one stream therefore take turns instead of racing on the four pinned words.
+constexpr int kStatsRecordWords = 8;  // one ec_moments (64 bytes); a Moments partial (ec_reduce_kernels.hpp) is no larger
 struct ScratchOwner;  // frees the three allocations when the last Scratch copy that names them is gone (ec_runtime.hip)
 struct Scratch {
     std::shared_ptr<ScratchOwner> owner;  // every copy handed out by get_scratch() shares ownership: releasing or recycling a
                                           // stream's entry only drops the TABLE's reference, so a host thread that is
                                           // inside ec_min_max / ec_mask_counts / ec_first_difference with this scratch
                                           // (its `mu` locked, its kernels queued) keeps valid memory until it returns
-    int64_t* dev = nullptr;    // 2*kMaxReduceBlocks partials + 4 result words + 4 accumulator words (zero between kernels)
+    int64_t* dev = nullptr;    // 2*kMaxReduceBlocks partials + 4 result words + 4 accumulator words (zero between kernels), then
+                               // kMaxReduceBlocks + 1 records of kStatsRecordWords words: the stats kernels' partials and ec_stats_compute's record
     int64_t* host = nullptr;   // 4 words, pinned (coherent): the synchronous-result entry points let the last kernel write
                                // its result straight into them — no device-to-host copy is queued behind the kernel
     int64_t* host_dev = nullptr;  // the same words as the device addresses them
     std::mutex* mu = nullptr;
     int64_t* dev_result() const { return dev + 2 * kMaxReduceBlocks; }
     int64_t* dev_acc() const { return dev + 2 * kMaxReduceBlocks + 4; }
+    int64_t* dev_stats() const { return dev + 2 * kMaxReduceBlocks + 8; }  // 64-byte aligned: hipMalloc's alignment + 64 * 1025 bytes
+    int64_t* dev_stats_record() const { return dev_stats() + size_t(kStatsRecordWords) * kMaxReduceBlocks; }
 };
+constexpr size_t kScratchWords = 2 * kMaxReduceBlocks + 8 + size_t(kStatsRecordWords) * (kMaxReduceBlocks + 1);
 ec_status get_scratch(hipStream_t s, Scratch* out);
+
+// Workgroups of `kernel` (BLOCK threads, no dynamic LDS) that fit on one CU at a time, at most `want`.
+template <typename K>
+inline int resident_per_cu(K kernel, int block, int want) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, 0) != hipSuccess || nb < 1) {
+        (void)hipGetLastError();
+        return want;
+    }
+    return nb < want ? nb : want;
+}
+
+// reduce_plan (ec_reduce_plan.hpp) of a launch on this thread's device under the current knobs.  `p0`: stream 0's first cell;
+// `residue1`: see reduce_plan; `stream_bytes`: what cache_plan() decides the load policy from.
+inline unsigned residue(const void* p, size_t mod) { return static_cast<unsigned>(reinterpret_cast<uintptr_t>(p) % mod); }
+inline ReducePlan plan_reduction(const void* p0, unsigned residue1, size_t cell_size, size_t n, const ReduceShape& shape,
+                                 const size_t* stream_bytes, int nstreams) {
+    return reduce_plan(residue(p0, 16), residue1, cell_size, n, shape, device_cus(), tuning().reduce_bpc, tuning().unaligned_vector != 0,
+                       cache_plan(stream_bytes, nstreams));
+}
 
 // binary arithmetic, one translation unit per op
 template <int OP>

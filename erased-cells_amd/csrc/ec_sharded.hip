@@ -5,7 +5,7 @@
 //     host ≈5 µs: eight devices served by one thread would serialise 40 µs of launches in front of kernels
 //     that take ≈55 µs per 1/8 shard of a 16384² raster; eight threads issue them side by side),
 //   * a non-blocking stream with its reduction scratch,
-//   * a 32-byte device payload slot and a 32-byte pinned host slot,
+//   * a 64-byte device payload slot and a 64-byte pinned host slot (two words for min/max and counts, one ec_moments for stats),
 //   * an RCCL communicator of the n-device clique (ncclCommInitAll) unless EC_GROUP_HOST_COMBINE.
 //
 // Element-wise entry points are FIRE-AND-FORGET (round 3): the calling thread checks the arguments, copies the
@@ -44,17 +44,20 @@
 #include "ec_hostpipe.hpp"
 #include "ec_lattice.hpp"
 #include "ec_runtime.hpp"
+#include "ec_stats_fold.hpp"
 #include "ec_worker.hpp"
 
 using namespace ecd;
+
+constexpr size_t kPayloadWords = sizeof(ec_moments) / sizeof(int64_t);  // the largest payload: one stats record
 
 struct ec_shard_group {
     int n = 0;
     uint32_t flags = 0;
     std::vector<int> devices;
     std::vector<hipStream_t> streams;
-    std::vector<int64_t*> payload_dev;   // 4 words per shard
-    std::vector<int64_t*> payload_host;  // 4 words per shard, pinned
+    std::vector<int64_t*> payload_dev;   // kPayloadWords per shard
+    std::vector<int64_t*> payload_host;  // kPayloadWords per shard, pinned
     std::vector<ncclComm_t> comms;       // empty with EC_GROUP_HOST_COMBINE
     std::vector<Worker*> workers;        // empty when n == 1: the caller's thread does the work
     std::mutex call_mu;                  // one sharded call is POSTED at a time per group (keeps every device's queue in
@@ -283,8 +286,8 @@ extern "C" ec_status ec_shard_group_create(const int32_t* devices, int32_t n, ui
         ec_stream s = nullptr;
         if (st == EC_OK) st = ec_stream_create(&s);  // also prepares the stream's reduction scratch
         g->streams[i] = static_cast<hipStream_t>(s);
-        if (st == EC_OK) st = check_hip(hipMalloc(reinterpret_cast<void**>(&g->payload_dev[i]), 4 * sizeof(int64_t)), "hipMalloc(payload)");
-        if (st == EC_OK) st = check_hip(hipHostMalloc(reinterpret_cast<void**>(&g->payload_host[i]), 4 * sizeof(int64_t), hipHostMallocDefault),
+        if (st == EC_OK) st = check_hip(hipMalloc(reinterpret_cast<void**>(&g->payload_dev[i]), kPayloadWords * sizeof(int64_t)), "hipMalloc(payload)");
+        if (st == EC_OK) st = check_hip(hipHostMalloc(reinterpret_cast<void**>(&g->payload_host[i]), kPayloadWords * sizeof(int64_t), hipHostMallocDefault),
                                         "hipHostMalloc(payload)");
     }
     if (st == EC_OK && !host_combine) {
@@ -697,4 +700,41 @@ extern "C" ec_status ec_sharded_counts(ec_shard_group* g, const uint8_t* const* 
     *n_true = static_cast<uint64_t>(sums[0]);
     *n_false = static_cast<uint64_t>(sums[1]);
     return EC_OK;
+}
+
+// Band statistics of the whole raster (ec_stats_device per shard; BufferOps::min_max, src/buffer.rs:169-173, with the moments
+// beside it): every shard writes its 64-byte record to its payload slot, the records come down and ec_stats_fold folds them in
+// shard order on the host.  No collective — nothing to poison, the same bits on every run, no RCCL.  Phased like the other
+// reductions as far as it goes: arguments first, then every shard's launch, and a failure an earlier call left behind comes first.
+extern "C" ec_status ec_sharded_stats(ec_shard_group* g, ec_dtype t, const void* const* p, const uint8_t* const* masks_or_null,
+                                      const size_t* n, void* stats_out) {
+    ec_status st = check_group(g, "ec_sharded_stats");
+    if (st != EC_OK) return st;
+    if (!p || !n || !stats_out) return set_error(EC_ERR_ARG, "ec_sharded_stats: null argument");
+    if (!ecl::valid(t)) return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_sharded_stats: bad dtype");
+    if ((st = check_col(g, "ec_sharded_stats", "p", p, n)) != EC_OK) return st;
+    if (masks_or_null && (st = check_col(g, "ec_sharded_stats", "masks", masks_or_null, n)) != EC_OK) return st;
+    const uint64_t limit = stats_max_cells(t);
+    for (int i = 0; i < g->n; ++i)
+        if (limit && n[i] > limit)
+            return set_error(EC_ERR_ARG, "ec_sharded_stats: shard %d has %zu cells, more than the %llu one exact record covers: shard it finer",
+                             i, n[i], static_cast<unsigned long long>(limit));
+    std::lock_guard<std::mutex> lk(g->call_mu);
+    st = for_each_shard(g, [&](int i) {
+        return ec_stats_device(t, p[i], masks_or_null ? masks_or_null[i] : nullptr, n[i], g->payload_dev[i], g->streams[i]);
+    });
+    const std::string keep = last_error_text();
+    const ec_status deferred = take_deferred(g);
+    if (deferred != EC_OK) return deferred;
+    if (st != EC_OK) return set_error_text(st, keep);
+    st = for_each_shard(g, [&](int i) {
+        ec_status s = check_hip(hipMemcpyAsync(g->payload_host[i], g->payload_dev[i], sizeof(ec_moments), hipMemcpyDeviceToHost, g->streams[i]),
+                                "hipMemcpyAsync(stats record)");
+        if (s != EC_OK) return s;
+        return check_hip(hipStreamSynchronize(g->streams[i]), "hipStreamSynchronize");
+    });
+    if (st != EC_OK) return st;
+    std::vector<ec_moments> recs(static_cast<size_t>(g->n));
+    for (int i = 0; i < g->n; ++i) std::memcpy(&recs[static_cast<size_t>(i)], g->payload_host[i], sizeof(ec_moments));
+    return ec_stats_fold(recs.data(), g->n, stats_out);
 }

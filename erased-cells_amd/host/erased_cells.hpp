@@ -324,6 +324,16 @@ struct NoData {
     }
 };
 
+// Band statistics of one pass over a resident buffer (ec_stats_compute): min / max as min_max() gives them, stddev the population
+// one (divided by count), as GDAL's STATISTICS_STDDEV (src/gdal/rasterband.rs:151-156).  count == 0: the (T::MAX, T::MIN) sentinels,
+// sum 0, mean and stddev NaN.
+struct Stats {
+    uint64_t count;
+    CellValue min, max;
+    double sum, mean, stddev;
+    explicit Stats(const ec_stats& s) : count(s.count), min(s.min), max(s.max), sum(s.sum), mean(s.mean), stddev(s.stddev) {}
+};
+
 // ---------------------------------------------------------------- CellBuffer (src/buffer.rs)
 class CellBuffer {
     CellType ct_ = CellType::UInt8;
@@ -480,6 +490,12 @@ public:
         ec_value mn, mx;
         check(ec_min_max(static_cast<ec_dtype>(ct_), ptr(), nullptr, n_, &mn, &mx, current_stream()));
         return {CellValue(mn), CellValue(mx)};
+    }
+    // count, min, max, sum, mean and population stddev in one pass over the cells where they are (ec_stats_compute)
+    Stats stats() const {
+        ec_stats out;
+        check(ec_stats_compute(static_cast<ec_dtype>(ct_), ptr(), nullptr, n_, &out, current_stream()));
+        return Stats(out);
     }
     template <typename T> std::vector<T> to_vec() const {  // buffer.rs:175-185
         CellBuffer r = convert(CellEncoding<T>::cell_type());
@@ -752,6 +768,12 @@ public:
         ec_value mn, mx;
         check(ec_min_max(static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), len(), &mn, &mx, current_stream()));
         return {CellValue(mn), CellValue(mx)};
+    }
+    // CellBuffer::stats over the valid cells: a masked-out cell contributes nothing, whatever it holds
+    Stats stats() const {
+        ec_stats out;
+        check(ec_stats_compute(static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), len(), &out, current_stream()));
+        return Stats(out);
     }
 
     // ---- ops (:323-383)
@@ -1189,6 +1211,17 @@ public:
         std::vector<const void*> p(ptrs_.begin(), ptrs_.end());
         check(ec_sharded_min_max(grp_->raw(), static_cast<ec_dtype>(ct_), p.data(), nullptr, lens_.data(), &mn, &mx));
         return {CellValue(mn), CellValue(mx)};
+    }
+    // CellBuffer::stats of the whole raster: one record per shard, folded on the host in shard order (no collective)
+    // (`mask`: a UInt8 buffer of 0 / 1 bytes cut the same way — a cell counts iff its byte is non-zero)
+    Stats stats(const ShardedCellBuffer* mask = nullptr) const {
+        if (mask && (mask->ct_ != CellType::UInt8 || mask->lens_ != lens_)) throw Error(EC_ERR_LENGTH, "the mask must be UInt8 and sharded identically");
+        ec_stats out;
+        std::vector<const void*> p(ptrs_.begin(), ptrs_.end());
+        std::vector<const uint8_t*> m;
+        if (mask) for (void* q : mask->ptrs_) m.push_back(static_cast<const uint8_t*>(q));
+        check(ec_sharded_stats(grp_->raw(), static_cast<ec_dtype>(ct_), p.data(), mask ? m.data() : nullptr, lens_.data(), &out));
+        return Stats(out);
     }
     template <typename T> std::vector<T> to_vec() const {  // gather; T must be the buffer's own cell type
         if (CellEncoding<T>::cell_type() != ct_) throw NarrowingError(ct_, CellEncoding<T>::cell_type());

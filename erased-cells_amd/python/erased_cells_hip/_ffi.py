@@ -37,6 +37,30 @@ class EcExprStep(C.Structure):
     _fields_ = [("op", C.c_int8), ("a", C.c_int8), ("b", C.c_int8), ("dst", C.c_int8)]
 
 
+class _MomentsInt(C.Structure):
+    _fields_ = [("sum", C.c_int64), ("sq_lo", C.c_uint64), ("sq_hi", C.c_uint64)]
+
+
+class _MomentsF64(C.Structure):
+    _fields_ = [("pivot", C.c_double), ("s1", C.c_double), ("s2", C.c_double)]
+
+
+class _MomentsUnion(C.Union):
+    _fields_ = [("i", _MomentsInt), ("f", _MomentsF64)]
+
+
+class EcMoments(C.Structure):
+    """ec_moments: the 64-byte record one ec_stats_device launch leaves on the device (include/erased_cells.h)."""
+    _fields_ = [("count", C.c_uint64), ("keys2", C.c_int64 * 2), ("kind", C.c_int32), ("dtype", C.c_int32),
+                ("u", _MomentsUnion), ("reserved", C.c_uint64)]
+
+
+class EcStats(C.Structure):
+    """ec_stats: what ec_stats_fold makes of one or several records."""
+    _fields_ = [("count", C.c_uint64), ("min", EcValue), ("max", EcValue), ("sum", C.c_double), ("mean", C.c_double),
+                ("stddev", C.c_double)]
+
+
 VP, SZ, I32, U8P = C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p
 PV = C.POINTER(EcValue)
 PVP, PSZ = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
@@ -142,6 +166,10 @@ SIGNATURES = {
     "ec_mask_not": (I32, [U8P, SZ, U8P, VP]),
     "ec_mask_counts": (I32, [U8P, SZ, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), VP]),
     "ec_mask_counts_device": (I32, [U8P, SZ, VP, VP]),
+    "ec_stats_device": (I32, [C.c_uint8, VP, U8P, SZ, VP, VP]),
+    "ec_stats_fold": (I32, [VP, I32, VP]),
+    "ec_stats_compute": (I32, [C.c_uint8, VP, U8P, SZ, VP, VP]),
+    "ec_sharded_stats": (I32, [VP, C.c_uint8, PVP, PVP, PSZ, VP]),
     "ec_window": (I32, [C.c_uint8, VP, U8P] + [C.c_uint64] * 8 + [VP, U8P, VP]),
     "ec_window_resample": (I32, [I32, C.c_uint8, VP, U8P] + [C.c_uint64] * 8 + [VP, U8P, VP]),
     "ec_window_put": (I32, [C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, VP, U8P] + [C.c_uint64] * 4 + [VP]),

@@ -15,11 +15,12 @@ erased-cells_amd/host/erased_cells.hpp and the Rust binding is in INTEGRATION.md
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import EC_ERR_ARG, EC_RESAMPLE_AVERAGE, EC_RESAMPLE_BILINEAR, EcError, EcValue, check, lib
+from ._ffi import EC_ERR_ARG, EC_RESAMPLE_AVERAGE, EC_RESAMPLE_BILINEAR, EcError, EcStats, EcValue, check, lib
 
 # CellType (src/ctype.rs:11-20; order of with_ct!, src/lib.rs:89-98)
 UInt8, UInt16, UInt32, UInt64, Int8, Int16, Int32, Int64, Float32, Float64 = range(10)
@@ -375,6 +376,23 @@ def _scalar(x) -> CellValue:
 
 
 # --------------------------------------------------------------------------- CellBuffer
+@dataclasses.dataclass(frozen=True)
+class Stats:
+    """Band statistics of one pass over a resident buffer (`ec_stats_compute`): `min` / `max` as `min_max()` gives them, `stddev` the
+    population one (divided by `count`), as GDAL's STATISTICS_STDDEV (src/gdal/rasterband.rs:151-156).  With `count == 0`: the
+    sentinels, `sum == 0.0`, `mean` and `stddev` NaN."""
+    count: int
+    min: "CellValue"
+    max: "CellValue"
+    sum: float
+    mean: float
+    stddev: float
+
+    @staticmethod
+    def from_ec(s: EcStats) -> "Stats":
+        return Stats(int(s.count), CellValue.from_ec(s.min), CellValue.from_ec(s.max), float(s.sum), float(s.mean), float(s.stddev))
+
+
 class CellBuffer:
     """Device-resident `CellBuffer` (src/buffer.rs:12-55): a cell type tag + n cells in HBM."""
 
@@ -534,6 +552,12 @@ class CellBuffer:
         mn, mx = EcValue(), EcValue()
         check(lib().ec_min_max(self.ct, self.mem.ptr, None, self.n, C.byref(mn), C.byref(mx), _stream))
         return CellValue.from_ec(mn), CellValue.from_ec(mx)
+
+    def stats(self) -> Stats:
+        """count, min, max, sum, mean and population stddev in one pass over the cells where they are."""
+        out = EcStats()
+        check(lib().ec_stats_compute(self.ct, self.mem.ptr, None, self.n, C.byref(out), _stream))
+        return Stats.from_ec(out)
 
     # ---- arithmetic (src/buffer.rs:321-371)
     def _binop(self, op: int, rhs) -> "CellBuffer":
@@ -885,6 +909,12 @@ class MaskedCellBuffer:
         check(lib().ec_min_max(self.cell_type(), self._buf.mem.ptr, self._mask.mem.ptr, self.len(),
                                C.byref(mn), C.byref(mx), _stream))
         return CellValue.from_ec(mn), CellValue.from_ec(mx)
+
+    def stats(self) -> Stats:
+        """`CellBuffer.stats` over the valid cells: a masked-out cell contributes nothing, whatever it holds."""
+        out = EcStats()
+        check(lib().ec_stats_compute(self.cell_type(), self._buf.mem.ptr, self._mask.mem.ptr, self.len(), C.byref(out), _stream))
+        return Stats.from_ec(out)
 
     # ---- arithmetic (src/masked/masked_buffer.rs:323-383)
     def _binop(self, op: int, rhs) -> "MaskedCellBuffer":

@@ -331,6 +331,11 @@ class Lazy:
                 return program_min_max(*prog)
         return self.eval().min_max()
 
+    def stats(self):
+        """`eval().stats()`: TWO passes — the tree's raster is written, then read once more for its statistics (there is no
+        statistics form of the one-pass kernels, unlike `min_max`)."""
+        return self.eval().stats()
+
     def eval(self):
         if self.op is None:
             return self.leaf

@@ -18,7 +18,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import buffer as B
-from ._ffi import EcValue, check, lib
+from ._ffi import EcStats, EcValue, check, lib
 
 
 def shard_range(n_rows: int, n_cols: int, shard: int, n_shards: int) -> tuple[int, int]:
@@ -258,6 +258,13 @@ class ShardGroup:
         check(lib().ec_sharded_min_max(self.handle, sb.ct, sb.ptrs, mask.ptrs if mask is not None else None,
                                        (C.c_size_t * self.n)(*sb.lens), C.byref(mn), C.byref(mx)))
         return B.CellValue.from_ec(mn), B.CellValue.from_ec(mx)
+
+    def stats(self, sb: ShardedBuffer, mask: ShardedBuffer = None) -> "B.Stats":
+        """`CellBuffer.stats` of the whole sharded raster: one record per shard, folded on the host in shard order (no collective)."""
+        out = EcStats()
+        check(lib().ec_sharded_stats(self.handle, sb.ct, sb.ptrs, mask.ptrs if mask is not None else None,
+                                     (C.c_size_t * self.n)(*sb.lens), C.byref(out)))
+        return B.Stats.from_ec(out)
 
     def counts(self, mask: ShardedBuffer) -> tuple[int, int]:
         t, f = C.c_uint64(), C.c_uint64()

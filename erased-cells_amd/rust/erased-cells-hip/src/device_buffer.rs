@@ -34,7 +34,45 @@ pub enum ResampleAlg {
     Average = EC_RESAMPLE_AVERAGE,
 }
 
+/// Band statistics of one pass over a resident buffer (`ec_stats_compute`): `min` / `max` as `min_max()` gives them, `stddev`
+/// the population one (divided by `count`), as GDAL's `STATISTICS_STDDEV`.  With `count == 0`: the `(T::MAX, T::MIN)` sentinels,
+/// `sum == 0.0`, `mean` and `stddev` NaN.
+#[derive(Clone, Copy, Debug)]
+pub struct Stats {
+    pub count: u64,
+    pub min: CellValue,
+    pub max: CellValue,
+    pub sum: f64,
+    pub mean: f64,
+    pub stddev: f64,
+}
+
+impl Stats {
+    pub(crate) fn blank() -> ec_stats {
+        let zero = CellValue::UInt8(0).to_ffi();
+        ec_stats { count: 0, min: zero, max: zero, sum: 0.0, mean: 0.0, stddev: 0.0 }
+    }
+    pub(crate) fn from_ffi(s: &ec_stats) -> Self {
+        Stats { count: s.count, min: CellValue::from_ffi(&s.min), max: CellValue::from_ffi(&s.max), sum: s.sum, mean: s.mean, stddev: s.stddev }
+    }
+}
+
 impl CellBuffer {
+    /// count, min, max, sum, mean and population stddev in one pass over the cells where they are.  `mask`: the device
+    /// bytes of a mask of the same length, or null.
+    pub(crate) fn stats_raw(&self, mask: *const u8) -> Stats {
+        let mut out = Stats::blank();
+        must(
+            unsafe { ec_stats_compute(self.ct as u8, self.dev_ptr(), mask, self.len, &mut out as *mut ec_stats as *mut c_void, stream()) },
+            "ec_stats_compute",
+        );
+        Stats::from_ffi(&out)
+    }
+
+    pub fn stats(&self) -> Stats {
+        self.stats_raw(std::ptr::null())
+    }
+
     pub fn new<T: CellEncoding>(data: Vec<T>) -> Self {
         Self::from_host(&data)
     }

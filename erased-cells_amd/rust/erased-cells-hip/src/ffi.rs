@@ -50,6 +50,31 @@ pub struct ec_value {
     pub bits: u64, // the C union; read/written through to_bits()/from_bits() of the primitive
 }
 
+/// Mirrors `ec_moments`: the 64-byte record one `ec_stats_device` launch leaves on the device.  `moments` is the C union:
+/// kind 0 holds `{sum: i64, sq_lo: u64, sq_hi: u64}`, kind 1 the bits of `{pivot, s1, s2}: f64`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct ec_moments {
+    pub count: u64,
+    pub keys2: [i64; 2],
+    pub kind: i32,
+    pub dtype: i32,
+    pub moments: [u64; 3],
+    pub reserved: u64,
+}
+
+/// Mirrors `ec_stats`: what `ec_stats_fold` makes of one or several records.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ec_stats {
+    pub count: u64,
+    pub min: ec_value,
+    pub max: ec_value,
+    pub sum: f64,
+    pub mean: f64,
+    pub stddev: f64,
+}
+
 /// One step of an expression program (`ec_expr`): `reg[dst] = a op b`; `a`, `b` are operand references
 /// (`ec_expr_stream(k)`, `ec_expr_reg(k)`, `ec_expr_scalar(k)`).
 #[repr(C)]
@@ -213,6 +238,15 @@ extern "C" {
                               mx: *mut ec_value) -> ec_status;
     pub fn ec_sharded_counts(g: *mut ec_shard_group, masks: *const *const u8, n: *const usize, n_true: *mut u64,
                              n_false: *mut u64) -> ec_status;
+    // band statistics in one pass (the reference has min_max only, src/buffer.rs:169-173; its NDVI test reads GDAL's
+    // STATISTICS_*, src/gdal/rasterband.rs:151-156); the record pointers are `ec_moments` / `ec_stats`, untyped in the header
+    pub fn ec_stats_device(t: ec_dtype, p: *const c_void, mask_or_null: *const u8, n: usize, moments_dev: *mut c_void,
+                           stream: ec_stream) -> ec_status;
+    pub fn ec_stats_fold(moments_host: *const c_void, n_recs: i32, stats_out: *mut c_void) -> ec_status;
+    pub fn ec_stats_compute(t: ec_dtype, p: *const c_void, mask_or_null: *const u8, n: usize, stats_out: *mut c_void,
+                            stream: ec_stream) -> ec_status;
+    pub fn ec_sharded_stats(g: *mut ec_shard_group, t: ec_dtype, p: *const *const c_void,
+                            masks_or_null: *const *const u8, n: *const usize, stats_out: *mut c_void) -> ec_status;
     pub fn ec_shard_range(n_rows: u64, n_cols: u64, shard: u32, n_shards: u32, cell_offset: *mut u64,
                           cell_len: *mut u64) -> ec_status;
 

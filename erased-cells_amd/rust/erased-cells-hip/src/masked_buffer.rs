@@ -11,7 +11,7 @@
 use crate::device::stream;
 use crate::error::{check, must, Result};
 use crate::ffi::*;
-use crate::{BufferOps, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Mask, NoData, ResampleAlg};
+use crate::{BufferOps, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Mask, NoData, ResampleAlg, Stats};
 use std::fmt::{Debug, Formatter};
 use std::ops::{Add, Div, Mul, Neg, Sub};
 
@@ -65,6 +65,11 @@ impl MaskedCellBuffer {
             )
         })?;
         Ok(MaskedCellBuffer(cells, mask))
+    }
+
+    /// [`CellBuffer::stats`] over the valid cells: a masked-out cell contributes nothing, whatever it holds.
+    pub fn stats(&self) -> Stats {
+        self.0.stats_raw(self.1.dev_ptr())
     }
 
     /// [`CellBuffer::window_resampled`] for the cells and their mask bytes in ONE launch: only the valid cells of a footprint carry

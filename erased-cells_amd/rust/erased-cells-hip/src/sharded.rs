@@ -13,7 +13,7 @@
 use crate::device::stream;
 use crate::error::{check, must, Result};
 use crate::ffi::*;
-use crate::{BufferOps, CellBuffer, CellEncoding, CellType, CellValue};
+use crate::{BufferOps, CellBuffer, CellEncoding, CellType, CellValue, Stats};
 #[cfg(feature = "masked")]
 use crate::Mask;
 use std::os::raw::c_void;
@@ -202,6 +202,22 @@ impl ShardedCellBuffer<'_> {
             ec_sharded_min_max(self.group.g, self.ct as u8, self.const_ptrs().as_ptr(), ptr::null(), self.lens.as_ptr(), &mut mn, &mut mx)
         })?;
         Ok((CellValue::from_ffi(&mn), CellValue::from_ffi(&mx)))
+    }
+
+    /// [`CellBuffer::stats`] of the whole raster: one record per shard, folded on the host in shard order (no collective).
+    /// `mask`: a `UInt8` raster of 0 / 1 bytes cut the same way; a cell counts iff its byte is non-zero.
+    pub fn stats(&self, mask: Option<&Self>) -> Result<Stats> {
+        if let Some(m) = mask {
+            assert_eq!(m.ct, CellType::UInt8, "a mask is UInt8 bytes");
+            assert_eq!(m.lens, self.lens, "the mask must be sharded identically");
+        }
+        let masks: Vec<*const u8> = mask.map_or(Vec::new(), |m| m.ptrs.iter().map(|p| *p as *const u8).collect());
+        let mut out = Stats::blank();
+        check(unsafe {
+            ec_sharded_stats(self.group.g, self.ct as u8, self.const_ptrs().as_ptr(), if mask.is_some() { masks.as_ptr() } else { ptr::null() },
+                             self.lens.as_ptr(), &mut out as *mut ec_stats as *mut c_void)
+        })?;
+        Ok(Stats::from_ffi(&out))
     }
 
     /// Gather the shards back into one host `Vec` (the type must be the buffer's own cell type).

@@ -514,6 +514,73 @@ ec_status ec_window_resample(int32_t alg /* an ec_resample */, ec_dtype t, const
                              void *dst, uint8_t *dst_mask_or_null, ec_stream stream);
 
 /* ---------------------------------------------------------------- *
+ * Band statistics: count, min, max, sum, mean and population standard deviation in one pass over a resident buffer.
+ * The reference has BufferOps::min_max only (src/buffer.rs:169-173; masked: src/masked/masked_buffer.rs:208-217); its own
+ * test of NDVI against GDAL's STATISTICS_MINIMUM / MAXIMUM / MEAN / STDDEV (src/gdal/rasterband.rs:151-156) can therefore
+ * assert two of the four.  These entry points compute all of them where the cells are.
+ * ---------------------------------------------------------------- */
+/* What one launch leaves on the device: 64 bytes.  A cell takes part iff there is no mask or its mask byte is non-zero; a
+ * cell that does not contributes nothing, whatever it holds.
+ *   kind 0 (u8, i8, u16, i16, u32, i32): exact integers, independent of launch shape, shard cut and order.
+ *   kind 1 (u64, i64, f32, f64): cells widened by CellValue::to_f64 (src/value.rs:145-156); pivot c = to_f64(p[0]) if n > 0
+ *          and that is finite, else 0.0 — taken whatever the mask says; every counted cell adds d = x - c to s1 and
+ *          fma(d, d, s2) to s2.  NaN and infinities propagate by IEEE rules.  No float atomics: the same launch twice gives
+ *          the same bits. */
+typedef struct ec_moments {
+    uint64_t count;    /* cells folded: n, or the mask's true cells */
+    int64_t keys2[2];  /* {~key(min), key(max)}, exactly what ec_min_max_keys writes (src/buffer.rs:169-173) */
+    int32_t kind;      /* 0: exact integers   1: pivoted f64 */
+    int32_t dtype;     /* the ec_dtype scanned */
+    union {
+        struct { int64_t sum; uint64_t sq_lo, sq_hi; } i; /* sum of x; sum of x * x as a 128-bit unsigned */
+        struct { double pivot, s1, s2; } f;               /* c; sum of (x - c); sum of (x - c)^2 */
+    } u;
+    uint64_t reserved; /* written as 0 */
+} ec_moments;
+/* min / max as ec_min_max gives them (sentinels (T::MAX, T::MIN) when count == 0); stddev is the population one (divided by
+ * count), which is what GDAL's STATISTICS_STDDEV holds (src/gdal/rasterband.rs:151-156); mean = stddev = NaN, sum = 0 when
+ * count == 0. */
+typedef struct ec_stats {
+    uint64_t count;
+    ec_value min, max;
+    double sum, mean, stddev;
+} ec_stats;
+/* Record pointers cross the ABI as `void *`, as enumerations cross it as int32_t: `moments_dev` / `moments_host` point at
+ * ec_moments, `stats_out` at one ec_stats.
+ *
+ * ec_stats_device — BufferOps::min_max (src/buffer.rs:169-173; masked: src/masked/masked_buffer.rs:208-217) and the moments
+ * of the same cells into the ec_moments at DEVICE address moments_dev.  Asynchronous, no allocation, no synchronisation,
+ * capturable (after ec_prepare_stream for a foreign stream).  n == 0 is legal.  EC_ERR_ARG, before any device work: a null
+ * pointer, or more cells than the exact sums allow — n > 2^32 for 1- and 2-byte cells, n > 2^31 for u32 / i32 (shard it:
+ * these are the bounds under which count * sum(x^2) - sum(x)^2 fits 128 bits in ec_stats_fold). */
+ec_status ec_stats_device(ec_dtype t, const void *p, const uint8_t *mask_or_null, size_t n,
+                          void *moments_dev, ec_stream stream);
+/* Host only, needs no device: folds n_recs ec_moments at HOST address moments_host, left to right, into *stats_out — the
+ * STATISTICS_* figures of src/gdal/rasterband.rs:151-156 over all records' cells; min / max as src/buffer.rs:169-173.
+ * Every step below is one individually rounded f64 operation (no FMA).  Per record with cnt = count > 0:
+ *   kind 0  sum = (double)S1; mean = (double)S1 / (double)cnt; M2 = (double)(cnt * S2 - S1 * S1) / (double)cnt, the
+ *           numerator exact in 128 bits;
+ *   kind 1  q = s1 / (double)cnt; mean = pivot + q; M2 = s2 - s1 * q, set to 0 if negative (not if NaN);
+ *           sum = pivot * (double)cnt + s1.
+ * Records with count == 0 are skipped.  Kind-0 records are first added exactly (count, S1, S2), left to right, while the cells
+ * they cover stay within one record's limit (ec_stats_device) — so a raster cut into shards folds to the very figures of the
+ * raster scanned whole; a run that would pass the limit is closed, enters the merge as one record, and the next begins.
+ * What enters the merge (runs, kind-1 records one by one) merges left to right (Chan et al.): n = nA + nB; delta = meanB - meanA;
+ * mean = meanA + delta * ((double)nB / (double)n); M2 = (M2A + M2B) + (delta * delta) * ((double)nA * (double)nB / (double)n);
+ * sum = sumA + sumB; keys2 by element-wise MAX.  stddev = sqrt(M2 / (double)n).
+ * EC_ERR_ARG: a null pointer, n_recs < 1, records of different dtype, a kind that is not its dtype's. */
+ec_status ec_stats_fold(const void *moments_host, int32_t n_recs, void *stats_out);
+/* ec_stats_device, a 64-byte download, ec_stats_fold: MaskedCellBuffer::min_max (src/masked/masked_buffer.rs:208-217) with
+ * the band statistics of src/gdal/rasterband.rs:151-156 beside it.  Synchronous result. */
+ec_status ec_stats_compute(ec_dtype t, const void *p, const uint8_t *mask_or_null, size_t n,
+                           void *stats_out, ec_stream stream);
+/* The same over a sharded raster (BufferOps::min_max, src/buffer.rs:169-173, of the whole): ec_stats_device per shard, the
+ * records downloaded and folded on the host in shard order.  No collective, so the result is deterministic and needs no
+ * RCCL.  masks_or_null == NULL: unmasked.  Synchronous result. */
+ec_status ec_sharded_stats(ec_shard_group *g, ec_dtype t, const void *const *p,
+                           const uint8_t *const *masks_or_null, const size_t *n, void *stats_out);
+
+/* ---------------------------------------------------------------- *
  * Test/bench support (not part of the reference surface).
  * ---------------------------------------------------------------- */
 /* x[i] = lo + splitmix64(seed ^ (base + i)) % (hi - lo + 1), t in {EC_U8, EC_U16, EC_F32}
