@@ -150,7 +150,9 @@ ec_status ec_stream_sync(ec_stream s);
 /* ---------------------------------------------------------------- *
  * Element-wise arithmetic.  out[i] = f64(l[i]) op f64(r[i]), always Float64
  * (src/value.rs:199-217).  `n` = min(len l, len r): the caller applies the zip
- * truncation of src/buffer.rs:327.  n == 0 is a no-op.
+ * truncation of src/buffer.rs:327.  n == 0 is a no-op.  Every element-wise entry point of this header writes exactly
+ * `n` cells of each of its outputs and no byte in front of or behind them, wherever the output sits (any cell offset:
+ * an f64 output at 8 mod 16, a mask at any byte); operands are not written (tests/test_gpu_output_bounds.py).
  * ---------------------------------------------------------------- */
 /* impl {Add,Sub,Mul,Div} for &CellBuffer — src/buffer.rs:324-329 */
 ec_status ec_binop(ec_op op, ec_dtype lt, const void *l, ec_dtype rt, const void *r,
