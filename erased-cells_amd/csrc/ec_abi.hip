@@ -12,46 +12,17 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
-#include <mutex>
 #include <string>
 
 #include "ec_lattice.hpp"
 #include "ec_map_kernels.hpp"
 #include "ec_reduce_kernels.hpp"
+#include "ec_reduce_launch.hpp"
 #include "ec_runtime.hpp"
 
 namespace ecd {
 
 static_assert(kMaxReduceBlocks <= kFinalizeMaxParts, "the finalize kernels read at most kFinalizeMaxParts partials");
-
-static ec_status ensure_init() { return ensure_ready(); }
-
-// Where the last kernel of a synchronous-result call writes its 1-2 result words: the stream's pinned host words as the
-// device sees them (zero-copy: the result is on the host when the stream has drained), or device scratch when the
-// mapping is unavailable.  fetch_result waits for the stream (and copies first in the fallback case).
-static int64_t* result_words(const Scratch& sc) { return sc.host_dev ? sc.host_dev : sc.dev_result(); }
-static ec_status fetch_result(const Scratch& sc, int words, hipStream_t s) {
-    if (!sc.host_dev) {
-        ec_status st = check_hip(hipMemcpyAsync(sc.host, sc.dev_result(), words * sizeof(int64_t), hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-        if (st != EC_OK) return st;
-    }
-    // (Polling the stream with hipStreamQuery before blocking was tried for the 5 µs kernels of fixture-sized rasters: 19.5 µs per ec_min_max
-    // call against 15.1 µs — hipStreamSynchronize's own wait is the faster one; profiles/r04/sync_result_latency.txt.)
-    return check_hip(hipStreamSynchronize(s), "hipStreamSynchronize");
-}
-// The synchronous-result prologue of ec_min_max, ec_first_difference and ec_mask_counts: takes the stream's turn at its result
-// words, has `run(sc, words)` queue the kernels whose last one writes `nwords` words there, waits, and leaves them in `host`.
-template <typename Run>
-static ec_status sync_result(hipStream_t s, int nwords, int64_t (&host)[2], Run run) {
-    Scratch sc;
-    ec_status st = get_scratch(s, &sc);
-    if (st != EC_OK) return st;
-    std::lock_guard<std::mutex> turn(*sc.mu);  // the pinned result words are per stream: host threads sharing it take turns
-    st = run(sc, result_words(sc));            // the last kernel writes the pinned words
-    if (st == EC_OK) st = fetch_result(sc, nwords, s);
-    if (st == EC_OK) std::memcpy(host, sc.host, nwords * sizeof(int64_t));
-    return st;
-}
 
 // first difference and mask counts: the default shape, its cell-wise branch inside the same kernel
 constexpr ReduceShape kScanShape = {kRBlock, kReduceU, 4, kRBlock, 4};
@@ -124,53 +95,31 @@ static ec_status dispatch_convert(int st, const void* src, int dt, void* dst, si
 
 // ------------------------------------------------------------------ min/max
 template <typename T>
-static ec_status launch_min_max(const void* p, const uint8_t* mask, size_t n, int64_t* keys2_dev, hipStream_t s) {
-    Scratch sc;
-    ec_status st = get_scratch(s, &sc);
-    if (st != EC_OK) return st;
-    const T* tp = static_cast<const T*>(p);
-    unsigned grid = 0;
-    if (n > 0) {
-        const size_t stream_bytes[2] = {n * sizeof(T), mask ? n : 0};
-        // launch shape: 512 threads x 8 loads in flight by default; "reduce_shape" selects the A/B alternatives
-        auto launch = [&](auto u_tag, auto block_tag, int per_cu) {
-            constexpr int U = decltype(u_tag)::value, BLOCK = decltype(block_tag)::value;
-            // as many workgroups per CU as are resident at once (the masked kernels of some types need more than
-            // 64 VGPRs and fit 3, not 4, of these workgroups on a CU): the grid then runs as ONE round.  (Probed once per type and
-            // shape, also when the plan then picks the cell-wise kernel — "unaligned_vector" off — which has no use for the answer.)
-            static const int resident[2] = {resident_per_cu(k_min_max_partials<T, false, U, BLOCK>, BLOCK, per_cu),
-                                            resident_per_cu(k_min_max_partials<T, true, U, BLOCK>, BLOCK, per_cu)};
-            const ReduceShape shape = {BLOCK, U, resident[mask ? 1 : 0], kBlock, 8};  // the cell-wise kernel: 256-thread workgroups
-            const ReducePlan pl = plan_reduction(p, mask ? residue(mask, 16 / sizeof(T)) : 0u, sizeof(T), n, shape, stream_bytes, 2);
-            grid = pl.grid;
-            int64_t* direct = pl.aligned && pl.single ? keys2_dev : nullptr;  // one workgroup: it writes the result itself
-            if (!pl.aligned) {
-                if (mask) k_min_max_partials_cellwise<T, true><<<grid, kBlock, 0, s>>>(tp, mask, n, sc.dev);
-                else k_min_max_partials_cellwise<T, false><<<grid, kBlock, 0, s>>>(tp, nullptr, n, sc.dev);
-            } else if (mask) {
-                k_min_max_partials<T, true, U, BLOCK><<<grid, BLOCK, 0, s>>>(tp, mask, n, sc.dev, pl.head_policy, direct);
-            } else {
-                k_min_max_partials<T, false, U, BLOCK><<<grid, BLOCK, 0, s>>>(tp, nullptr, n, sc.dev, pl.head_policy, direct);
-            }
-            return direct != nullptr;
-        };
-        using std::integral_constant;
-        bool direct = false;
-        switch (tuning().reduce_shape) {
-            case 1: direct = launch(integral_constant<int, 16>{}, integral_constant<int, 512>{}, 4); break;
-            case 2: direct = launch(integral_constant<int, 8>{}, integral_constant<int, 256>{}, 8); break;
-            case 3: direct = launch(integral_constant<int, 8>{}, integral_constant<int, 1024>{}, 2); break;
-            case 4: direct = launch(integral_constant<int, 4>{}, integral_constant<int, 512>{}, 4); break;
-            default: direct = launch(integral_constant<int, kReduceU>{}, integral_constant<int, kRBlock>{}, 4); break;
-        }
-        if (direct) return check_launch("min_max(single workgroup)");
-        st = check_launch("min_max(partials)");
-        if (st != EC_OK) return st;
+struct MinMaxReduction {
+    using Cell = T;
+    using Partial = int64_t;  // partials[2 * b], [2 * b + 1]: workgroup b's key pair
+    using Out = int64_t;      // {~key(min), key(max)}
+    static constexpr ScratchSlot kPartials = kScratchPartials;
+    static constexpr const char *kSingle = "min_max(single workgroup)", *kPartialsName = "min_max(partials)", *kFinalizeName = "min_max(finalize)";
+    template <bool MASKED, int U, int BLOCK> static auto vector_kernel() { return k_min_max_partials<T, MASKED, U, BLOCK>; }
+    template <bool MASKED> static auto cellwise_kernel() { return k_min_max_partials_cellwise<T, MASKED>; }
+    static void finalize(const int64_t* partials, int nparts, const T*, int64_t* keys2_dev, hipStream_t s) {
+        // sentinels (T::MAX, T::MIN): src/buffer.rs:170, finite for floats (src/ctype.rs:158-179)
+        k_min_max_finalize<<<1, kFinalizeBlock, 0, s>>>(partials, nparts, order_key<T>(Limits<T>::hi), order_key<T>(Limits<T>::lo), keys2_dev);
     }
-    // sentinels (T::MAX, T::MIN): src/buffer.rs:170, finite for floats (src/ctype.rs:158-179)
-    k_min_max_finalize<<<1, kFinalizeBlock, 0, s>>>(sc.dev, static_cast<int>(grid), order_key<T>(Limits<T>::hi),
-                                            order_key<T>(Limits<T>::lo), keys2_dev);
-    return check_launch("min_max(finalize)");
+};
+
+template <typename T>
+static ec_status launch_min_max(const void* p, const uint8_t* mask, size_t n, int64_t* keys2_dev, hipStream_t s) {
+    using R = MinMaxReduction<T>;
+    // launch shape: 512 threads x 8 loads in flight, 4 workgroups per CU by default; "reduce_shape" selects the A/B alternatives
+    switch (tuning().reduce_shape) {
+        case 1: return launch_reduction<R, 16, 512, 4>(p, mask, n, keys2_dev, s);
+        case 2: return launch_reduction<R, 8, 256, 8>(p, mask, n, keys2_dev, s);
+        case 3: return launch_reduction<R, 8, 1024, 2>(p, mask, n, keys2_dev, s);
+        case 4: return launch_reduction<R, 4, 512, 4>(p, mask, n, keys2_dev, s);
+        default: return launch_reduction<R, kReduceU, kRBlock, 4>(p, mask, n, keys2_dev, s);
+    }
 }
 
 static ec_status dispatch_min_max(int t, const void* p, const uint8_t* mask, size_t n, int64_t* keys2_dev, hipStream_t s) {
@@ -289,7 +238,7 @@ extern "C" ec_status ec_shard_range(uint64_t n_rows, uint64_t n_cols, uint32_t s
 // =================================================================== arithmetic
 #define EC_REQUIRE_INIT()               \
     do {                                \
-        ec_status st_ = ensure_init();  \
+        ec_status st_ = ensure_ready();  \
         if (st_ != EC_OK) return st_;   \
     } while (0)
 
@@ -404,7 +353,7 @@ extern "C" ec_status ec_min_max(ec_dtype t, const void* p, const uint8_t* mask_o
     EC_REQUIRE_INIT();
     if (!mn || !mx || (n > 0 && !p)) return set_error(EC_ERR_ARG, "ec_min_max: null pointer");
     int64_t keys2[2];
-    ec_status st = sync_result(S(stream), 2, keys2, [&](const Scratch&, int64_t* words) {
+    ec_status st = sync_result(S(stream), kResultWords, keys2, sizeof keys2, [&](const Scratch&, int64_t* words) {
         return dispatch_min_max(t, p, mask_or_null, n, words, S(stream));
     });
     if (st != EC_OK) return st;
@@ -417,7 +366,7 @@ static ec_status first_diff_w(const void* l, const void* r, size_t n, const Scra
     const size_t stream_bytes[2] = {n * sizeof(W), n * sizeof(W)};
     const ReducePlan pl = plan_reduction(l, residue(r, 16), sizeof(W), n, kScanShape, stream_bytes, 2);
     k_first_diff_partials<W, kReduceU><<<pl.grid, kRBlock, 0, s>>>(static_cast<const W*>(l), static_cast<const W*>(r), n,
-                                                                  reinterpret_cast<uint64_t*>(sc.dev), pl.aligned, pl.head_policy);
+                                                                  reinterpret_cast<uint64_t*>(sc.at(kScratchPartials)), pl.aligned, pl.head_policy);
     *grid_out = pl.grid;
     return check_launch("first_diff(partials)");
 }
@@ -428,8 +377,8 @@ extern "C" ec_status ec_first_difference(ec_dtype t, const void* l, const void* 
     if (!index || (n > 0 && (!l || !r))) return set_error(EC_ERR_ARG, "ec_first_difference: null pointer");
     *index = n;
     if (n == 0) return EC_OK;
-    int64_t word[2];
-    ec_status st = sync_result(S(stream), 1, word, [&](const Scratch& sc, int64_t* words) {
+    uint64_t first = 0;
+    ec_status st = sync_result(S(stream), kResultWords, &first, sizeof first, [&](const Scratch& sc, int64_t* words) {
         unsigned grid = 0;
         ec_status st2;
         switch (ecl::size_of(t)) {
@@ -439,12 +388,11 @@ extern "C" ec_status ec_first_difference(ec_dtype t, const void* l, const void* 
             default: st2 = first_diff_w<uint64_t>(l, r, n, sc, S(stream), &grid); break;
         }
         if (st2 != EC_OK) return st2;
-        k_first_diff_finalize<<<1, kFinalizeBlock, 0, S(stream)>>>(reinterpret_cast<const uint64_t*>(sc.dev), static_cast<int>(grid),
+        k_first_diff_finalize<<<1, kFinalizeBlock, 0, S(stream)>>>(reinterpret_cast<const uint64_t*>(sc.at(kScratchPartials)), static_cast<int>(grid),
                                                            reinterpret_cast<uint64_t*>(words));
         return check_launch("first_diff(finalize)");
     });
     if (st != EC_OK) return st;
-    const uint64_t first = static_cast<uint64_t>(word[0]);
     *index = first == ~0ull ? n : first;
     return EC_OK;
 }
@@ -572,26 +520,26 @@ extern "C" ec_status ec_mask_counts_device(const uint8_t* m, size_t n, uint64_t*
         // every workgroup is still streaming a gigabyte.  Big masks keep the finalize launch, which they do not feel (2 %); knob
         // `counts_one_launch`: 0 never, 1 (default) below 2^29 cells, 2 always (below 2^40: ticket and sum share a 64-bit word).
         const int one = tuning().counts_one_launch.load();
-        uint64_t* acc = (!direct && ((one == 1 && n < (size_t(1) << 29)) || (one >= 2 && n < (size_t(1) << 40)))) ? reinterpret_cast<uint64_t*>(sc.dev_acc()) : nullptr;
-        k_mask_count_partials<kReduceU><<<grid, kRBlock, 0, S(stream)>>>(m, n, reinterpret_cast<uint64_t*>(sc.dev), pl.aligned, pl.head_policy,
+        uint64_t* acc = (!direct && ((one == 1 && n < (size_t(1) << 29)) || (one >= 2 && n < (size_t(1) << 40)))) ? reinterpret_cast<uint64_t*>(sc.at(kScratchAcc)) : nullptr;
+        k_mask_count_partials<kReduceU><<<grid, kRBlock, 0, S(stream)>>>(m, n, reinterpret_cast<uint64_t*>(sc.at(kScratchPartials)), pl.aligned, pl.head_policy,
                                                                         direct, acc, counts2_dev);
         st = check_launch("mask_counts(partials)");
         if (st != EC_OK || direct || acc) return st;
     }
-    k_mask_count_finalize<<<1, kFinalizeBlock, 0, S(stream)>>>(reinterpret_cast<const uint64_t*>(sc.dev), static_cast<int>(grid), n, counts2_dev);
+    k_mask_count_finalize<<<1, kFinalizeBlock, 0, S(stream)>>>(reinterpret_cast<const uint64_t*>(sc.at(kScratchPartials)), static_cast<int>(grid), n, counts2_dev);
     return check_launch("mask_counts(finalize)");
 }
 
 extern "C" ec_status ec_mask_counts(const uint8_t* m, size_t n, uint64_t* n_true, uint64_t* n_false, ec_stream stream) {
     EC_REQUIRE_INIT();
     if (!n_true || !n_false) return set_error(EC_ERR_ARG, "ec_mask_counts: null pointer");
-    int64_t counts2[2];
-    ec_status st = sync_result(S(stream), 2, counts2, [&](const Scratch&, int64_t* words) {
+    uint64_t counts2[2];
+    ec_status st = sync_result(S(stream), kResultWords, counts2, sizeof counts2, [&](const Scratch&, int64_t* words) {
         return ec_mask_counts_device(m, n, reinterpret_cast<uint64_t*>(words), stream);
     });
     if (st != EC_OK) return st;
-    *n_true = static_cast<uint64_t>(counts2[0]);
-    *n_false = static_cast<uint64_t>(counts2[1]);
+    *n_true = counts2[0];
+    *n_false = counts2[1];
     return EC_OK;
 }
 

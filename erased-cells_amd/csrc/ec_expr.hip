@@ -7,13 +7,13 @@
 #include <cstring>
 
 #include <limits>
-#include <mutex>
 #include <string>
 
 #include "ec_expr.hpp"
 #include "ec_expr_fixed.hpp"
 #include "ec_expr_jit.hpp"
 #include "ec_lattice.hpp"
+#include "ec_reduce_launch.hpp"
 #include "ec_runtime.hpp"
 
 using namespace ecd;
@@ -241,19 +241,14 @@ extern "C" ec_status ec_expr_min_max(const ec_dtype* dt, const void* const* p, c
     if (st != EC_OK) return st;
     if (!mn || !mx) return set_error(EC_ERR_ARG, "ec_expr_min_max: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // the two key words live in the stream's reduction scratch, after the words ec_min_max_keys itself uses.  (Not a 16-byte
+    // the two key words live in the stream's reduction scratch, in a slot of their own beside the words ec_min_max_keys itself
+    // uses (kScratchExprKeys).  (Not a 16-byte
     // block from the pool: hipMallocAsync carves such a block out of the 2 GiB one the two-pass form has just returned, and the
     // next 2 GiB request becomes a fresh 130 ms allocation — profiles/r03/expr_kernel.md.)
-    Scratch sc;
-    if ((st = get_scratch(s, &sc)) != EC_OK) return st;
     int64_t keys[2];
-    {
-        std::lock_guard<std::mutex> turn(*sc.mu);
-        int64_t* dkeys = sc.dev_result() + 2;
-        st = expr_min_max_keys(dt, p, masks_or_null, n_streams, scalars, n_scalars, steps, n_steps, n, dkeys, s, "ec_expr_min_max");
-        if (st == EC_OK) st = check_hip(hipMemcpyAsync(keys, dkeys, sizeof keys, hipMemcpyDeviceToHost, s), "hipMemcpyAsync(keys)");
-        if (st == EC_OK) st = check_hip(hipStreamSynchronize(s), "hipStreamSynchronize");  // `keys` is this frame's: nothing may be in flight on return
-    }
+    st = sync_result(s, kResultExprKeys, keys, sizeof keys, [&](const Scratch&, int64_t* dkeys) {
+        return expr_min_max_keys(dt, p, masks_or_null, n_streams, scalars, n_scalars, steps, n_steps, n, dkeys, s, "ec_expr_min_max");
+    });
     if (st != EC_OK) return st;
     return ec_min_max_decode(EC_F64, keys, mn, mx);
 }

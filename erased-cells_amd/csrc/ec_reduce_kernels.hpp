@@ -10,6 +10,8 @@
 // (packed 16-bit min/max for u16/i16).  Each of the three partials kernels keeps its own scan (head | policy word, peeled
 // head cells, grid-stride tile loop, tail cells): one shared scan frame was tried and cost two min/max kernels a
 // waves-per-SIMD step (profiles/r08/reduce_frame.md).  What they share, written once below:
+//   MinMaxLanes   a lane's {min, max} accumulators: the sentinels, the fold of a 16-byte group under its mask bytes (ByteFold
+//                 for 1-byte cells), the horizontal fold, the fold of one cell — min/max's and the stats kernels'.
 //   block_fold    a wavefront shuffle-reduce (DPP/ds_bpermute via __shfl_xor, 6 steps), then the waves of the block
 //                 combine through one LDS word (or {min, max} pair) per wave behind ONE barrier; thread 0 holds the result
 //                 and writes the block's partial.
@@ -17,7 +19,8 @@
 //                 min/max the two order-preserving int64 keys {~key(min), key(max)}, the form a MAX all-reduce over
 //                 shards needs.
 // No atomics in min/max and first difference, so the result is deterministic and needs no zero-initialised memory (the
-// one-launch form of the counts adds integers: order-free).  What the host decides per launch: ec_reduce_plan.hpp.
+// one-launch form of the counts adds integers: order-free).  What the host decides per launch: ec_reduce_plan.hpp; the launch
+// sequence and the hand-over of a result: ec_reduce_launch.hpp.
 #pragma once
 
 #include <type_traits>
@@ -166,6 +169,68 @@ struct ByteFold {
     }
 };
 
+// One lane's running {min, max}, as acc keys: the reference's fold from the sentinels (T::MAX, T::MIN) in total_cmp order, written
+// once for the min/max and the stats kernels.  The vector kernels fold 16-byte groups into one accumulator pair per slot of the
+// group (ByteFold for 1-byte cells) and finish() folds the slots into the lane's pair; single cells — the head and tail cells of
+// workgroup 0, the cell-wise kernels — go into that pair directly, and a cell the mask hides is the caller's to skip.
+template <typename T, bool MASKED>
+struct MinMaxLanes {
+    using A = typename AccT<T>::type;
+    static constexpr int CPL = 16 / sizeof(T);
+    static constexpr bool BYTES = sizeof(T) == 1;
+    vec<A, CPL> vmin, vmax;
+    ByteFold<typename std::conditional<BYTES, T, uint8_t>::type> bf;
+    A amin, amax;
+
+    __device__ __forceinline__ void init() {
+        amin = acc_key<T>(Limits<T>::hi);
+        amax = acc_key<T>(Limits<T>::lo);
+#pragma unroll
+        for (int k = 0; k < CPL; ++k) { vmin[k] = amin; vmax[k] = amax; }
+        bf.init();
+    }
+    // 1-byte cells and the mask bytes travel as words (ec_device.hpp cells<>); a hidden cell folds as the sentinels
+    __device__ __forceinline__ void fold_group(const cells<T, CPL>& x, const cells<uint8_t, CPL>& m) {
+        if constexpr (BYTES) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) bf.template fold<MASKED>(x.v[k], m.v[k]);
+        } else {
+            const A hi0 = acc_key<T>(Limits<T>::hi), lo0 = acc_key<T>(Limits<T>::lo);
+#pragma unroll
+            for (int k = 0; k < CPL; ++k) {
+                A key = acc_key<T>(x[k]);
+                A kmin = key, kmax = key;
+                if constexpr (MASKED) {
+                    kmin = m[k] ? key : hi0;
+                    kmax = m[k] ? key : lo0;
+                }
+                vmin[k] = kmin < vmin[k] ? kmin : vmin[k];
+                vmax[k] = kmax > vmax[k] ? kmax : vmax[k];
+            }
+        }
+    }
+    // the horizontal fold of the slots: after the last group, before the first single cell
+    __device__ __forceinline__ void finish() {
+        amin = vmin[0];
+        amax = vmax[0];
+        if constexpr (BYTES) {
+            amin = bf.result_min();
+            amax = bf.result_max();
+        } else {
+#pragma unroll
+            for (int k = 1; k < CPL; ++k) {
+                amin = vmin[k] < amin ? vmin[k] : amin;
+                amax = vmax[k] > amax ? vmax[k] : amax;
+            }
+        }
+    }
+    __device__ __forceinline__ void fold_cell(T v) {
+        const A key = acc_key<T>(v);
+        amin = key < amin ? key : amin;
+        amax = key > amax ? key : amax;
+    }
+};
+
 // Launch shape of the reductions (tools/tune_reduce.hip, profiles/r02/tune_reduce.log): 512-thread workgroups with
 // 8 x 16 B in flight per lane and a grid capped at 4 workgroups per CU read a 16384² byte mask in 41.4 µs including
 // the finalize launch (0.81 of 8 TB/s); round 1's 256 threads x 4 loads x 8/CU took 43.3 µs, one tile per workgroup
@@ -191,37 +256,14 @@ __global__ __launch_bounds__(BLOCK) void k_min_max_partials(const T* __restrict_
     using A = typename AccT<T>::type;
     constexpr int CPL = 16 / sizeof(T);
     using TV = cells<T, CPL>;        // 1-byte cells and the mask bytes travel as words: their loads keep `nt` (ec_device.hpp)
-    using AV = vec<A, CPL>;
     using MV = cells<uint8_t, CPL>;
-    constexpr bool BYTES = sizeof(T) == 1;
-    const A hi0 = acc_key<T>(Limits<T>::hi), lo0 = acc_key<T>(Limits<T>::lo);
-    AV vmin, vmax;
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) { vmin[k] = hi0; vmax[k] = lo0; }
-    ByteFold<typename std::conditional<BYTES, T, uint8_t>::type> bf;
-    bf.init();
+    MinMaxLanes<T, MASKED> mm;
+    mm.init();
 
     const size_t ngroups = n / CPL;
     constexpr size_t TILE = size_t(BLOCK) * U;
     const size_t ntiles = (ngroups + TILE - 1) / TILE;
-    auto fold = [&](const TV& x, const MV& m) {
-        if constexpr (BYTES) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) bf.template fold<MASKED>(x.v[k], m.v[k]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < CPL; ++k) {
-                A key = acc_key<T>(x[k]);
-                A kmin = key, kmax = key;
-                if constexpr (MASKED) {
-                    kmin = m[k] ? key : hi0;
-                    kmax = m[k] ? key : lo0;
-                }
-                vmin[k] = kmin < vmin[k] ? kmin : vmin[k];
-                vmax[k] = kmax > vmax[k] ? kmax : vmax[k];
-            }
-        }
-    };
+    auto fold = [&](const TV& x, const MV& m) { mm.fold_group(x, m); };
 
     for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const size_t base = tile * TILE + threadIdx.x;
@@ -251,28 +293,16 @@ __global__ __launch_bounds__(BLOCK) void k_min_max_partials(const T* __restrict_
         }
     }
     // horizontal fold of the lane's accumulators, then the ragged tail cells
-    A amin = vmin[0], amax = vmax[0];
-    if constexpr (BYTES) {
-        amin = bf.result_min();
-        amax = bf.result_max();
-    } else {
-#pragma unroll
-        for (int k = 1; k < CPL; ++k) {
-            amin = vmin[k] < amin ? vmin[k] : amin;
-            amax = vmax[k] > amax ? vmax[k] : amax;
-        }
-    }
+    mm.finish();
     if (blockIdx.x == 0) {
         auto fold_cell = [&](ptrdiff_t i) {
             if (MASKED && !ld_cell(mask + i)) return;
-            A key = acc_key<T>(ld_cell(p + i));
-            amin = key < amin ? key : amin;
-            amax = key > amax ? key : amax;
+            mm.fold_cell(ld_cell(p + i));
         };
         for (size_t i = ngroups * CPL + threadIdx.x; i < n; i += BLOCK) fold_cell(static_cast<ptrdiff_t>(i));
         for (unsigned h = threadIdx.x; h < head; h += BLOCK) fold_cell(-static_cast<ptrdiff_t>(h) - 1);  // the peeled cells
     }
-    K2 k = {acc_to_i64<A>(amin), acc_to_i64<A>(amax)};
+    K2 k = {acc_to_i64<A>(mm.amin), acc_to_i64<A>(mm.amax)};
     if (block_fold<BLOCK>(k, FoldMinMax{})) {
         if (keys2_if_single) {
             keys2_if_single[0] = ~k.x;
@@ -289,15 +319,14 @@ template <typename T, bool MASKED>
 __global__ __launch_bounds__(kBlock) void k_min_max_partials_cellwise(const T* __restrict__ p, const uint8_t* __restrict__ mask,
                                                                       size_t n, int64_t* __restrict__ partials) {
     using A = typename AccT<T>::type;
-    A amin = acc_key<T>(Limits<T>::hi), amax = acc_key<T>(Limits<T>::lo);
+    MinMaxLanes<T, MASKED> mm;
+    mm.init();
     const size_t stride = size_t(gridDim.x) * kBlock;
     for (size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
         if (MASKED && !mask[i]) continue;
-        A key = acc_key<T>(p[i]);
-        amin = key < amin ? key : amin;
-        amax = key > amax ? key : amax;
+        mm.fold_cell(p[i]);
     }
-    K2 k = {acc_to_i64<A>(amin), acc_to_i64<A>(amax)};
+    K2 k = {acc_to_i64<A>(mm.amin), acc_to_i64<A>(mm.amax)};
     if (block_fold<kBlock>(k, FoldMinMax{})) {
         partials[2 * size_t(blockIdx.x)] = k.x;
         partials[2 * size_t(blockIdx.x) + 1] = k.y;

@@ -1,9 +1,10 @@
 // ec_reduce_plan.hpp — what the host decides for one launch of a reduction (ec_reduce_kernels.hpp), in plain C++: nothing from
 // HIP or from this library, so that host/test_reduce_plan.cpp can hold it against the launchers' formulas it replaced.
 //
-// The launchers of ec_abi.hip (min/max, first difference, mask counts) pass what they know — where the streams start, the
-// cell size and count, the launch shape, the device's CU count, the knobs, the load policy of cache_plan() — and keep what is
-// theirs: the kernel per shape, the residency probe, the one-launch rule of the counts, the finalize launch.
+// The launchers — launch_reduction (ec_reduce_launch.hpp) for min/max and the band statistics, first_diff_w and
+// ec_mask_counts_device (ec_abi.hip) — pass what they know — where the streams start, the cell size and count, the launch
+// shape, the device's CU count, the knobs, the load policy of cache_plan() — and keep what is theirs: the kernel per shape, the
+// residency probe, the one-launch rule of the counts, the finalize launch.
 #pragma once
 
 #include <stddef.h>

@@ -219,8 +219,9 @@ ec_status get_scratch(hipStream_t s, Scratch* out) {
         ec_status st = check_hip(hipMalloc(reinterpret_cast<void**>(&own->dev), kScratchWords * sizeof(int64_t)),
                                  "hipMalloc(scratch)");
         if (st != EC_OK) return st;
-        // the accumulator words (Scratch::dev_acc) start at zero; every kernel that uses one leaves it at zero again
-        st = check_hip(hipMemset(own->dev + 2 * kMaxReduceBlocks, 0, 8 * sizeof(int64_t)), "hipMemset(scratch)");
+        // the accumulator words (kScratchAcc) start at zero, the result words before them too; every kernel that uses an
+        // accumulator leaves it at zero again
+        st = check_hip(hipMemset(own->dev + kScratchResult.word, 0, (kScratchAcc.end() - kScratchResult.word) * sizeof(int64_t)), "hipMemset(scratch)");
         if (st != EC_OK) return st;
         st = check_hip(hipHostMalloc(reinterpret_cast<void**>(&own->host), 4 * sizeof(int64_t), hipHostMallocDefault),
                        "hipHostMalloc(scratch)");
@@ -232,7 +233,7 @@ ec_status get_scratch(hipStream_t s, Scratch* out) {
         void* as_device = nullptr;
         static const bool no_zero_copy = std::getenv("EC_NO_ZERO_COPY_RESULTS") != nullptr;  // A/B switch
         if (!no_zero_copy && hipHostGetDevicePointer(&as_device, e.sc.host, 0) == hipSuccess && as_device) e.sc.host_dev = static_cast<int64_t*>(as_device);
-        else (void)hipGetLastError();  // host_dev stays null: results go through dev_result() and a copy
+        else (void)hipGetLastError();  // host_dev stays null: results go through kScratchResult and a copy
         e.sc.owner = std::move(own);
         it = table.emplace(s, e).first;
     }

@@ -207,28 +207,36 @@ inline unsigned grid_capped(size_t blocks, int bpc) {
 }
 
 // Per-(device, stream) scratch for reduction partials (device) and results (pinned host).  Launches that use the
-// partials are ordered by the stream itself; `mu` serialises the synchronous-result entry points (ec_min_max,
-// ec_mask_counts, ec_first_difference), which read `host` after waiting for the stream — two host threads sharing
-// one stream therefore take turns instead of racing on the four pinned words.
+// partials are ordered by the stream itself; `mu` serialises the synchronous-result entry points (sync_result,
+// ec_reduce_launch.hpp), which read a result slot after waiting for the stream — two host threads sharing one stream
+// therefore take turns instead of racing on it.
+//
+// The layout of Scratch::dev, in 64-bit words: every slot is named here and nowhere else.
 constexpr int kStatsRecordWords = 8;  // one ec_moments (64 bytes); a Moments partial (ec_reduce_kernels.hpp) is no larger
+struct ScratchSlot { size_t word, words; constexpr size_t end() const { return word + words; } };  // first word, length
+constexpr ScratchSlot kScratchPartials = {0, 2 * size_t(kMaxReduceBlocks)};    // min/max: a key pair per workgroup; first difference, counts: a word
+constexpr ScratchSlot kScratchResult = {kScratchPartials.end(), 2};           // min/max, counts, first difference without the pinned mapping
+constexpr ScratchSlot kScratchExprKeys = {kScratchResult.end(), 2};           // ec_expr_min_max's key pair
+constexpr ScratchSlot kScratchAcc = {kScratchExprKeys.end(), 4};              // the one-launch counts' accumulator word (zero between kernels)
+constexpr ScratchSlot kScratchStatsPartials = {kScratchAcc.end(), size_t(kStatsRecordWords) * kMaxReduceBlocks};  // a Moments per workgroup
+constexpr ScratchSlot kScratchStatsRecord = {kScratchStatsPartials.end(), kStatsRecordWords};                     // ec_stats_compute's record
+constexpr size_t kScratchWords = kScratchStatsRecord.end();
+static_assert(kScratchPartials.end() <= kScratchResult.word && kScratchResult.end() <= kScratchExprKeys.word && kScratchExprKeys.end() <= kScratchAcc.word &&
+              kScratchAcc.end() <= kScratchStatsPartials.word && kScratchStatsPartials.end() <= kScratchStatsRecord.word, "two slots of the stream's scratch overlap");
+static_assert(kScratchStatsPartials.word % 8 == 0 && kScratchStatsRecord.word % 8 == 0, "the stats area is 64-byte aligned: hipMalloc's alignment + whole 64-byte lines");
 struct ScratchOwner;  // frees the three allocations when the last Scratch copy that names them is gone (ec_runtime.hip)
 struct Scratch {
     std::shared_ptr<ScratchOwner> owner;  // every copy handed out by get_scratch() shares ownership: releasing or recycling a
                                           // stream's entry only drops the TABLE's reference, so a host thread that is
-                                          // inside ec_min_max / ec_mask_counts / ec_first_difference with this scratch
-                                          // (its `mu` locked, its kernels queued) keeps valid memory until it returns
-    int64_t* dev = nullptr;    // 2*kMaxReduceBlocks partials + 4 result words + 4 accumulator words (zero between kernels), then
-                               // kMaxReduceBlocks + 1 records of kStatsRecordWords words: the stats kernels' partials and ec_stats_compute's record
-    int64_t* host = nullptr;   // 4 words, pinned (coherent): the synchronous-result entry points let the last kernel write
-                               // its result straight into them — no device-to-host copy is queued behind the kernel
+                                          // inside a synchronous-result call with this scratch (its `mu` locked, its
+                                          // kernels queued) keeps valid memory until it returns
+    int64_t* dev = nullptr;    // kScratchWords words, laid out as above
+    int64_t* host = nullptr;   // 4 words, pinned (coherent): the calls whose result is one or two words let the last kernel
+                               // write it straight into them — no device-to-host copy is queued behind the kernel
     int64_t* host_dev = nullptr;  // the same words as the device addresses them
     std::mutex* mu = nullptr;
-    int64_t* dev_result() const { return dev + 2 * kMaxReduceBlocks; }
-    int64_t* dev_acc() const { return dev + 2 * kMaxReduceBlocks + 4; }
-    int64_t* dev_stats() const { return dev + 2 * kMaxReduceBlocks + 8; }  // 64-byte aligned: hipMalloc's alignment + 64 * 1025 bytes
-    int64_t* dev_stats_record() const { return dev_stats() + size_t(kStatsRecordWords) * kMaxReduceBlocks; }
+    int64_t* at(const ScratchSlot& slot) const { return dev + slot.word; }
 };
-constexpr size_t kScratchWords = 2 * kMaxReduceBlocks + 8 + size_t(kStatsRecordWords) * (kMaxReduceBlocks + 1);
 ec_status get_scratch(hipStream_t s, Scratch* out);
 
 // Workgroups of `kernel` (BLOCK threads, no dynamic LDS) that fit on one CU at a time, at most `want`.
@@ -250,6 +258,10 @@ inline ReducePlan plan_reduction(const void* p0, unsigned residue1, size_t cell_
     return reduce_plan(residue(p0, 16), residue1, cell_size, n, shape, device_cus(), tuning().reduce_bpc, tuning().unaligned_vector != 0,
                        cache_plan(stream_bytes, nstreams));
 }
+
+// The cells one exact stats record may cover (stats_max_cells, ec_stats_fold.hpp), checked for a whole buffer (shard < 0) or
+// for shard `shard` of a group; `advice` closes the refusal's text.  ec_stats.hip.
+ec_status check_stats_cells(const char* who, int shard, int t, size_t n, const char* advice);
 
 // binary arithmetic, one translation unit per op
 template <int OP>

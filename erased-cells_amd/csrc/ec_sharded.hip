@@ -44,7 +44,6 @@
 #include "ec_hostpipe.hpp"
 #include "ec_lattice.hpp"
 #include "ec_runtime.hpp"
-#include "ec_stats_fold.hpp"
 #include "ec_worker.hpp"
 
 using namespace ecd;
@@ -714,11 +713,8 @@ extern "C" ec_status ec_sharded_stats(ec_shard_group* g, ec_dtype t, const void*
     if (!ecl::valid(t)) return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_sharded_stats: bad dtype");
     if ((st = check_col(g, "ec_sharded_stats", "p", p, n)) != EC_OK) return st;
     if (masks_or_null && (st = check_col(g, "ec_sharded_stats", "masks", masks_or_null, n)) != EC_OK) return st;
-    const uint64_t limit = stats_max_cells(t);
     for (int i = 0; i < g->n; ++i)
-        if (limit && n[i] > limit)
-            return set_error(EC_ERR_ARG, "ec_sharded_stats: shard %d has %zu cells, more than the %llu one exact record covers: shard it finer",
-                             i, n[i], static_cast<unsigned long long>(limit));
+        if ((st = check_stats_cells("ec_sharded_stats", i, t, n[i], "shard it finer")) != EC_OK) return st;
     std::lock_guard<std::mutex> lk(g->call_mu);
     st = for_each_shard(g, [&](int i) {
         return ec_stats_device(t, p[i], masks_or_null ? masks_or_null[i] : nullptr, n[i], g->payload_dev[i], g->streams[i]);

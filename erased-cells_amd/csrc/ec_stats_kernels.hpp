@@ -6,8 +6,9 @@
 // The frame is the reductions' (ec_reduce_kernels.hpp, ec_reduce_plan.hpp): the launch shape of reduce_plan(), a read-only
 // stream at 16 B per lane with U loads in flight, the peeled head and the ragged tail folded cell by cell by workgroup 0,
 // one barrier per workgroup through block_fold over a Moments partial, partials in the stream's scratch, one finalize
-// workgroup over block_fold (k_stats_finalize) — or, with a one-workgroup grid, the record written by that workgroup itself.  The min/max
-// part is k_min_max_partials' fold, ByteFold included.  What is new is the moments:
+// workgroup over block_fold (k_stats_finalize) — or, with a one-workgroup grid, the record written by that workgroup itself.  The
+// launch sequence is launch_reduction's (ec_reduce_launch.hpp), which ec_stats.hip describes these kernels to.  The min/max
+// part is MinMaxLanes (ec_reduce_kernels.hpp), the accumulator of k_min_max_partials, ByteFold included.  What is new is the moments:
 //   kind 0 (1-, 2-, 4-byte integers)  exact: the count, the sum in int64, the sum of squares in 128 bits.
 //   kind 1 (u64, i64, f32, f64)       d = to_f64(x) - pivot; s1 += d; s2 = fma(d, d, s2), one accumulator pair per slot of the
 //                                     16-byte group, combined in slot order.  No atomics anywhere: the record is a pure
@@ -98,11 +99,11 @@ __device__ __forceinline__ void write_record(ec_moments* __restrict__ out, const
 
 // One lane's running record, cell by cell: the head, the tail, the cell-wise kernel — and what the vector kernel's tile
 // accumulators are flushed into.
-template <typename T>
+template <typename T, bool MASKED>
 struct CellMoments {
     using A = typename AccT<T>::type;
     static constexpr int KIND = StatsKind<T>::value;
-    A amin, amax;
+    MinMaxLanes<T, MASKED> mm;  // the vector kernel folds its groups into it as well
     uint64_t cnt;    // <= 2^24 + 32 per lane
     int64_t sum;     // kind 0: |sum| <= (2^24 + 32) * 2^16 < 2^41 (1, 2 bytes); <= (2^23 + 32) * 2^32 < 2^56 (4 bytes)
     uint64_t sq_lo;  // kind 0: 1, 2 bytes: <= (2^24 + 32) * 2^32 < 2^57, never carries; 4 bytes: carries into sq_hi
@@ -110,8 +111,7 @@ struct CellMoments {
     double s1, s2;   // kind 1
 
     __device__ __forceinline__ void init() {
-        amin = acc_key<T>(Limits<T>::hi);
-        amax = acc_key<T>(Limits<T>::lo);
+        mm.init();
         cnt = 0;
         sum = 0;
         sq_lo = 0;
@@ -119,9 +119,7 @@ struct CellMoments {
         s1 = s2 = 0.0;
     }
     __device__ __forceinline__ void add(T x, double pivot) {
-        const A key = acc_key<T>(x);
-        amin = key < amin ? key : amin;
-        amax = key > amax ? key : amax;
+        mm.fold_cell(x);
         ++cnt;
         if constexpr (KIND == 0) {
             const int64_t w = static_cast<int64_t>(x);
@@ -138,8 +136,8 @@ struct CellMoments {
     __device__ __forceinline__ Moments partial() const {
         Moments r;
         r.count = cnt;
-        r.kmin = acc_to_i64<A>(amin);
-        r.kmax = acc_to_i64<A>(amax);
+        r.kmin = acc_to_i64<A>(mm.amin);
+        r.kmax = acc_to_i64<A>(mm.amax);
         if constexpr (KIND == 0) {
             r.a = static_cast<uint64_t>(sum);
             r.b = sq_lo;
@@ -172,17 +170,11 @@ __global__ __launch_bounds__(BLOCK) void k_stats_partials(const T* __restrict__ 
     using A = typename AccT<T>::type;
     constexpr int CPL = 16 / sizeof(T);
     using TV = cells<T, CPL>;
-    using AV = vec<A, CPL>;
     using MV = cells<uint8_t, CPL>;
     constexpr bool BYTES = sizeof(T) == 1;
     constexpr bool SIGNED = !is_fp<T>::value && T(-1) < T(0);
     const A hi0 = acc_key<T>(Limits<T>::hi), lo0 = acc_key<T>(Limits<T>::lo);
-    AV vmin, vmax;
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) { vmin[k] = hi0; vmax[k] = lo0; }
-    ByteFold<typename std::conditional<BYTES, T, uint8_t>::type> bf;
-    bf.init();
-    CellMoments<T> acc;  // the lane's record; its amin / amax take the vector fold's result after the tile loop
+    CellMoments<T, MASKED> acc;  // the lane's record; its min/max lanes (acc.mm) take the groups of the tile loop too
     acc.init();
     double s1[CPL], s2[CPL];  // kind 1: one pair per slot of the 16-byte group
 #pragma unroll
@@ -198,11 +190,11 @@ __global__ __launch_bounds__(BLOCK) void k_stats_partials(const T* __restrict__ 
     const size_t ntiles = (ngroups + TILE - 1) / TILE;
     auto fold = [&](const TV& x, const MV& m) {
         if constexpr (BYTES) {
+            acc.mm.fold_group(x, m);
             // four cells per instruction: v_dot4 against ones for the sum, against itself for the squares
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 uint32_t xw = x.v[k];
-                bf.template fold<MASKED>(xw, m.v[k]);
                 if constexpr (MASKED) {
                     xw &= m.v[k] * 0xFFu;  // 0 / 1 bytes -> 0x00 / 0xFF: a hidden cell becomes 0 and adds nothing
                     t_cnt = mask_word_count(m.v[k], t_cnt);
@@ -218,17 +210,20 @@ __global__ __launch_bounds__(BLOCK) void k_stats_partials(const T* __restrict__ 
         } else {
             typename TV::rep xm = x.v;  // kind 0: the cells that count, a hidden cell as 0
             if constexpr (KIND != 0) (void)xm;
+            if constexpr (MASKED && KIND == 0) {
+                // MinMaxLanes::fold_group's loop with the hidden cell zeroed beside each slot's select, the parent's text: an unsigned
+                // cell's zeroed form IS its max-side select, and only written like this (hi0 / lo0 the kernel's, one loop) does the
+                // compiler keep them as one — else +5 % (u32) and +11 % (u16) instructions (profiles/r09/reduce_launch.md §0)
 #pragma unroll
-            for (int k = 0; k < CPL; ++k) {
-                A key = acc_key<T>(x[k]);
-                A kmin = key, kmax = key;
-                if constexpr (MASKED) {
-                    kmin = m[k] ? key : hi0;
-                    kmax = m[k] ? key : lo0;
-                    if constexpr (KIND == 0) xm[k] = m[k] ? x[k] : T(0);
+                for (int k = 0; k < CPL; ++k) {
+                    const A key = acc_key<T>(x[k]);
+                    const A kmin = m[k] ? key : hi0, kmax = m[k] ? key : lo0;
+                    xm[k] = m[k] ? x[k] : T(0);
+                    acc.mm.vmin[k] = kmin < acc.mm.vmin[k] ? kmin : acc.mm.vmin[k];
+                    acc.mm.vmax[k] = kmax > acc.mm.vmax[k] ? kmax : acc.mm.vmax[k];
                 }
-                vmin[k] = kmin < vmin[k] ? kmin : vmin[k];
-                vmax[k] = kmax > vmax[k] ? kmax : vmax[k];
+            } else {
+                acc.mm.fold_group(x, m);
             }
             if constexpr (MASKED) {
                 if constexpr (CPL == 2) t_cnt += (m.v & 1u) + ((m.v >> 8) & 1u);
@@ -311,19 +306,7 @@ __global__ __launch_bounds__(BLOCK) void k_stats_partials(const T* __restrict__ 
         t_cnt = t_sum = t_sq = 0;
     }
     // horizontal fold of the lane's accumulators, then the ragged tail and the peeled head
-    A amin = vmin[0], amax = vmax[0];
-    if constexpr (BYTES) {
-        amin = bf.result_min();
-        amax = bf.result_max();
-    } else {
-#pragma unroll
-        for (int k = 1; k < CPL; ++k) {
-            amin = vmin[k] < amin ? vmin[k] : amin;
-            amax = vmax[k] > amax ? vmax[k] : amax;
-        }
-    }
-    acc.amin = amin;
-    acc.amax = amax;
+    acc.mm.finish();
     if constexpr (KIND == 1) {
         acc.s1 = s1[0];
         acc.s2 = s2[0];
@@ -353,7 +336,7 @@ template <typename T, bool MASKED>
 __global__ __launch_bounds__(kBlock) void k_stats_partials_cellwise(const T* __restrict__ p, const uint8_t* __restrict__ mask,
                                                                     size_t n, Moments* __restrict__ partials) {
     const double pivot = stats_pivot<T>(p);
-    CellMoments<T> acc;
+    CellMoments<T, MASKED> acc;
     acc.init();
     const size_t stride = size_t(gridDim.x) * kBlock;
     for (size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {

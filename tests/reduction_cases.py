@@ -25,7 +25,7 @@ from oracle.eco import NP_DTYPES
 WAVE = 64                    # kWave, ec_binop_kernels.hpp
 SHAPES = {0: (512, 8), 1: (512, 16), 2: (256, 8), 3: (1024, 8), 4: (512, 4)}   # reduce_shape -> (BLOCK, U): ec_abi.hip launch_min_max
 RBLOCK, RU = 512, 8          # k_first_diff_partials / k_mask_count_partials: kRBlock (ec_reduce_kernels.hpp), kReduceU (ec_reduce_plan.hpp); kScanShape, ec_abi.hip
-CELLWISE_BLOCK = 256         # k_min_max_partials_cellwise: kBlock (ec_binop_kernels.hpp), at most 8 workgroups per CU (ec_abi.hip launch_min_max)
+CELLWISE_BLOCK = 256         # k_min_max_partials_cellwise: kBlock (ec_binop_kernels.hpp), at most 8 workgroups per CU (ec_reduce_launch.hpp launch_reduction)
 CELLWISE_PER_CU = 8
 FINALIZE_BLOCK = 1024        # kFinalizeBlock, ec_reduce_kernels.hpp (finalize_fold): four load slots per thread
 MAX_PARTS = 4096             # kMaxReduceBlocks (ec_reduce_plan.hpp, reduce_cap) = kFinalizeMaxParts (ec_reduce_kernels.hpp): the grid's hard cap

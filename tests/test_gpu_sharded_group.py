@@ -323,29 +323,54 @@ def test_scratch_table_is_bounded_and_streams_can_be_released(ec):
 @pytest.mark.gpu
 @pytest.mark.timeout(300)
 def test_host_threads_sharing_one_stream_take_turns(ec):
-    """Synchronous-result entry points on ONE stream from several host threads: the per-stream pinned result words
-    are guarded, so each thread reads its own answer."""
+    """Synchronous-result entry points on ONE stream from several host threads: all five go through one hand-over that guards
+    the stream's result slots (the pinned words of ec_min_max, ec_mask_counts and ec_first_difference, the device slots of
+    ec_stats_compute's record and ec_expr_min_max's keys), so each thread reads its own answer, every time.  Past one workgroup:
+    the partials and the finalize launches share the scratch as well."""
+    import stats_ref
     from vectors import rand_cells, rand_mask
-    L, chk = ec.lib(), ec._ffi.check
+    L, E, chk = ec.lib(), ec._ffi, ec._ffi.check
     s = C.c_void_p()
     chk(L.ec_stream_create(C.byref(s)))
+    one_u16 = (C.c_uint8 * 1)(ec.UInt16)
+    add_1_5 = ((E.EcValue * 1)(ec.CellValue.new(1.5).to_ec()), (E.EcExprStep * 1)(E.EcExprStep(eco.ADD, 0, 8, 0)))  # s0 + k0
     cases = []
     for i in range(4):
         a = rand_cells(eco.U16, 50000 + 977 * i, 41 + i)
         m = rand_mask(a.size, 51 + i)
-        cases.append((ec.CellBuffer.from_vec(a), ec.Mask.new(m), eco.f_min_max(a), eco.mask_counts(m)))
+        other, at = a.copy(), 30011 + 4099 * i  # one planted difference, beyond the first workgroup's tile
+        other[at] ^= 1
+        plus = eco.f_min_max(eco.f_binop(eco.ADD, a, np.full(a.size, 1.5)))
+        cases.append((ec.CellBuffer.from_vec(a), ec.Mask.new(m), eco.f_min_max(a), eco.mask_counts(m),
+                      ec.CellBuffer.from_vec(other), at, stats_ref.stats(stats_ref.U16, a), plus))
     errors = []
+
+    def f64_bits(x):
+        return np.float64(x).view(np.uint64)
 
     def work(i):
         try:
-            buf, msk, (emn, emx), ecnt = cases[i]
+            buf, msk, (emn, emx), ecnt, other, at, est, (pmn, pmx) = cases[i]
             for _ in range(200):
-                mn, mx = ec._ffi.EcValue(), ec._ffi.EcValue()
+                mn, mx = E.EcValue(), E.EcValue()
                 chk(L.ec_min_max(ec.UInt16, buf.mem.ptr, None, buf.len(), C.byref(mn), C.byref(mx), s))
                 assert (ec.CellValue.from_ec(mn).bits(), ec.CellValue.from_ec(mx).bits()) == (emn.bits(), emx.bits())
                 t, f = C.c_uint64(), C.c_uint64()
                 chk(L.ec_mask_counts(msk.mem.ptr, msk.len(), C.byref(t), C.byref(f), s))
                 assert (t.value, f.value) == ecnt
+                idx = C.c_uint64(0)
+                chk(L.ec_first_difference(ec.UInt16, buf.mem.ptr, other.mem.ptr, buf.len(), C.byref(idx), s))
+                assert idx.value == at
+                st = E.EcStats()
+                chk(L.ec_stats_compute(ec.UInt16, buf.mem.ptr, None, buf.len(), C.byref(st), s))
+                got = (st.count, st.min.dtype, st.max.dtype, ec.CellValue.from_ec(st.min).bits(), ec.CellValue.from_ec(st.max).bits(),
+                       f64_bits(st.sum), f64_bits(st.mean), f64_bits(st.stddev))
+                assert got == (est["count"], ec.UInt16, ec.UInt16, est["min"], est["max"],
+                               f64_bits(est["sum"]), f64_bits(est["mean"]), f64_bits(est["stddev"])), ("stats", got, est)
+                mn, mx = E.EcValue(), E.EcValue()
+                chk(L.ec_expr_min_max(one_u16, (C.c_void_p * 1)(buf.mem.ptr), None, 1, add_1_5[0], 1, add_1_5[1], 1, buf.len(),
+                                      C.byref(mn), C.byref(mx), s))
+                assert (ec.CellValue.from_ec(mn).bits(), ec.CellValue.from_ec(mx).bits()) == (pmn.bits(), pmx.bits())
         except Exception as e:  # noqa: BLE001
             errors.append(repr(e))
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Latency of the synchronous-result entry points on a fixture-sized buffer (186 x 169 cells) and on 16384² (dev tool).
 Run twice: as is (results written straight into pinned host words) and with EC_NO_ZERO_COPY_RESULTS=1 (device scratch +
-a queued device-to-host copy, the round-1 path)."""
+a queued device-to-host copy, the round-1 path).  ec_stats_compute and ec_expr_min_max (`a + 1.5`, two passes), whose results
+come back from device slots by a copy either way, are timed at the fixture size only."""
 import ctypes as C
 import os
 import sys
@@ -24,6 +25,12 @@ for n in (186 * 169, 16384 * 16384):
     calls = {"min_max": lambda: chk(L.ec_min_max(ec.UInt16, a.mem.ptr, None, n, C.byref(mn), C.byref(mx), None)),
              "mask_counts": lambda: chk(L.ec_mask_counts(m.mem.ptr, n, C.byref(t), C.byref(f), None)),
              "first_difference": lambda: chk(L.ec_first_difference(ec.UInt16, a.mem.ptr, b.mem.ptr, n, C.byref(idx), None))}
+    if n < 1 << 20:
+        st = ec._ffi.EcStats()
+        dt, ptr = (C.c_uint8 * 1)(ec.UInt16), (C.c_void_p * 1)(a.mem.ptr)
+        k0, step = (ec._ffi.EcValue * 1)(ec.CellValue.new(1.5).to_ec()), (ec._ffi.EcExprStep * 1)(ec._ffi.EcExprStep(0, 0, 8, 0))  # s0 + k0
+        calls["stats_compute"] = lambda: chk(L.ec_stats_compute(ec.UInt16, a.mem.ptr, None, n, C.byref(st), None))
+        calls["expr_min_max"] = lambda: chk(L.ec_expr_min_max(dt, ptr, None, 1, k0, 1, step, 1, n, C.byref(mn), C.byref(mx), None))
     for name, fn in calls.items():
         for spin in (0,):  # (round 4 tried polling the stream with hipStreamQuery for up to 200 µs before blocking: slower, removed)
             for _ in range(200):
