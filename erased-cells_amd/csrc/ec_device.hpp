@@ -14,6 +14,7 @@
 
 #include <type_traits>
 
+#include "ec_order_key.hpp"
 #include "erased_cells.h"
 
 namespace ecd {
@@ -33,10 +34,6 @@ using vec = T __attribute__((ext_vector_type(N)));
     X(EC_I64, int64_t)     \
     X(EC_F32, float)       \
     X(EC_F64, double)
-
-template <typename T> struct is_fp { static constexpr bool value = false; };
-template <> struct is_fp<float> { static constexpr bool value = true; };
-template <> struct is_fp<double> { static constexpr bool value = true; };
 
 constexpr uint64_t kNegQNaN = 0xFFF8000000000000ull;  // x86-64 SSE default NaN
 constexpr uint64_t kQuietBit = 0x0008000000000000ull;
@@ -145,41 +142,7 @@ __device__ __forceinline__ void cell_op_n(const double (&a)[N], const double (&b
     }
 }
 
-// f32/f64::total_cmp keys (src/value.rs:260-261) and their integer siblings:
-// every cell type maps to an int64 whose natural order is the reference order.
-template <typename T>
-__device__ __host__ __forceinline__ int64_t order_key(T v) {
-    if constexpr (sizeof(T) == 8 && !is_fp<T>::value && T(-1) > T(0)) {
-        return static_cast<int64_t>(static_cast<uint64_t>(v) ^ 0x8000000000000000ull);  // u64
-    } else if constexpr (!is_fp<T>::value) {
-        return static_cast<int64_t>(v);
-    } else if constexpr (sizeof(T) == 4) {
-        int32_t b = __builtin_bit_cast(int32_t, v);
-        b ^= static_cast<int32_t>(static_cast<uint32_t>(b >> 31) >> 1);
-        return b;
-    } else {
-        int64_t b = __builtin_bit_cast(int64_t, v);
-        b ^= static_cast<int64_t>(static_cast<uint64_t>(b >> 63) >> 1);
-        return b;
-    }
-}
-
-template <typename T>
-__device__ __host__ __forceinline__ T key_value(int64_t k) {
-    if constexpr (sizeof(T) == 8 && !is_fp<T>::value && T(-1) > T(0)) {
-        return static_cast<T>(static_cast<uint64_t>(k) ^ 0x8000000000000000ull);
-    } else if constexpr (!is_fp<T>::value) {
-        return static_cast<T>(k);
-    } else if constexpr (sizeof(T) == 4) {
-        int32_t b = static_cast<int32_t>(k);
-        b ^= static_cast<int32_t>(static_cast<uint32_t>(b >> 31) >> 1);
-        return __builtin_bit_cast(float, b);
-    } else {
-        int64_t b = k;
-        b ^= static_cast<int64_t>(static_cast<uint64_t>(b >> 63) >> 1);
-        return __builtin_bit_cast(double, b);
-    }
-}
+// order_key / key_value (f32/f64::total_cmp keys, src/value.rs:260-261, and their integer siblings) and is_fp: ec_order_key.hpp
 
 __device__ __host__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;

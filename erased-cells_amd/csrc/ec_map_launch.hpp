@@ -1,0 +1,52 @@
+// ec_map_launch.hpp — host-side launch of the k_map family (ec_map_kernels.hpp): one workgroup per tile of U 16-byte groups per
+// lane, the cell-wise kernel when a pointer is not 16-byte aligned and the "unaligned_vector" knob is off.
+#pragma once
+
+#include <type_traits>
+
+#include "ec_map_kernels.hpp"
+#include "ec_runtime.hpp"
+
+namespace ecd {
+
+template <typename Fn> struct pure_store : std::false_type {};
+template <typename W> struct pure_store<FillFn<W>> : std::true_type {};
+
+template <typename Fn, int U>
+static void launch_map_u(const Fn& fn, size_t n, hipStream_t s) {
+    const size_t groups = n / Fn::CPL;
+    const size_t tiles = (groups + size_t(kBlock) * U - 1) / (size_t(kBlock) * U);
+    const size_t stream_bytes[2] = {n * Fn::kIn0, n * Fn::kIn1};
+    // ec_fill is a pure write stream with nothing to compute: unused dynamic LDS caps its resident workgroups per CU (the generators
+    // load nothing either, but hash every cell — they need their occupancy: 576 -> 879 µs for 2^28 u8 cells under the same cap)
+    const unsigned lds = (pure_store<Fn>::value ? static_cast<unsigned>(tuning().write_lds_kb.load())
+                                                : (Fn::kIn0 != 0 ? static_cast<unsigned>(tuning().map_lds_kb.load()) : 0u)) << 10;
+    k_map<Fn, U><<<grid_for(tiles), kBlock, lds, s>>>(fn, n, cache_plan(stream_bytes, 2));
+}
+
+template <typename Fn>
+static ec_status launch_map(const Fn& fn, size_t n, bool aligned, hipStream_t s, const char* what) {
+    if (n == 0) return EC_OK;
+    if (!aligned) {
+        k_map_cellwise<Fn><<<grid_capped((n + kBlock - 1) / kBlock, 8), kBlock, 0, s>>>(fn, n);
+    } else {
+        switch (tuning().map_u) {  // groups of 16 B per lane per tile
+            case 1: launch_map_u<Fn, 1>(fn, n, s); break;
+            case 4: launch_map_u<Fn, 4>(fn, n, s); break;
+            default: launch_map_u<Fn, 2>(fn, n, s); break;
+        }
+    }
+    return check_launch(what);
+}
+
+// The same at the default tile shape only ("map_u" = 2, whatever the knob says): for kernel families with many type pairs
+// (ec_compare.hip), which would otherwise triple their instantiation count over the knob.
+template <typename Fn>
+static ec_status launch_map_default_u(const Fn& fn, size_t n, bool aligned, hipStream_t s, const char* what) {
+    if (n == 0) return EC_OK;
+    if (!aligned) k_map_cellwise<Fn><<<grid_capped((n + kBlock - 1) / kBlock, 8), kBlock, 0, s>>>(fn, n);
+    else launch_map_u<Fn, 2>(fn, n, s);
+    return check_launch(what);
+}
+
+}  // namespace ecd

@@ -151,6 +151,8 @@ ec_status check_group(const ec_shard_group* g, const char* what) {
 //   ec_sharded_masked_binop       l, r, lmask, rmask, out, out_mask
 //   ec_sharded_convert            src, dst
 //   ec_sharded_mask_from_nodata   p, mask
+//   ec_sharded_compare            l, r, lmask and rmask where given, out_mask
+//   ec_sharded_compare_scalar     l, lmask where given, out_mask
 //   ec_sharded_fused              p[k] of every operand with a column, out.  NOT masks[k] and out_mask: they are copied
 //                                 unchecked, a null per-shard mask reaches ec_masked_fused as it is
 //   ec_sharded_expr               p[k] and (masked) masks[k] stream by stream, out, (masked) out_mask
@@ -494,6 +496,53 @@ extern "C" ec_status ec_sharded_mask_from_nodata(ec_shard_group* g, ec_dtype t, 
     std::lock_guard<std::mutex> lk(g->call_mu);
     return post_each_shard(g, [g, t, has_nd, nd, p = std::move(pv), n = copy_col(g, n), mask = std::move(mv)](int i) {
         return ec_mask_from_nodata(t, p[i], n[i], has_nd ? &nd : nullptr, mask[i], g->streams[i]);
+    });
+}
+
+// an optional mask column: checked and copied when given, a column of nulls otherwise
+static std::vector<const uint8_t*> take_optional(const ec_shard_group* g, const char* what, const char* name, const uint8_t* const* col,
+                                                 const size_t* n, ec_status* st) {
+    return col ? take(g, what, name, col, n, st) : std::vector<const uint8_t*>(g->n, nullptr);
+}
+
+extern "C" ec_status ec_sharded_compare(ec_shard_group* g, int32_t rel, ec_dtype lt, const void* const* l, const uint8_t* const* lmask_or_null,
+                                        ec_dtype rt, const void* const* r, const uint8_t* const* rmask_or_null, const size_t* n,
+                                        uint8_t* const* out_mask) {
+    const char* what = "ec_sharded_compare";
+    ec_status st = check_group(g, what);
+    if (st != EC_OK) return st;
+    st = ec_compare(rel, lt, nullptr, nullptr, rt, nullptr, nullptr, 0, nullptr, nullptr);  // relation and dtypes, before any device work
+    if (st != EC_OK) return st;
+    if (!l || !r || !n || !out_mask) return set_error(EC_ERR_ARG, "%s: null argument", what);
+    auto lv = take(g, what, "l", l, n, &st);
+    auto rv = take(g, what, "r", r, n, &st);
+    auto lmv = take_optional(g, what, "lmask", lmask_or_null, n, &st);
+    auto rmv = take_optional(g, what, "rmask", rmask_or_null, n, &st);
+    auto ov = take(g, what, "out_mask", out_mask, n, &st);
+    if (st != EC_OK) return st;
+    std::lock_guard<std::mutex> lk(g->call_mu);
+    return post_each_shard(g, [g, rel, lt, rt, l = std::move(lv), lm = std::move(lmv), r = std::move(rv), rm = std::move(rmv),
+                               n = copy_col(g, n), out = std::move(ov)](int i) {
+        return ec_compare(rel, lt, l[i], lm[i], rt, r[i], rm[i], n[i], out[i], g->streams[i]);
+    });
+}
+
+extern "C" ec_status ec_sharded_compare_scalar(ec_shard_group* g, int32_t rel, ec_dtype lt, const void* const* l,
+                                               const uint8_t* const* lmask_or_null, const size_t* n, const ec_value* rhs,
+                                               uint8_t* const* out_mask) {
+    const char* what = "ec_sharded_compare_scalar";
+    ec_status st = check_group(g, what);
+    if (st != EC_OK) return st;
+    st = ec_compare_scalar(rel, lt, nullptr, nullptr, 0, rhs, nullptr, nullptr);  // relation, scalar and dtypes, before any device work
+    if (st != EC_OK) return st;
+    if (!l || !n || !out_mask) return set_error(EC_ERR_ARG, "%s: null argument", what);
+    auto lv = take(g, what, "l", l, n, &st);
+    auto lmv = take_optional(g, what, "lmask", lmask_or_null, n, &st);
+    auto ov = take(g, what, "out_mask", out_mask, n, &st);
+    if (st != EC_OK) return st;
+    std::lock_guard<std::mutex> lk(g->call_mu);
+    return post_each_shard(g, [g, rel, lt, rhs = *rhs, l = std::move(lv), lm = std::move(lmv), n = copy_col(g, n), out = std::move(ov)](int i) {
+        return ec_compare_scalar(rel, lt, l[i], lm[i], n[i], &rhs, out[i], g->streams[i]);
     });
 }
 

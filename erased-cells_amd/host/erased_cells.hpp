@@ -335,6 +335,8 @@ struct Stats {
 };
 
 // ---------------------------------------------------------------- CellBuffer (src/buffer.rs)
+class Mask;
+
 class CellBuffer {
     CellType ct_ = CellType::UInt8;
     size_t n_ = 0;
@@ -528,6 +530,12 @@ public:
         return out;
     }
 
+    // ---- per-cell order predicates (impl Ord for CellValue, value.rs:248-271, cell by cell): the Mask of the cells for which
+    // `self[i] rel rhs[i]` holds — both cells unified to CellType::union, ints natural, floats total_cmp; rhs a buffer (zip-truncated)
+    // or a scalar.  One launch.  (Defined behind Mask.)  The operators == < > below are NOT this: they stay the whole-buffer Ord.
+    Mask compare(ec_cmp rel, const CellBuffer& rhs) const;
+    Mask compare(ec_cmp rel, const CellValue& rhs) const;
+
     // ---- Ord/Eq (buffer.rs:373-436): cell type first, then lexicographic total order, then length
     int cmp(const CellBuffer& o) const {  // decided on the device: first differing cell, no download
         int32_t res = 0;
@@ -666,6 +674,29 @@ inline Mask operator|(Mask&& l, const Mask& r) {  // mask.rs:142-151
     return std::move(l);
 }
 
+inline Mask CellBuffer::compare(ec_cmp rel, const CellBuffer& rhs) const {
+    const size_t n = n_ < rhs.n_ ? n_ : rhs.n_;  // zip (buffer.rs:327)
+    Mask m(n);
+    check(ec_compare(rel, static_cast<ec_dtype>(ct_), ptr(), nullptr, static_cast<ec_dtype>(rhs.ct_), rhs.ptr(), nullptr, n, m.ptr(), current_stream()));
+    return m;
+}
+inline Mask CellBuffer::compare(ec_cmp rel, const CellValue& rhs) const {
+    Mask m(n_);
+    check(ec_compare_scalar(rel, static_cast<ec_dtype>(ct_), ptr(), nullptr, n_, &rhs.raw(), m.ptr(), current_stream()));
+    return m;
+}
+// out[i] = mask[i] ? a[i] : b[i] (ec_select), zip-truncated; operands of different cell types are converted to their union first
+inline CellBuffer select(const Mask& mask, const CellBuffer& a, const CellBuffer& b) {
+    if (a.cell_type() != b.cell_type()) {
+        const CellType u = union_of(a.cell_type(), b.cell_type());
+        return select(mask, a.convert(u), b.convert(u));
+    }
+    const size_t n = std::min(mask.len(), std::min(a.len(), b.len()));
+    CellBuffer out(a.cell_type(), n);
+    check(ec_select(static_cast<ec_dtype>(a.cell_type()), a.ptr(), b.ptr(), mask.ptr(), n, out.ptr(), current_stream()));
+    return out;
+}
+
 // ---------------------------------------------------------------- MaskedCellBuffer (src/masked/masked_buffer.rs)
 class MaskedCellBuffer {
     CellBuffer buf_;
@@ -775,6 +806,35 @@ public:
         check(ec_stats_compute(static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), len(), &out, current_stream()));
         return Stats(out);
     }
+
+    // ---- per-cell order predicates ANDed, in the same launch, with the masks: a cell that is not valid satisfies none (:326-335)
+    Mask compare(ec_cmp rel, const MaskedCellBuffer& rhs) const {
+        const size_t n = len() < rhs.len() ? len() : rhs.len();
+        Mask m(n);
+        check(ec_compare(rel, static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), static_cast<ec_dtype>(rhs.cell_type()), rhs.buf_.ptr(),
+                         rhs.mask_.ptr(), n, m.ptr(), current_stream()));
+        return m;
+    }
+    Mask compare(ec_cmp rel, const CellValue& rhs) const {
+        Mask m(len());
+        check(ec_compare_scalar(rel, static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), len(), &rhs.raw(), m.ptr(), current_stream()));
+        return m;
+    }
+    // out[i], out_mask[i] = sel[i] ? (a[i], amask[i]) : (b[i], bmask[i]) (ec_masked_select); different cell types meet in their union
+    static MaskedCellBuffer select(const Mask& sel, const MaskedCellBuffer& a, const MaskedCellBuffer& b) {
+        if (a.cell_type() != b.cell_type()) {
+            const CellType u = union_of(a.cell_type(), b.cell_type());
+            return select(sel, a.convert(u), b.convert(u));
+        }
+        const size_t n = std::min(sel.len(), std::min(a.len(), b.len()));
+        CellBuffer out(a.cell_type(), n);
+        Mask om(n);
+        check(ec_masked_select(static_cast<ec_dtype>(a.cell_type()), a.buf_.ptr(), a.mask_.ptr(), b.buf_.ptr(), b.mask_.ptr(), sel.ptr(), n,
+                               out.ptr(), om.ptr(), current_stream()));
+        return MaskedCellBuffer(std::move(out), std::move(om));
+    }
+    // this buffer's cell where it is valid, else `other`'s cell with `other`'s validity (cloud fill)
+    MaskedCellBuffer or_else(const MaskedCellBuffer& other) const { return select(mask_, *this, other); }
 
     // ---- ops (:323-383)
     MaskedCellBuffer binop(ec_op op, const MaskedCellBuffer& rhs) const {
@@ -1205,6 +1265,26 @@ public:
     ShardedCellBuffer operator-(const ShardedCellBuffer& r) const { return binop(EC_SUB, r); }
     ShardedCellBuffer operator*(const ShardedCellBuffer& r) const { return binop(EC_MUL, r); }
     ShardedCellBuffer operator/(const ShardedCellBuffer& r) const { return binop(EC_DIV, r); }
+    // CellBuffer::compare on every shard (value.rs:248-271 per cell): a UInt8 buffer of 0 / 1 bytes cut the same way; `rhs` an
+    // identically sharded buffer or a scalar
+    ShardedCellBuffer compare(ec_cmp rel, const ShardedCellBuffer& rhs) const {
+        if (lens_ != rhs.lens_) throw Error(EC_ERR_LENGTH, "operands must be sharded identically");
+        ShardedCellBuffer out(*grp_, CellType::UInt8, lens_);
+        std::vector<const void*> l(ptrs_.begin(), ptrs_.end()), r(rhs.ptrs_.begin(), rhs.ptrs_.end());
+        std::vector<uint8_t*> o;
+        for (void* p : out.ptrs_) o.push_back(static_cast<uint8_t*>(p));
+        check(ec_sharded_compare(grp_->raw(), rel, static_cast<ec_dtype>(ct_), l.data(), nullptr, static_cast<ec_dtype>(rhs.ct_), r.data(), nullptr,
+                                 lens_.data(), o.data()));
+        return out;
+    }
+    ShardedCellBuffer compare(ec_cmp rel, const CellValue& rhs) const {
+        ShardedCellBuffer out(*grp_, CellType::UInt8, lens_);
+        std::vector<const void*> l(ptrs_.begin(), ptrs_.end());
+        std::vector<uint8_t*> o;
+        for (void* p : out.ptrs_) o.push_back(static_cast<uint8_t*>(p));
+        check(ec_sharded_compare_scalar(grp_->raw(), rel, static_cast<ec_dtype>(ct_), l.data(), nullptr, lens_.data(), &rhs.raw(), o.data()));
+        return out;
+    }
     // BufferOps::min_max of the whole raster (buffer.rs:169-173): per-shard keys, one all-reduce(MAX), decode
     std::pair<CellValue, CellValue> min_max() const {
         ec_value mn, mx;

@@ -19,6 +19,8 @@ EC_OK, EC_ERR_NARROWING, EC_ERR_UNSUPPORTED_TYPE, EC_ERR_LENGTH, EC_ERR_HIP, EC_
     EC_ERR_NOT_INITIALIZED = range(8)
 EC_RESAMPLE_NEAREST, EC_RESAMPLE_BILINEAR, EC_RESAMPLE_AVERAGE = 0, 1, 5  # ec_resample: GDAL's GRIORA_* numbers
 EC_WINDOW_MAX_REDUCTION = 64
+# ec_cmp: a relation is the truth table over Ordering — bit 0 Less, bit 1 Equal, bit 2 Greater
+EC_CMP_LT, EC_CMP_EQ, EC_CMP_LE, EC_CMP_GT, EC_CMP_NE, EC_CMP_GE = 1, 2, 3, 4, 5, 6
 
 
 class _Payload(C.Union):
@@ -166,6 +168,12 @@ SIGNATURES = {
     "ec_mask_not": (I32, [U8P, SZ, U8P, VP]),
     "ec_mask_counts": (I32, [U8P, SZ, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), VP]),
     "ec_mask_counts_device": (I32, [U8P, SZ, VP, VP]),
+    "ec_compare": (I32, [I32, C.c_uint8, VP, U8P, C.c_uint8, VP, U8P, SZ, U8P, VP]),
+    "ec_compare_scalar": (I32, [I32, C.c_uint8, VP, U8P, SZ, PV, U8P, VP]),
+    "ec_select": (I32, [C.c_uint8, VP, VP, U8P, SZ, VP, VP]),
+    "ec_masked_select": (I32, [C.c_uint8, VP, U8P, VP, U8P, U8P, SZ, VP, U8P, VP]),
+    "ec_sharded_compare": (I32, [VP, I32, C.c_uint8, PVP, PVP, C.c_uint8, PVP, PVP, PSZ, PVP]),
+    "ec_sharded_compare_scalar": (I32, [VP, I32, C.c_uint8, PVP, PVP, PSZ, PV, PVP]),
     "ec_stats_device": (I32, [C.c_uint8, VP, U8P, SZ, VP, VP]),
     "ec_stats_fold": (I32, [VP, I32, VP]),
     "ec_stats_compute": (I32, [C.c_uint8, VP, U8P, SZ, VP, VP]),

@@ -20,7 +20,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import EC_ERR_ARG, EC_RESAMPLE_AVERAGE, EC_RESAMPLE_BILINEAR, EcError, EcStats, EcValue, check, lib
+from ._ffi import EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_RESAMPLE_AVERAGE, EC_RESAMPLE_BILINEAR, EcError, EcStats, EcValue, check, lib
 
 # CellType (src/ctype.rs:11-20; order of with_ct!, src/lib.rs:89-98)
 UInt8, UInt16, UInt32, UInt64, Int8, Int16, Int32, Int64, Float32, Float64 = range(10)
@@ -375,6 +375,33 @@ def _scalar(x) -> CellValue:
     return CellValue.new(x)
 
 
+# the spellings of an ec_cmp relation: the truth table over Ordering (bit 0 Less, bit 1 Equal, bit 2 Greater)
+RELATIONS = {"<": EC_CMP_LT, "==": EC_CMP_EQ, "<=": EC_CMP_LE, ">": EC_CMP_GT, "!=": EC_CMP_NE, ">=": EC_CMP_GE}
+
+
+def _relation(rel) -> int:
+    """the ec_cmp number of "<" "<=" ">" ">=" "==" "!=" or of an ec_cmp value; anything else is refused"""
+    r = RELATIONS.get(rel, rel) if isinstance(rel, str) else rel
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= int(r) <= 6:
+        raise EcError(EC_ERR_ARG, f"compare: relation {rel!r} is not one of {sorted(RELATIONS)} or an ec_cmp value 1..6")
+    return int(r)
+
+
+def _compare(rel, lhs: "CellBuffer", lmask, rhs, rmask=None) -> "Mask":
+    """ec_compare / ec_compare_scalar of `lhs` against a buffer or a scalar, ANDed with the masks given, into a new Mask"""
+    r = _relation(rel)
+    if isinstance(rhs, CellBuffer):
+        n = min(lhs.n, rhs.n)  # zip (buffer.rs:327)
+        out = Mask.empty(n)
+        check(lib().ec_compare(r, lhs.ct, lhs.mem.ptr, lmask.mem.ptr if lmask else None, rhs.ct, rhs.mem.ptr,
+                               rmask.mem.ptr if rmask else None, n, out.mem.ptr, _stream))
+        return out
+    v = _scalar(rhs).to_ec()
+    out = Mask.empty(lhs.n)
+    check(lib().ec_compare_scalar(r, lhs.ct, lhs.mem.ptr, lmask.mem.ptr if lmask else None, lhs.n, C.byref(v), out.mem.ptr, _stream))
+    return out
+
+
 # --------------------------------------------------------------------------- CellBuffer
 @dataclasses.dataclass(frozen=True)
 class Stats:
@@ -587,7 +614,23 @@ class CellBuffer:
         check(lib().ec_neg(self.ct, self.mem.ptr, self.n, out.mem.ptr, _stream))
         return out
 
-    # ---- Ord / Eq (src/buffer.rs:373-436), decided on the device: first differing cell, no download
+    # ---- per-cell order predicates (impl Ord for CellValue, src/value.rs:248-271, cell by cell)
+    def compare(self, rel, rhs) -> "Mask":
+        """The Mask of the cells for which `self[i] rel rhs[i]` holds under the reference's per-cell order (both cells unified to
+        CellType::union, ints natural, floats total_cmp).  `rel`: one of "<" "<=" ">" ">=" "==" "!=" or an ec_cmp value; `rhs`: a
+        CellBuffer (zip-truncated) or a scalar.  One launch, nothing downloaded.  The operators `==` `<` `>` of a buffer are NOT
+        this: they stay the reference's whole-buffer Ord (`cmp`)."""
+        return _compare(rel, self, None, rhs)
+
+    def lt(self, rhs) -> "Mask": return self.compare(EC_CMP_LT, rhs)
+    def le(self, rhs) -> "Mask": return self.compare(EC_CMP_LE, rhs)
+    def gt(self, rhs) -> "Mask": return self.compare(EC_CMP_GT, rhs)
+    def ge(self, rhs) -> "Mask": return self.compare(EC_CMP_GE, rhs)
+    def eq(self, rhs) -> "Mask": return self.compare(EC_CMP_EQ, rhs)
+    def ne(self, rhs) -> "Mask": return self.compare(EC_CMP_NE, rhs)
+
+    # ---- Ord / Eq (src/buffer.rs:373-436), decided on the device: first differing cell, no download.  `==` `<` `>` are the
+    # reference's WHOLE-BUFFER order; the per-cell predicates are compare() and lt() .. ne() above.
     def cmp(self, other: "CellBuffer") -> int:
         res = C.c_int32()
         check(lib().ec_buffer_cmp(self.ct, self.mem.ptr, self.n, other.ct, other.mem.ptr, other.n, C.byref(res), _stream))
@@ -937,6 +980,27 @@ class MaskedCellBuffer:
     def __neg__(self) -> "MaskedCellBuffer":
         return MaskedCellBuffer(-self._buf, self._mask.clone())
 
+    # ---- per-cell order predicates: the predicate ANDed with the masks (a cell that is not valid satisfies none)
+    def compare(self, rel, rhs) -> Mask:
+        """CellBuffer.compare ANDed, in the same launch, with this buffer's mask and — when `rhs` is a MaskedCellBuffer — with its
+        mask too: the masked-operator rule (src/masked/masked_buffer.rs:326-335).  `rhs` may also be a CellBuffer or a scalar.
+        `==` `<` `>` of a MaskedCellBuffer stay the reference's whole-buffer order."""
+        if isinstance(rhs, MaskedCellBuffer):
+            return _compare(rel, self._buf, self._mask, rhs._buf, rhs._mask)
+        return _compare(rel, self._buf, self._mask, rhs)
+
+    def lt(self, rhs) -> Mask: return self.compare(EC_CMP_LT, rhs)
+    def le(self, rhs) -> Mask: return self.compare(EC_CMP_LE, rhs)
+    def gt(self, rhs) -> Mask: return self.compare(EC_CMP_GT, rhs)
+    def ge(self, rhs) -> Mask: return self.compare(EC_CMP_GE, rhs)
+    def eq(self, rhs) -> Mask: return self.compare(EC_CMP_EQ, rhs)
+    def ne(self, rhs) -> Mask: return self.compare(EC_CMP_NE, rhs)
+
+    def or_else(self, other: "MaskedCellBuffer") -> "MaskedCellBuffer":
+        """This buffer's cell where it is valid, else `other`'s cell with `other`'s validity (cloud fill): ec_masked_select with
+        sel == this mask.  Operands of different cell types are converted to their union first."""
+        return select(self._mask, self, other)
+
     def __eq__(self, other):  # derived PartialEq (masked_buffer.rs:39): buffer (all cells) and mask
         return isinstance(other, MaskedCellBuffer) and self._buf == other._buf and self._mask == other._mask
 
@@ -967,3 +1031,25 @@ def mask_from_nodata(b: CellBuffer, nodata: NoData) -> Mask:
     check(lib().ec_mask_from_nodata(b.ct, b.mem.ptr, b.len(), C.byref(ev) if ev is not None else None,
                                     m.mem.ptr, _stream))
     return m
+
+
+def select(mask: Mask, a, b):
+    """out[i] = mask[i] ? a[i] : b[i] (ec_select), zip-truncated to the shortest of the three.  `a` and `b` are both CellBuffers or both
+    MaskedCellBuffers — then the result's mask is picked the same way (ec_masked_select); operands of different cell types are
+    converted to their CellType::union with `convert` first."""
+    masked = isinstance(a, MaskedCellBuffer)
+    if masked != isinstance(b, MaskedCellBuffer):
+        raise EcError(EC_ERR_ARG, "select: a and b must both be CellBuffers or both MaskedCellBuffers")
+    if a.cell_type() != b.cell_type():
+        ct = union(a.cell_type(), b.cell_type())
+        a = a if a.cell_type() == ct else a.convert(ct)
+        b = b if b.cell_type() == ct else b.convert(ct)
+    ct, n = a.cell_type(), min(mask.len(), a.len(), b.len())
+    out = CellBuffer.empty(n, ct)
+    if not masked:
+        check(lib().ec_select(ct, a.mem.ptr, b.mem.ptr, mask.mem.ptr, n, out.mem.ptr, _stream))
+        return out
+    om = Mask.empty(n)
+    check(lib().ec_masked_select(ct, a._buf.mem.ptr, a._mask.mem.ptr, b._buf.mem.ptr, b._mask.mem.ptr, mask.mem.ptr, n,
+                                 out.mem.ptr, om.mem.ptr, _stream))
+    return MaskedCellBuffer(out, om)

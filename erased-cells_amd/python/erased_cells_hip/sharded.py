@@ -193,6 +193,23 @@ class ShardGroup:
         check(lib().ec_sharded_binop(self.handle, op, l.ct, l.ptrs, r.ct, r.ptrs, (C.c_size_t * self.n)(*l.lens), out.ptrs))
         return out
 
+    def compare(self, rel, l: ShardedBuffer, rhs, lmask: ShardedBuffer = None, rmask: ShardedBuffer = None) -> ShardedBuffer:
+        """`CellBuffer.compare` on every shard, fire-and-forget: `rhs` an identically sharded buffer or a scalar; the sharded masks
+        given are ANDed into the result.  Returns the sharded mask (ct = UInt8)."""
+        r = B._relation(rel)
+        lens = (C.c_size_t * self.n)(*l.lens)
+        assert all(m is None or m.lens == l.lens for m in (lmask, rmask)), "masks must be sharded like their operand"
+        out = self.alloc(B.UInt8, l.lens)
+        lm = lmask.ptrs if lmask is not None else None
+        if isinstance(rhs, ShardedBuffer):
+            assert l.lens == rhs.lens, "operands must be sharded identically"
+            check(lib().ec_sharded_compare(self.handle, r, l.ct, l.ptrs, lm, rhs.ct, rhs.ptrs, rmask.ptrs if rmask is not None else None,
+                                           lens, out.ptrs))
+        else:
+            v = B.CellValue.new(rhs).to_ec()
+            check(lib().ec_sharded_compare_scalar(self.handle, r, l.ct, l.ptrs, lm, lens, C.byref(v), out.ptrs))
+        return out
+
     def program(self, streams, scalars, steps, masks=None):
         """An expression program (`fused.program`: steps `(op, a, b, dst)`) on every shard, fire-and-forget: `streams` up to four
         identically sharded buffers, `masks` (optional) one sharded mask per stream.  Returns the f64 result, or

@@ -11,6 +11,8 @@
 use crate::device::{download, stream, upload, DeviceMem};
 use crate::error::{check, must, Error, Result};
 use crate::ffi::*;
+#[cfg(feature = "masked")]
+use crate::Mask;
 use crate::{with_ct, BufferOps, CellEncoding, CellType, CellValue, Elided};
 use num_traits::ToPrimitive;
 use std::cmp::Ordering;
@@ -54,6 +56,66 @@ impl Stats {
     }
     pub(crate) fn from_ffi(s: &ec_stats) -> Self {
         Stats { count: s.count, min: CellValue::from_ffi(&s.min), max: CellValue::from_ffi(&s.max), sum: s.sum, mean: s.mean, stddev: s.stddev }
+    }
+}
+
+/// A per-cell order predicate (`ec_cmp`): the truth table over `Ordering` — bit 0 `Less`, bit 1 `Equal`, bit 2 `Greater`.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum Cmp {
+    Lt = EC_CMP_LT,
+    Eq = EC_CMP_EQ,
+    Le = EC_CMP_LE,
+    Gt = EC_CMP_GT,
+    Ne = EC_CMP_NE,
+    Ge = EC_CMP_GE,
+}
+
+#[cfg(feature = "masked")]
+impl CellBuffer {
+    /// The [`Mask`] of the cells for which `self[i] rel rhs[i]` holds under `impl Ord for CellValue`, cell by cell: both cells
+    /// unified to `CellType::union`, integers natural, floats `total_cmp`.  Zip-truncated; one launch, nothing downloaded.
+    /// `lmask` / `rmask`: device bytes ANDed into the result, or null.  The operators `==` `<` `>` of a buffer are not this:
+    /// they stay the whole-buffer `Ord`.
+    pub(crate) fn compare_raw(&self, rel: Cmp, lmask: *const u8, rhs: &CellBuffer, rmask: *const u8) -> Mask {
+        let n = self.len.min(rhs.len);
+        let out = Mask::uninit(n);
+        must(
+            unsafe { ec_compare(rel as i32, self.ct as u8, self.dev_ptr(), lmask, rhs.ct as u8, rhs.dev_ptr(), rmask, n, out.dev_ptr_mut(), stream()) },
+            "ec_compare",
+        );
+        out
+    }
+
+    pub(crate) fn compare_scalar_raw(&self, rel: Cmp, lmask: *const u8, rhs: CellValue) -> Mask {
+        let out = Mask::uninit(self.len);
+        let v = rhs.to_ffi();
+        must(
+            unsafe { ec_compare_scalar(rel as i32, self.ct as u8, self.dev_ptr(), lmask, self.len, &v, out.dev_ptr_mut(), stream()) },
+            "ec_compare_scalar",
+        );
+        out
+    }
+
+    pub fn compare(&self, rel: Cmp, rhs: &CellBuffer) -> Mask {
+        self.compare_raw(rel, std::ptr::null(), rhs, std::ptr::null())
+    }
+
+    /// [`CellBuffer::compare`] against a scalar; the scalar's own type takes part in the union.
+    pub fn compare_scalar<R: Into<CellValue>>(&self, rel: Cmp, rhs: R) -> Mask {
+        self.compare_scalar_raw(rel, std::ptr::null(), rhs.into())
+    }
+
+    /// `out[i] = mask[i] ? a[i] : b[i]` (`ec_select`), zip-truncated; operands of different cell types meet in their union.
+    pub fn select(mask: &Mask, a: &CellBuffer, b: &CellBuffer) -> Result<CellBuffer> {
+        if a.ct != b.ct {
+            let u = a.ct.union(b.ct);
+            return Self::select(mask, &a.convert(u)?, &b.convert(u)?);
+        }
+        let n = mask.len().min(a.len).min(b.len);
+        let out = Self::uninit(a.ct, n);
+        check(unsafe { ec_select(a.ct as u8, a.dev_ptr(), b.dev_ptr(), mask.dev_ptr(), n, out.mem.ptr(), stream()) })?;
+        Ok(out)
     }
 }
 

@@ -40,6 +40,13 @@ pub const EC_RESAMPLE_BILINEAR: i32 = 1;
 pub const EC_RESAMPLE_AVERAGE: i32 = 5;
 /// An average reduces an axis by at most this factor per call; chain calls for more.
 pub const EC_WINDOW_MAX_REDUCTION: u64 = 64;
+/// `ec_cmp`: a relation is the truth table over `Ordering` — bit 0 `Less`, bit 1 `Equal`, bit 2 `Greater` (`ec_compare` takes it as an `i32`).
+pub const EC_CMP_LT: i32 = 1;
+pub const EC_CMP_EQ: i32 = 2;
+pub const EC_CMP_LE: i32 = 3;
+pub const EC_CMP_GT: i32 = 4;
+pub const EC_CMP_NE: i32 = 5;
+pub const EC_CMP_GE: i32 = 6;
 
 /// Mirrors `ec_value`: tag + 8-byte payload, 16 bytes.
 #[repr(C)]
@@ -155,6 +162,15 @@ extern "C" {
                                s: ec_stream) -> ec_status;
     pub fn ec_mask_select(t: ec_dtype, p: *const c_void, mask: *const u8, n: usize, nd_or_null: *const ec_value,
                           out: *mut c_void, s: ec_stream) -> ec_status;
+    // per-cell order predicates as masks (impl Ord for CellValue, src/value.rs:248-271) and the pick of cells by a mask
+    pub fn ec_compare(rel: i32, lt: ec_dtype, l: *const c_void, lmask_or_null: *const u8, rt: ec_dtype, r: *const c_void,
+                      rmask_or_null: *const u8, n: usize, out_mask: *mut u8, s: ec_stream) -> ec_status;
+    pub fn ec_compare_scalar(rel: i32, lt: ec_dtype, l: *const c_void, lmask_or_null: *const u8, n: usize,
+                             rhs: *const ec_value, out_mask: *mut u8, s: ec_stream) -> ec_status;
+    pub fn ec_select(t: ec_dtype, a: *const c_void, b: *const c_void, sel: *const u8, n: usize, out: *mut c_void,
+                     s: ec_stream) -> ec_status;
+    pub fn ec_masked_select(t: ec_dtype, a: *const c_void, amask: *const u8, b: *const c_void, bmask: *const u8,
+                            sel: *const u8, n: usize, out: *mut c_void, out_mask: *mut u8, s: ec_stream) -> ec_status;
     pub fn ec_mask_and(l: *const u8, r: *const u8, n: usize, out: *mut u8, s: ec_stream) -> ec_status;
     pub fn ec_mask_or(l: *const u8, r: *const u8, n: usize, out: *mut u8, s: ec_stream) -> ec_status;
     pub fn ec_mask_not(m: *const u8, n: usize, out: *mut u8, s: ec_stream) -> ec_status;
@@ -221,6 +237,12 @@ extern "C" {
                               dst: *const *mut c_void, n: *const usize) -> ec_status;
     pub fn ec_sharded_mask_from_nodata(g: *mut ec_shard_group, t: ec_dtype, p: *const *const c_void, n: *const usize,
                                        nd_or_null: *const ec_value, mask: *const *mut u8) -> ec_status;
+    pub fn ec_sharded_compare(g: *mut ec_shard_group, rel: i32, lt: ec_dtype, l: *const *const c_void,
+                              lmask_or_null: *const *const u8, rt: ec_dtype, r: *const *const c_void,
+                              rmask_or_null: *const *const u8, n: *const usize, out_mask: *const *mut u8) -> ec_status;
+    pub fn ec_sharded_compare_scalar(g: *mut ec_shard_group, rel: i32, lt: ec_dtype, l: *const *const c_void,
+                                     lmask_or_null: *const *const u8, n: *const usize, rhs: *const ec_value,
+                                     out_mask: *const *mut u8) -> ec_status;
     pub fn ec_sharded_fused(g: *mut ec_shard_group, o1: ec_op, o2: ec_op, o3: ec_op, dt: *const ec_dtype,
                             p: *const *const *const c_void, masks_or_null: *const *const *const u8,
                             scalars_or_null: *const ec_value, n: *const usize, out: *const *mut f64,

@@ -11,7 +11,7 @@
 use crate::device::stream;
 use crate::error::{check, must, Result};
 use crate::ffi::*;
-use crate::{BufferOps, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Mask, NoData, ResampleAlg, Stats};
+use crate::{BufferOps, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Cmp, Mask, NoData, ResampleAlg, Stats};
 use std::fmt::{Debug, Formatter};
 use std::ops::{Add, Div, Mul, Neg, Sub};
 
@@ -65,6 +65,39 @@ impl MaskedCellBuffer {
             )
         })?;
         Ok(MaskedCellBuffer(cells, mask))
+    }
+
+    /// [`CellBuffer::compare`] ANDed, in the same launch, with both masks: a cell that is not valid satisfies no predicate
+    /// (the masked-operator rule).
+    pub fn compare(&self, rel: Cmp, rhs: &MaskedCellBuffer) -> Mask {
+        self.0.compare_raw(rel, self.1.dev_ptr(), &rhs.0, rhs.1.dev_ptr())
+    }
+
+    /// [`CellBuffer::compare_scalar`] ANDed with this buffer's mask.
+    pub fn compare_scalar<R: Into<CellValue>>(&self, rel: Cmp, rhs: R) -> Mask {
+        self.0.compare_scalar_raw(rel, self.1.dev_ptr(), rhs.into())
+    }
+
+    /// `sel[i] ? (a[i], amask[i]) : (b[i], bmask[i])` in one launch (`ec_masked_select`); different cell types meet in their union.
+    pub fn select(sel: &Mask, a: &MaskedCellBuffer, b: &MaskedCellBuffer) -> Result<Self> {
+        if a.0.ct != b.0.ct {
+            let u = a.0.ct.union(b.0.ct);
+            return Self::select(sel, &a.convert(u)?, &b.convert(u)?);
+        }
+        let n = sel.len().min(a.0.len()).min(b.0.len());
+        let cells = CellBuffer::uninit(a.0.ct, n);
+        let mask = Mask::uninit(n);
+        check(unsafe {
+            ec_masked_select(
+                a.0.ct as u8, a.0.dev_ptr(), a.1.dev_ptr(), b.0.dev_ptr(), b.1.dev_ptr(), sel.dev_ptr(), n, cells.mem.ptr(), mask.dev_ptr_mut(), stream(),
+            )
+        })?;
+        Ok(MaskedCellBuffer(cells, mask))
+    }
+
+    /// This buffer's cell where it is valid, else `other`'s cell with `other`'s validity (cloud fill).
+    pub fn or_else(&self, other: &MaskedCellBuffer) -> Result<Self> {
+        Self::select(&self.1, self, other)
     }
 
     /// [`CellBuffer::stats`] over the valid cells: a masked-out cell contributes nothing, whatever it holds.

@@ -13,7 +13,7 @@
 use crate::device::stream;
 use crate::error::{check, must, Result};
 use crate::ffi::*;
-use crate::{BufferOps, CellBuffer, CellEncoding, CellType, CellValue, Stats};
+use crate::{BufferOps, CellBuffer, CellEncoding, CellType, CellValue, Cmp, Stats};
 #[cfg(feature = "masked")]
 use crate::Mask;
 use std::os::raw::c_void;
@@ -191,6 +191,30 @@ impl ShardedCellBuffer<'_> {
         check(unsafe {
             ec_sharded_binop(self.group.g, op, self.ct as u8, self.const_ptrs().as_ptr(), rhs.ct as u8, rhs.const_ptrs().as_ptr(),
                              self.lens.as_ptr(), outs.as_ptr())
+        })?;
+        Ok(out)
+    }
+
+    /// [`CellBuffer::compare`] on every shard (no communication): a `UInt8` raster of 0 / 1 bytes cut the same way.
+    pub fn compare(&self, rel: Cmp, rhs: &Self) -> Result<Self> {
+        assert_eq!(self.lens, rhs.lens, "operands must be sharded identically");
+        let out = self.alloc_like(CellType::UInt8)?;
+        let outs: Vec<*mut u8> = out.ptrs.iter().map(|p| *p as *mut u8).collect();
+        check(unsafe {
+            ec_sharded_compare(self.group.g, rel as i32, self.ct as u8, self.const_ptrs().as_ptr(), ptr::null(), rhs.ct as u8,
+                               rhs.const_ptrs().as_ptr(), ptr::null(), self.lens.as_ptr(), outs.as_ptr())
+        })?;
+        Ok(out)
+    }
+
+    /// [`CellBuffer::compare_scalar`] on every shard.
+    pub fn compare_scalar<R: Into<CellValue>>(&self, rel: Cmp, rhs: R) -> Result<Self> {
+        let out = self.alloc_like(CellType::UInt8)?;
+        let outs: Vec<*mut u8> = out.ptrs.iter().map(|p| *p as *mut u8).collect();
+        let v = rhs.into().to_ffi();
+        check(unsafe {
+            ec_sharded_compare_scalar(self.group.g, rel as i32, self.ct as u8, self.const_ptrs().as_ptr(), ptr::null(), self.lens.as_ptr(), &v,
+                                      outs.as_ptr())
         })?;
         Ok(out)
     }

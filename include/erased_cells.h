@@ -458,6 +458,49 @@ ec_status ec_mask_counts(const uint8_t *m, size_t n, uint64_t *n_true, uint64_t 
 ec_status ec_mask_counts_device(const uint8_t *m, size_t n, uint64_t *counts2_dev, ec_stream stream);
 
 /* ---------------------------------------------------------------- *
+ * Per-cell order predicates as masks (`ndvi > 0.3`, `qa == 4`, `nir < red`), and the pick of cells by a mask.
+ * ---------------------------------------------------------------- */
+/* A relation is the truth table over Ordering (impl Ord for CellValue, src/value.rs:248-265): bit 0 = Less, bit 1 = Equal,
+ * bit 2 = Greater.  The entry points take it as an int32_t, as every enumeration crosses this ABI (ec_op). */
+typedef enum { EC_CMP_LT = 1, EC_CMP_EQ = 2, EC_CMP_LE = 3, EC_CMP_GT = 4, EC_CMP_NE = 5, EC_CMP_GE = 6 } ec_cmp;
+/* impl Ord / PartialEq for CellValue — src/value.rs:248-271, cell by cell:
+ *   out_mask[i] = (rel >> (1 + CellValue(l[i]).cmp(CellValue(r[i])))) & 1.
+ * Both cells are converted to CellType::union(lt, rt) first (`unify`, src/value.rs:103-107), exactly as the reference does: a
+ * u64 cell 2^53 + 1 and an i64 cell 2^53 are Equal (their union is Float64), two i64 cells 2^53 and 2^53 + 1 are not.  Integer
+ * unions compare naturally, f32 / f64 unions by total_cmp: -0.0 < +0.0, a negative NaN below -inf, a positive NaN above +inf,
+ * NaN == NaN for equal bits.  With masks the result is also ANDed with every mask given, in the same launch — the
+ * masked-operator rule of src/masked/masked_buffer.rs:326-335: a cell that is not valid satisfies no predicate.  `n` is the caller's zip-truncated length; n == 0 is a no-op.  No allocation, no synchronisation.
+ * EC_ERR_ARG (rel outside 1..6, a null pointer with n > 0) and EC_ERR_UNSUPPORTED_TYPE are decided before any device work and
+ * without a device.  This family launches at the default "map_u" whatever the knob says. */
+ec_status ec_compare(int32_t rel /* an ec_cmp */, ec_dtype lt, const void *l, const uint8_t *lmask_or_null,
+                     ec_dtype rt, const void *r, const uint8_t *rmask_or_null,
+                     size_t n, uint8_t *out_mask, ec_stream stream);
+/* The same with r[i] replaced by the scalar `rhs` (src/value.rs:248-271 with a CellValue on the right); the scalar's own type
+ * takes part in the union.  ec_compare_scalar(EC_CMP_NE, t, x, NULL, n, nd) is ec_mask_from_nodata(t, x, n, nd). */
+ec_status ec_compare_scalar(int32_t rel /* an ec_cmp */, ec_dtype lt, const void *l, const uint8_t *lmask_or_null,
+                            size_t n, const ec_value *rhs, uint8_t *out_mask, ec_stream stream);
+/* out[i] = sel[i] ? a[i] : b[i], moved by cell width; a, b and out have type t.  The two-buffer form of
+ * to_vec_with_nodata (src/masked/masked_buffer.rs:143-151), where b is a buffer instead of one nodata value: cloud fill,
+ * compositing.  out may be a or b (the in-place patch): a lane loads a group of cells before it stores the same group, the
+ * reason ec_mask_and may run in place.  Same refusals and guarantees as ec_compare. */
+ec_status ec_select(ec_dtype t, const void *a, const void *b, const uint8_t *sel, size_t n,
+                    void *out, ec_stream stream);
+/* ec_select that also writes out_mask[i] = sel[i] ? amask[i] : bmask[i] (src/masked/masked_buffer.rs:143-151 for two masked
+ * buffers).  With sel == amask this is "a where a is valid, else b".  out may be a or b and out_mask
+ * amask or bmask, as for ec_select. */
+ec_status ec_masked_select(ec_dtype t, const void *a, const uint8_t *amask, const void *b, const uint8_t *bmask,
+                           const uint8_t *sel, size_t n, void *out, uint8_t *out_mask, ec_stream stream);
+/* ec_compare / ec_compare_scalar on every shard of a group (src/value.rs:248-271 per cell), one pointer per shard as
+ * ec_sharded_mask_from_nodata; lmask_or_null / rmask_or_null are NULL or per-shard columns.  Refusals come back on the
+ * calling thread before anything is posted.  Fire-and-forget, no communication. */
+ec_status ec_sharded_compare(ec_shard_group *g, int32_t rel /* an ec_cmp */, ec_dtype lt, const void *const *l,
+                             const uint8_t *const *lmask_or_null, ec_dtype rt, const void *const *r,
+                             const uint8_t *const *rmask_or_null, const size_t *n, uint8_t *const *out_mask);
+ec_status ec_sharded_compare_scalar(ec_shard_group *g, int32_t rel /* an ec_cmp */, ec_dtype lt, const void *const *l,
+                                    const uint8_t *const *lmask_or_null, const size_t *n, const ec_value *rhs,
+                                    uint8_t *const *out_mask);
+
+/* ---------------------------------------------------------------- *
  * 2-D windows of a raster resident on the device.
  * ---------------------------------------------------------------- */
 /* RasterBandEx::read_cells / read_cells_masked(window, window_size, size, e_resample_alg) — src/gdal/rasterband.rs:82-125,
