@@ -546,6 +546,47 @@ extern "C" ec_status ec_sharded_compare_scalar(ec_shard_group* g, int32_t rel, e
     });
 }
 
+extern "C" ec_status ec_sharded_cast(ec_shard_group* g, int32_t mode, ec_dtype st_, const void* const* src, ec_dtype dt, void* const* dst,
+                                     const size_t* n) {
+    const char* what = "ec_sharded_cast";
+    ec_status st = check_group(g, what);
+    if (st != EC_OK) return st;
+    st = ec_cast(mode, st_, nullptr, dt, nullptr, 0, nullptr);  // mode and dtypes, before any device work
+    if (st != EC_OK) return st;
+    if (!src || !dst || !n) return set_error(EC_ERR_ARG, "%s: null argument", what);
+    auto sv = take(g, what, "src", src, n, &st);
+    auto dv = take(g, what, "dst", dst, n, &st);
+    if (st != EC_OK) return st;
+    std::lock_guard<std::mutex> lk(g->call_mu);
+    return post_each_shard(g, [g, mode, st_, dt, src = std::move(sv), dst = std::move(dv), n = copy_col(g, n)](int i) {
+        return ec_cast(mode, st_, src[i], dt, dst[i], n[i], g->streams[i]);
+    });
+}
+
+extern "C" ec_status ec_sharded_cast_scaled(ec_shard_group* g, ec_dtype st_, const void* const* src, const uint8_t* const* masks_or_null,
+                                            const size_t* n, double scale, double offset, ec_dtype dt, const ec_value* nodata_or_null,
+                                            void* const* dst) {
+    const char* what = "ec_sharded_cast_scaled";
+    ec_status st = check_group(g, what);
+    if (st != EC_OK) return st;
+    // the pairing of masks and nodata, its dtype, the dtypes, scale and offset, before any device work (n = 0: nothing is read)
+    st = ec_cast_scaled(st_, nullptr, reinterpret_cast<const uint8_t*>(masks_or_null), 0, scale, offset, dt, nodata_or_null, nullptr, nullptr);
+    if (st != EC_OK) return st;
+    if (!src || !dst || !n) return set_error(EC_ERR_ARG, "%s: null argument", what);
+    auto sv = take(g, what, "src", src, n, &st);
+    auto mv = take_optional(g, what, "masks", masks_or_null, n, &st);
+    auto dv = take(g, what, "dst", dst, n, &st);
+    if (st != EC_OK) return st;
+    const bool masked = nodata_or_null != nullptr;
+    const ec_value nd = masked ? *nodata_or_null : ec_value{};
+    std::lock_guard<std::mutex> lk(g->call_mu);
+    return post_each_shard(g, [g, st_, dt, scale, offset, masked, nd, src = std::move(sv), m = std::move(mv), dst = std::move(dv),
+                               n = copy_col(g, n)](int i) -> ec_status {
+        if (n[i] == 0) return EC_OK;  // an empty shard may have no mask pointer: not the "mask without nodata" refusal
+        return ec_cast_scaled(st_, src[i], m[i], n[i], scale, offset, dt, masked ? &nd : nullptr, dst[i], g->streams[i]);
+    });
+}
+
 extern "C" ec_status ec_sharded_fused(ec_shard_group* g, ec_op o1, ec_op o2, ec_op o3, const ec_dtype dt[4], const void* const* const p[4],
                                       const uint8_t* const* const masks_or_null[4], const ec_value* scalars_or_null, const size_t* n,
                                       double* const* out, uint8_t* const* out_mask_or_null) {

@@ -24,6 +24,7 @@
 // rows (f)-(h).
 #pragma once
 
+#include "ec_cast_cell.hpp"
 #include "ec_window_kernels.hpp"
 
 namespace ecd {
@@ -59,25 +60,10 @@ __device__ __forceinline__ uint64_t tap_cell(const ResampleAxis& a, uint64_t c) 
 }
 
 // r as a cell of type T: f64 as it is, f32 rounded to nearest even, integers rounded half away from zero by ONE f64 add and a
-// truncation, then saturated as Rust's `as` saturates (the 64-bit types compare in f64 before the cast).
+// truncation, then saturated as Rust's `as` saturates (the 64-bit types compare in f64 before the cast): round_cell, the one
+// definition of the rule (ec_cast_cell.hpp), which ec_cast's EC_CAST_ROUND shares.
 template <typename T>
-__device__ __forceinline__ T resample_cell_of(double r) {
-    if constexpr (sizeof(T) == 8 && is_fp<T>::value) return r;
-    else if constexpr (is_fp<T>::value) return static_cast<float>(r);
-    else {
-        const double v = __builtin_trunc(r + __builtin_copysign(0.5, r));
-        constexpr bool SIGNED = T(-1) < T(0);
-        if constexpr (sizeof(T) == 8 && !SIGNED) {
-            return v >= 18446744073709551616.0 ? ~uint64_t(0) : !(v > 0.0) ? uint64_t(0) : static_cast<uint64_t>(v);
-        } else if constexpr (sizeof(T) == 8) {
-            return v >= 9223372036854775808.0 ? INT64_MAX : v <= -9223372036854775808.0 ? INT64_MIN : v != v ? int64_t(0) : static_cast<int64_t>(v);
-        } else {
-            constexpr double lo = SIGNED ? -double(uint64_t(1) << (8 * sizeof(T) - 1)) : 0.0;
-            constexpr double hi = SIGNED ? double((uint64_t(1) << (8 * sizeof(T) - 1)) - 1) : double((uint64_t(1) << (8 * sizeof(T))) - 1);
-            return v != v ? T(0) : static_cast<T>(static_cast<int64_t>(v < lo ? lo : v > hi ? hi : v));
-        }
-    }
-}
+__device__ __forceinline__ T resample_cell_of(double r) { return round_cell<T>(r); }
 
 template <bool NT, typename T>
 __device__ __forceinline__ T resample_load(const T* p) {

@@ -488,6 +488,21 @@ public:
         check(ec_convert(static_cast<ec_dtype>(ct_), ptr(), static_cast<ec_dtype>(cell_type), out.ptr(), n_, current_stream()));
         return out;
     }
+    // ---- the cells in a storage cell type, for every pair of types (ec_cast) — where convert refuses a narrowing.  EC_CAST_ROUND: the
+    // storing rule (integers clamped, floats rounded half away from zero, then saturated, NaN -> 0); EC_CAST_AS: Rust's `as`.
+    CellBuffer cast(CellType cell_type, ec_cast_mode mode = EC_CAST_ROUND) const {
+        CellBuffer out(cell_type, n_);
+        check(ec_cast(mode, static_cast<ec_dtype>(ct_), ptr(), static_cast<ec_dtype>(cell_type), out.ptr(), n_, current_stream()));
+        return out;
+    }
+    // self * scale + offset (two rounded f64 steps) stored as `cell_type` by the EC_CAST_ROUND rule, in one launch (ec_cast_scaled);
+    // with `mask` and `nodata` (both or neither) a cell whose mask byte is 0 receives *nodata
+    CellBuffer to_scaled(CellType cell_type, double scale, double offset, const uint8_t* mask = nullptr, const CellValue* nodata = nullptr) const {
+        CellBuffer out(cell_type, n_);
+        check(ec_cast_scaled(static_cast<ec_dtype>(ct_), ptr(), mask, n_, scale, offset, static_cast<ec_dtype>(cell_type),
+                             nodata ? &nodata->raw() : nullptr, out.ptr(), current_stream()));
+        return out;
+    }
     std::pair<CellValue, CellValue> min_max() const {  // buffer.rs:169-173
         ec_value mn, mx;
         check(ec_min_max(static_cast<ec_dtype>(ct_), ptr(), nullptr, n_, &mn, &mx, current_stream()));
@@ -779,6 +794,13 @@ public:
         mask_.extend(m);
     }
     MaskedCellBuffer convert(CellType ct) const { return MaskedCellBuffer(buf_.convert(ct), mask_.clone()); }  // :200-206
+    // CellBuffer::cast of the cells; the mask travels unchanged
+    MaskedCellBuffer cast(CellType ct, ec_cast_mode mode = EC_CAST_ROUND) const { return MaskedCellBuffer(buf_.cast(ct, mode), mask_.clone()); }
+    // to_vec_with_nodata (:137-152) for a type the buffer does not fit into, scaled, in one launch, the result left on the device:
+    // a cell that is not valid receives `nodata` (of type `ct`) whatever it holds
+    CellBuffer to_scaled(CellType ct, double scale, double offset, const CellValue& nodata) const {
+        return buf_.to_scaled(ct, scale, offset, mask_.ptr(), &nodata);
+    }
     template <typename T> std::vector<T> to_vec() const { return buf_.to_vec<T>(); }
     template <typename T> std::vector<T> to_vec_with_nodata(NoData<T> no_data) const {  // :137-152
         CellBuffer conv = buf_.convert(CellEncoding<T>::cell_type());
@@ -1283,6 +1305,25 @@ public:
         std::vector<uint8_t*> o;
         for (void* p : out.ptrs_) o.push_back(static_cast<uint8_t*>(p));
         check(ec_sharded_compare_scalar(grp_->raw(), rel, static_cast<ec_dtype>(ct_), l.data(), nullptr, lens_.data(), &rhs.raw(), o.data()));
+        return out;
+    }
+    // CellBuffer::cast / to_scaled on every shard (no communication)
+    ShardedCellBuffer cast(CellType cell_type, ec_cast_mode mode = EC_CAST_ROUND) const {
+        ShardedCellBuffer out(*grp_, cell_type, lens_);
+        std::vector<const void*> src(ptrs_.begin(), ptrs_.end());
+        check(ec_sharded_cast(grp_->raw(), mode, static_cast<ec_dtype>(ct_), src.data(), static_cast<ec_dtype>(cell_type), out.ptrs_.data(), lens_.data()));
+        return out;
+    }
+    // `mask` (a UInt8 buffer of 0 / 1 bytes sharded like this one) and `nodata` (of type `cell_type`) together, or neither
+    ShardedCellBuffer to_scaled(CellType cell_type, double scale, double offset, const ShardedCellBuffer* mask = nullptr,
+                                const CellValue* nodata = nullptr) const {
+        if (mask && mask->lens_ != lens_) throw Error(EC_ERR_LENGTH, "the mask must be sharded like its operand");
+        ShardedCellBuffer out(*grp_, cell_type, lens_);
+        std::vector<const void*> src(ptrs_.begin(), ptrs_.end());
+        std::vector<const uint8_t*> m;
+        if (mask) for (void* p : mask->ptrs_) m.push_back(static_cast<const uint8_t*>(p));
+        check(ec_sharded_cast_scaled(grp_->raw(), static_cast<ec_dtype>(ct_), src.data(), mask ? m.data() : nullptr, lens_.data(), scale, offset,
+                                     static_cast<ec_dtype>(cell_type), nodata ? &nodata->raw() : nullptr, out.ptrs_.data()));
         return out;
     }
     // BufferOps::min_max of the whole raster (buffer.rs:169-173): per-shard keys, one all-reduce(MAX), decode

@@ -21,6 +21,7 @@ EC_RESAMPLE_NEAREST, EC_RESAMPLE_BILINEAR, EC_RESAMPLE_AVERAGE = 0, 1, 5  # ec_r
 EC_WINDOW_MAX_REDUCTION = 64
 # ec_cmp: a relation is the truth table over Ordering — bit 0 Less, bit 1 Equal, bit 2 Greater
 EC_CMP_LT, EC_CMP_EQ, EC_CMP_LE, EC_CMP_GT, EC_CMP_NE, EC_CMP_GE = 1, 2, 3, 4, 5, 6
+EC_CAST_AS, EC_CAST_ROUND = 0, 1  # ec_cast_mode: Rust's `as` / the storing rule (clamp, round half away from zero)
 
 
 class _Payload(C.Union):
@@ -174,6 +175,10 @@ SIGNATURES = {
     "ec_masked_select": (I32, [C.c_uint8, VP, U8P, VP, U8P, U8P, SZ, VP, U8P, VP]),
     "ec_sharded_compare": (I32, [VP, I32, C.c_uint8, PVP, PVP, C.c_uint8, PVP, PVP, PSZ, PVP]),
     "ec_sharded_compare_scalar": (I32, [VP, I32, C.c_uint8, PVP, PVP, PSZ, PV, PVP]),
+    "ec_cast": (I32, [I32, C.c_uint8, VP, C.c_uint8, VP, SZ, VP]),
+    "ec_cast_scaled": (I32, [C.c_uint8, VP, U8P, SZ, C.c_double, C.c_double, C.c_uint8, PV, VP, VP]),
+    "ec_sharded_cast": (I32, [VP, I32, C.c_uint8, PVP, C.c_uint8, PVP, PSZ]),
+    "ec_sharded_cast_scaled": (I32, [VP, C.c_uint8, PVP, PVP, PSZ, C.c_double, C.c_double, C.c_uint8, PV, PVP]),
     "ec_stats_device": (I32, [C.c_uint8, VP, U8P, SZ, VP, VP]),
     "ec_stats_fold": (I32, [VP, I32, VP]),
     "ec_stats_compute": (I32, [C.c_uint8, VP, U8P, SZ, VP, VP]),

@@ -20,7 +20,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_RESAMPLE_AVERAGE, EC_RESAMPLE_BILINEAR, EcError, EcStats, EcValue, check, lib
+from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_RESAMPLE_AVERAGE, EC_RESAMPLE_BILINEAR, EcError, EcStats, EcValue, check, lib
 
 # CellType (src/ctype.rs:11-20; order of with_ct!, src/lib.rs:89-98)
 UInt8, UInt16, UInt32, UInt64, Int8, Int16, Int32, Int64, Float32, Float64 = range(10)
@@ -402,6 +402,27 @@ def _compare(rel, lhs: "CellBuffer", lmask, rhs, rmask=None) -> "Mask":
     return out
 
 
+# the spellings of an ec_cast_mode
+CAST_MODES = {"as": EC_CAST_AS, "round": EC_CAST_ROUND}
+
+
+def _cast_mode(mode) -> int:
+    """the ec_cast_mode number of "as" / "round" or of an ec_cast_mode value; anything else is refused"""
+    m = CAST_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) not in (EC_CAST_AS, EC_CAST_ROUND):
+        raise EcError(EC_ERR_ARG, f"cast: mode {mode!r} is not one of {sorted(CAST_MODES)} or an ec_cast_mode value")
+    return int(m)
+
+
+def _to_scaled(buf: "CellBuffer", mask, ct: int, scale, offset, nd) -> "CellBuffer":
+    """ec_cast_scaled of `buf` (with `mask` and the nodata CellValue `nd`, or neither) into a new buffer of type ct"""
+    out = CellBuffer.empty(buf.n, ct)
+    ev = nd.to_ec() if nd is not None else None
+    check(lib().ec_cast_scaled(buf.ct, buf.mem.ptr, mask.mem.ptr if ev is not None else None, buf.n, float(scale), float(offset), ct,
+                               C.byref(ev) if ev is not None else None, out.mem.ptr, _stream))
+    return out
+
+
 # --------------------------------------------------------------------------- CellBuffer
 @dataclasses.dataclass(frozen=True)
 class Stats:
@@ -567,6 +588,20 @@ class CellBuffer:
         out = CellBuffer.empty(self.n, ct)
         check(lib().ec_convert(self.ct, self.mem.ptr, ct, out.mem.ptr, self.n, _stream))
         return out
+
+    def cast(self, ct: int, mode="round") -> "CellBuffer":
+        """The cells as type `ct`, for every pair of types (ec_cast) — where `convert` refuses a narrowing.  mode "round": the
+        storing rule (integers clamped to the range, floats rounded half away from zero, then saturated, NaN -> 0); mode "as":
+        Rust's `as` (integers wrap, floats truncate toward zero and saturate).  A pair that fits is `convert` in either mode."""
+        m = _cast_mode(mode)
+        out = CellBuffer.empty(self.n, ct)
+        check(lib().ec_cast(m, self.ct, self.mem.ptr, ct, out.mem.ptr, self.n, _stream))
+        return out
+
+    def to_scaled(self, ct: int, scale: float, offset: float) -> "CellBuffer":
+        """`self * scale + offset` (two rounded f64 steps) stored as type `ct` by the "round" rule, in one launch (ec_cast_scaled):
+        `ndvi.to_scaled(Int16, 10000.0, 0.0)`."""
+        return _to_scaled(self, None, ct, scale, offset, None)
 
     def to_vec(self, ct: Optional[int] = None) -> np.ndarray:
         ct = self.ct if ct is None else ct
@@ -933,6 +968,17 @@ class MaskedCellBuffer:
 
     def to_vec(self, ct: Optional[int] = None) -> np.ndarray:
         return self._buf.to_vec(ct)
+
+    def cast(self, ct: int, mode="round") -> "MaskedCellBuffer":
+        """`CellBuffer.cast` of the cells; the mask travels unchanged."""
+        return MaskedCellBuffer(self._buf.cast(ct, mode), self._mask.clone())
+
+    def to_scaled(self, ct: int, scale: float, offset: float, no_data: NoData) -> CellBuffer:
+        """`CellBuffer.to_scaled` where a cell that is not valid receives `no_data.value()` whatever it holds, in one launch:
+        to_vec_with_nodata (masked_buffer.rs:137-152) for a type the buffer does not fit into, the result left on the device.
+        NoData.none() stores every cell."""
+        nd = no_data.value(ct)
+        return _to_scaled(self._buf, self._mask if nd is not None else None, ct, scale, offset, nd)
 
     def to_vec_with_nodata(self, ct: int, no_data: NoData) -> np.ndarray:
         """masked_buffer.rs:137-152: convert to T, then masked cells become no_data.value()."""

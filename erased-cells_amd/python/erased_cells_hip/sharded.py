@@ -210,6 +210,22 @@ class ShardGroup:
             check(lib().ec_sharded_compare_scalar(self.handle, r, l.ct, l.ptrs, lm, lens, C.byref(v), out.ptrs))
         return out
 
+    def cast(self, src: ShardedBuffer, ct: int, mode="round") -> ShardedBuffer:
+        """`CellBuffer.cast` on every shard, fire-and-forget.  Returns the sharded buffer of type `ct`."""
+        m = B._cast_mode(mode)
+        out = self.alloc(ct, src.lens)
+        check(lib().ec_sharded_cast(self.handle, m, src.ct, src.ptrs, ct, out.ptrs, (C.c_size_t * self.n)(*src.lens)))
+        return out
+
+    def to_scaled(self, src: ShardedBuffer, ct: int, scale: float, offset: float, mask: ShardedBuffer = None, no_data=None) -> ShardedBuffer:
+        """`to_scaled` on every shard, fire-and-forget: `mask` (sharded like `src`) and the nodata scalar `no_data` together, or neither."""
+        assert mask is None or mask.lens == src.lens, "the mask must be sharded like its operand"
+        out = self.alloc(ct, src.lens)
+        ev = B.CellValue(ct, no_data.value if isinstance(no_data, B.CellValue) else no_data).to_ec() if no_data is not None else None
+        check(lib().ec_sharded_cast_scaled(self.handle, src.ct, src.ptrs, mask.ptrs if mask is not None else None, (C.c_size_t * self.n)(*src.lens),
+                                           float(scale), float(offset), ct, C.byref(ev) if ev is not None else None, out.ptrs))
+        return out
+
     def program(self, streams, scalars, steps, masks=None):
         """An expression program (`fused.program`: steps `(op, a, b, dst)`) on every shard, fire-and-forget: `streams` up to four
         identically sharded buffers, `masks` (optional) one sharded mask per stream.  Returns the f64 result, or

@@ -119,6 +119,43 @@ impl CellBuffer {
     }
 }
 
+/// How [`CellBuffer::cast`] turns a cell into a narrower type (`ec_cast_mode`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum CastMode {
+    /// Rust's `as`: integers keep their low bits, floats truncate toward zero and saturate, NaN becomes 0.
+    As = EC_CAST_AS,
+    /// The storing rule: integers are clamped to the range, floats rounded half away from zero and saturated, NaN becomes 0.
+    Round = EC_CAST_ROUND,
+}
+
+impl CellBuffer {
+    /// The cells as type `cell_type`, for every pair of types — where `convert` refuses a narrowing.  A pair that fits is
+    /// `convert` in either mode.  One launch.
+    pub fn cast(&self, cell_type: CellType, mode: CastMode) -> Result<CellBuffer> {
+        let out = Self::uninit(cell_type, self.len);
+        check(unsafe { ec_cast(mode as i32, self.ct as u8, self.dev_ptr(), cell_type as u8, out.mem.ptr(), self.len, stream()) })?;
+        Ok(out)
+    }
+
+    /// `ec_cast_scaled` with a mask and a nodata value of type `cell_type` (both, or a null pointer and `None`).
+    pub(crate) fn to_scaled_raw(&self, cell_type: CellType, scale: f64, offset: f64, mask: *const u8, nodata: Option<CellValue>) -> Result<CellBuffer> {
+        let out = Self::uninit(cell_type, self.len);
+        let marker = nodata.map(|v| v.to_ffi());
+        let marker_ptr = marker.as_ref().map_or(std::ptr::null(), |m| m as *const ec_value);
+        check(unsafe {
+            ec_cast_scaled(self.ct as u8, self.dev_ptr(), mask, self.len, scale, offset, cell_type as u8, marker_ptr, out.mem.ptr(), stream())
+        })?;
+        Ok(out)
+    }
+
+    /// `self * scale + offset` (two rounded f64 steps, never an fma) stored as `cell_type` by the [`CastMode::Round`] rule, in
+    /// one launch: `ndvi.to_scaled(CellType::Int16, 10000.0, 0.0)`.
+    pub fn to_scaled(&self, cell_type: CellType, scale: f64, offset: f64) -> Result<CellBuffer> {
+        self.to_scaled_raw(cell_type, scale, offset, std::ptr::null(), None)
+    }
+}
+
 impl CellBuffer {
     /// count, min, max, sum, mean and population stddev in one pass over the cells where they are.  `mask`: the device
     /// bytes of a mask of the same length, or null.

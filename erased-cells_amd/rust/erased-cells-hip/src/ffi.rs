@@ -47,6 +47,9 @@ pub const EC_CMP_LE: i32 = 3;
 pub const EC_CMP_GT: i32 = 4;
 pub const EC_CMP_NE: i32 = 5;
 pub const EC_CMP_GE: i32 = 6;
+/// `ec_cast_mode`: Rust's `as`, or the storing rule — clamp, round half away from zero, saturate (`ec_cast` takes it as an `i32`).
+pub const EC_CAST_AS: i32 = 0;
+pub const EC_CAST_ROUND: i32 = 1;
 
 /// Mirrors `ec_value`: tag + 8-byte payload, 16 bytes.
 #[repr(C)]
@@ -171,6 +174,10 @@ extern "C" {
                      s: ec_stream) -> ec_status;
     pub fn ec_masked_select(t: ec_dtype, a: *const c_void, amask: *const u8, b: *const c_void, bmask: *const u8,
                             sel: *const u8, n: usize, out: *mut c_void, out_mask: *mut u8, s: ec_stream) -> ec_status;
+    // the cells in a storage cell type, for all 100 type pairs (never EC_ERR_NARROWING), and the storing direction of a scale and offset
+    pub fn ec_cast(mode: i32, st: ec_dtype, src: *const c_void, dt: ec_dtype, dst: *mut c_void, n: usize, s: ec_stream) -> ec_status;
+    pub fn ec_cast_scaled(st: ec_dtype, src: *const c_void, mask_or_null: *const u8, n: usize, scale: f64, offset: f64,
+                          dt: ec_dtype, nodata_or_null: *const ec_value, dst: *mut c_void, s: ec_stream) -> ec_status;
     pub fn ec_mask_and(l: *const u8, r: *const u8, n: usize, out: *mut u8, s: ec_stream) -> ec_status;
     pub fn ec_mask_or(l: *const u8, r: *const u8, n: usize, out: *mut u8, s: ec_stream) -> ec_status;
     pub fn ec_mask_not(m: *const u8, n: usize, out: *mut u8, s: ec_stream) -> ec_status;
@@ -243,6 +250,11 @@ extern "C" {
     pub fn ec_sharded_compare_scalar(g: *mut ec_shard_group, rel: i32, lt: ec_dtype, l: *const *const c_void,
                                      lmask_or_null: *const *const u8, n: *const usize, rhs: *const ec_value,
                                      out_mask: *const *mut u8) -> ec_status;
+    pub fn ec_sharded_cast(g: *mut ec_shard_group, mode: i32, st: ec_dtype, src: *const *const c_void, dt: ec_dtype,
+                           dst: *const *mut c_void, n: *const usize) -> ec_status;
+    pub fn ec_sharded_cast_scaled(g: *mut ec_shard_group, st: ec_dtype, src: *const *const c_void,
+                                  masks_or_null: *const *const u8, n: *const usize, scale: f64, offset: f64, dt: ec_dtype,
+                                  nodata_or_null: *const ec_value, dst: *const *mut c_void) -> ec_status;
     pub fn ec_sharded_fused(g: *mut ec_shard_group, o1: ec_op, o2: ec_op, o3: ec_op, dt: *const ec_dtype,
                             p: *const *const *const c_void, masks_or_null: *const *const *const u8,
                             scalars_or_null: *const ec_value, n: *const usize, out: *const *mut f64,

@@ -11,7 +11,7 @@
 use crate::device::stream;
 use crate::error::{check, must, Result};
 use crate::ffi::*;
-use crate::{BufferOps, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Cmp, Mask, NoData, ResampleAlg, Stats};
+use crate::{BufferOps, CastMode, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Cmp, Mask, NoData, ResampleAlg, Stats};
 use std::fmt::{Debug, Formatter};
 use std::ops::{Add, Div, Mul, Neg, Sub};
 
@@ -98,6 +98,20 @@ impl MaskedCellBuffer {
     /// This buffer's cell where it is valid, else `other`'s cell with `other`'s validity (cloud fill).
     pub fn or_else(&self, other: &MaskedCellBuffer) -> Result<Self> {
         Self::select(&self.1, self, other)
+    }
+
+    /// [`CellBuffer::cast`] of the cells; the mask travels unchanged.
+    pub fn cast(&self, cell_type: CellType, mode: CastMode) -> Result<Self> {
+        Ok(MaskedCellBuffer(self.0.cast(cell_type, mode)?, self.1.clone()))
+    }
+
+    /// [`CellBuffer::to_scaled`] where a cell that is not valid receives `no_data`'s value whatever it holds, in one launch:
+    /// `to_vec_with_nodata` for a type the buffer does not fit into, the result left on the device.  `NoData::None` stores every cell.
+    pub fn to_scaled<T: CellEncoding>(&self, scale: f64, offset: f64, no_data: NoData<T>) -> Result<CellBuffer> {
+        match no_data.value() {
+            Some(v) => self.0.to_scaled_raw(T::cell_type(), scale, offset, self.1.dev_ptr(), Some(CellValue::new(v))),
+            None => self.0.to_scaled(T::cell_type(), scale, offset),
+        }
     }
 
     /// [`CellBuffer::stats`] over the valid cells: a masked-out cell contributes nothing, whatever it holds.

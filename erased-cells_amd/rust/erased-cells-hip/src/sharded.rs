@@ -13,7 +13,7 @@
 use crate::device::stream;
 use crate::error::{check, must, Result};
 use crate::ffi::*;
-use crate::{BufferOps, CellBuffer, CellEncoding, CellType, CellValue, Cmp, Stats};
+use crate::{BufferOps, CastMode, CellBuffer, CellEncoding, CellType, CellValue, Cmp, Stats};
 #[cfg(feature = "masked")]
 use crate::Mask;
 use std::os::raw::c_void;
@@ -215,6 +215,39 @@ impl ShardedCellBuffer<'_> {
         check(unsafe {
             ec_sharded_compare_scalar(self.group.g, rel as i32, self.ct as u8, self.const_ptrs().as_ptr(), ptr::null(), self.lens.as_ptr(), &v,
                                       outs.as_ptr())
+        })?;
+        Ok(out)
+    }
+
+    /// [`CellBuffer::cast`] on every shard (no communication).
+    pub fn cast(&self, cell_type: CellType, mode: CastMode) -> Result<Self> {
+        let out = self.alloc_like(cell_type)?;
+        check(unsafe {
+            ec_sharded_cast(self.group.g, mode as i32, self.ct as u8, self.const_ptrs().as_ptr(), cell_type as u8, out.ptrs.as_ptr(), self.lens.as_ptr())
+        })?;
+        Ok(out)
+    }
+
+    /// [`CellBuffer::to_scaled`] on every shard.
+    pub fn to_scaled(&self, cell_type: CellType, scale: f64, offset: f64) -> Result<Self> {
+        let out = self.alloc_like(cell_type)?;
+        check(unsafe {
+            ec_sharded_cast_scaled(self.group.g, self.ct as u8, self.const_ptrs().as_ptr(), ptr::null(), self.lens.as_ptr(), scale, offset,
+                                   cell_type as u8, ptr::null(), out.ptrs.as_ptr())
+        })?;
+        Ok(out)
+    }
+
+    /// [`MaskedCellBuffer::to_scaled`] on every shard: `mask` is a `UInt8` raster of 0 / 1 bytes cut the same way, and a cell whose
+    /// mask byte is 0 receives `nodata` (a value of type `cell_type`).
+    pub fn to_scaled_masked(&self, cell_type: CellType, scale: f64, offset: f64, mask: &Self, nodata: CellValue) -> Result<Self> {
+        assert_eq!(self.lens, mask.lens, "the mask must be sharded like its operand");
+        let out = self.alloc_like(cell_type)?;
+        let masks: Vec<*const u8> = mask.ptrs.iter().map(|p| *p as *const u8).collect();
+        let marker = nodata.to_ffi();
+        check(unsafe {
+            ec_sharded_cast_scaled(self.group.g, self.ct as u8, self.const_ptrs().as_ptr(), masks.as_ptr(), self.lens.as_ptr(), scale, offset,
+                                   cell_type as u8, &marker, out.ptrs.as_ptr())
         })?;
         Ok(out)
     }

@@ -501,6 +501,45 @@ ec_status ec_sharded_compare_scalar(ec_shard_group *g, int32_t rel /* an ec_cmp 
                                     uint8_t *const *out_mask);
 
 /* ---------------------------------------------------------------- *
+ * Results in a storage cell type: f32 rasters, i16 scaled by 10000 with a nodata value, u8 classes.
+ * ---------------------------------------------------------------- */
+/* How ec_cast turns a cell into a narrower type.  It crosses the ABI as an int32_t, like ec_op and ec_cmp. */
+typedef enum { EC_CAST_AS = 0, EC_CAST_ROUND = 1 } ec_cast_mode;
+/* dst[i] = src[i] as a cell of type dt, for all 100 type pairs: never EC_ERR_NARROWING (CellValue::convert, src/value.rs:74-98,
+ * refuses 59 of them and carries the TODO this answers, src/value.rs:75).
+ *   A pair with ec_can_fit_into(st, dt), either mode: exactly ec_convert's cells (and its kernels).
+ *   EC_CAST_AS is Rust's `as`: integer to integer keeps the low bits (two's-complement wrap, sign extension); float to integer
+ *     truncates toward zero, saturates to dt's range, NaN -> 0; integer to f32 and f64 to f32 round to nearest even, overflow
+ *     to +-inf, a NaN stays a NaN of the same sign.
+ *   EC_CAST_ROUND is the storing rule: integer to integer is clamped to dt's range, exact in integers (an i64 cell 2^53 + 1
+ *     to u64 stays 2^53 + 1); float to integer is trunc(x + copysign(0.5, x)) on the cell widened to f64 — half away from zero
+ *     by ONE f64 add, the rule of ec_window_resample — then saturated, the 64-bit limits compared in f64, NaN -> 0; into f32
+ *     as EC_CAST_AS.
+ * dst must not overlap src.  Asynchronous, no allocation, no synchronisation, capturable; writes exactly n cells of dst, at
+ * any cell offset of src and dst.  EC_ERR_ARG (a mode outside {0, 1}, a null pointer with n > 0) and EC_ERR_UNSUPPORTED_TYPE
+ * are decided before any device work and without a device; n == 0 is EC_OK and launches nothing.  This family launches at the
+ * default "map_u" whatever the knob says. */
+ec_status ec_cast(int32_t mode /* an ec_cast_mode */, ec_dtype st, const void *src, ec_dtype dt, void *dst, size_t n,
+                  ec_stream stream);
+/* The storing direction of a scale and offset (the reading direction is the catalogue program a * k0 + k1):
+ *   y = to_f64(src[i]) * scale + offset, the product and the sum rounded individually — never an fma;
+ *   dst[i] = y for Float64, EC_CAST_ROUND of y otherwise.
+ * With a mask, a cell whose mask byte is 0 receives *nodata_or_null, whatever the cell holds (a NaN leaves no trace):
+ * to_vec_with_nodata (src/masked/masked_buffer.rs:137-152) for a type the buffer does not fit into, in one launch.
+ * EC_ERR_ARG besides ec_cast's: mask_or_null and nodata_or_null not both given or both NULL, nodata->dtype != dt, scale or
+ * offset not finite.  dst must not overlap src or the mask.  Same guarantees as ec_cast. */
+ec_status ec_cast_scaled(ec_dtype st, const void *src, const uint8_t *mask_or_null, size_t n,
+                         double scale, double offset,
+                         ec_dtype dt, const ec_value *nodata_or_null, void *dst, ec_stream stream);
+/* ec_cast / ec_cast_scaled on every shard of a group, one pointer per shard as ec_sharded_convert; masks_or_null is NULL or a
+ * per-shard column.  Refusals come back on the calling thread before anything is posted.  Fire-and-forget, no communication. */
+ec_status ec_sharded_cast(ec_shard_group *g, int32_t mode /* an ec_cast_mode */, ec_dtype st, const void *const *src,
+                          ec_dtype dt, void *const *dst, const size_t *n);
+ec_status ec_sharded_cast_scaled(ec_shard_group *g, ec_dtype st, const void *const *src,
+                                 const uint8_t *const *masks_or_null, const size_t *n, double scale, double offset,
+                                 ec_dtype dt, const ec_value *nodata_or_null, void *const *dst);
+
+/* ---------------------------------------------------------------- *
  * 2-D windows of a raster resident on the device.
  * ---------------------------------------------------------------- */
 /* RasterBandEx::read_cells / read_cells_masked(window, window_size, size, e_resample_alg) — src/gdal/rasterband.rs:82-125,
