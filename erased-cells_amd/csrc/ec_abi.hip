@@ -14,6 +14,7 @@
 #include <map>
 #include <string>
 
+#include "ec_dispatch.hpp"
 #include "ec_lattice.hpp"
 #include "ec_map_kernels.hpp"
 #include "ec_map_launch.hpp"
@@ -27,8 +28,6 @@ static_assert(kMaxReduceBlocks <= kFinalizeMaxParts, "the finalize kernels read 
 
 // first difference and mask counts: the default shape, its cell-wise branch inside the same kernel
 constexpr ReduceShape kScanShape = {kRBlock, kReduceU, 4, kRBlock, 4};
-
-static inline hipStream_t S(ec_stream s) { return static_cast<hipStream_t>(s); }
 
 // ------------------------------------------------------------------ convert
 template <typename Sx, typename Dx>
@@ -44,24 +43,8 @@ static ec_status launch_convert(const void* src, void* dst, size_t n, hipStream_
 }
 
 static ec_status dispatch_convert(int st, const void* src, int dt, void* dst, size_t n, hipStream_t s) {
-#define EC_ROW(SID, ST)                                                      \
-    case SID:                                                                \
-        switch (dt) {                                                        \
-            case EC_U8: return launch_convert<ST, uint8_t>(src, dst, n, s);  \
-            case EC_U16: return launch_convert<ST, uint16_t>(src, dst, n, s); \
-            case EC_U32: return launch_convert<ST, uint32_t>(src, dst, n, s); \
-            case EC_U64: return launch_convert<ST, uint64_t>(src, dst, n, s); \
-            case EC_I8: return launch_convert<ST, int8_t>(src, dst, n, s);   \
-            case EC_I16: return launch_convert<ST, int16_t>(src, dst, n, s); \
-            case EC_I32: return launch_convert<ST, int32_t>(src, dst, n, s); \
-            case EC_I64: return launch_convert<ST, int64_t>(src, dst, n, s); \
-            case EC_F32: return launch_convert<ST, float>(src, dst, n, s);   \
-            case EC_F64: return launch_convert<ST, double>(src, dst, n, s);  \
-        }                                                                    \
-        break;
-    switch (st) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "convert: bad dtype");
+    return ecl::with_cell_types(st, dt, [&](auto sc, auto dc) { return launch_convert<ecl::cell_t<decltype(sc)>, ecl::cell_t<decltype(dc)>>(src, dst, n, s); },
+                                [] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "convert: bad dtype"); });
 }
 
 // ------------------------------------------------------------------ min/max
@@ -94,20 +77,14 @@ static ec_status launch_min_max(const void* p, const uint8_t* mask, size_t n, in
 }
 
 static ec_status dispatch_min_max(int t, const void* p, const uint8_t* mask, size_t n, int64_t* keys2_dev, hipStream_t s) {
-#define EC_ROW(ID, T) case ID: return launch_min_max<T>(p, mask, n, keys2_dev, s);
-    switch (t) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "min_max: bad dtype");
+    return ecl::with_cell_type(t, [&](auto c) { return launch_min_max<ecl::cell_t<decltype(c)>>(p, mask, n, keys2_dev, s); },
+                               [] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "min_max: bad dtype"); });
 }
 
 template <typename T>
 static void decode_keys(const int64_t keys2[2], ec_value* mn, ec_value* mx) {
-    T a = key_value<T>(~keys2[0]), b = key_value<T>(keys2[1]);
-    std::memset(mn, 0, sizeof *mn);
-    std::memset(mx, 0, sizeof *mx);
-    mn->dtype = mx->dtype = static_cast<uint8_t>(ecl::dtype_of<T>::value);
-    std::memcpy(&mn->v, &a, sizeof a);
-    std::memcpy(&mx->v, &b, sizeof b);
+    ecl::put_value<T>(mn, ecl::dtype_of<T>::value, key_value<T>(~keys2[0]));
+    ecl::put_value<T>(mx, ecl::dtype_of<T>::value, key_value<T>(keys2[1]));
 }
 
 }  // namespace ecd
@@ -124,26 +101,18 @@ extern "C" int32_t ec_can_fit_into(ec_dtype src, ec_dtype dst) {
 extern "C" size_t ec_size_of(ec_dtype t) { return ecl::size_of(t); }
 extern "C" ec_dtype ec_neg_result_type(ec_dtype t) { return static_cast<ec_dtype>(ecl::neg_result(t)); }
 
-template <typename T>
-static void put_value(ec_value* out, int dtype, T x) {
-    std::memset(out, 0, sizeof *out);
-    out->dtype = static_cast<uint8_t>(dtype);
-    std::memcpy(&out->v, &x, sizeof x);
-}
+using ecl::put_value;
+using ecl::value_as;
 
 extern "C" ec_status ec_min_value(ec_dtype t, ec_value* out) {
     if (!out) return set_error(EC_ERR_ARG, "ec_min_value: null out");
-#define EC_ROW(ID, T) case ID: put_value<T>(out, ID, Limits<T>::lo); return EC_OK;
-    switch (t) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_min_value: bad dtype %d", int(t));
+    return ecl::with_cell_type(t, [&](auto c) -> ec_status { using T = ecl::cell_t<decltype(c)>; put_value<T>(out, t, Limits<T>::lo); return EC_OK; },
+                               [&] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_min_value: bad dtype %d", int(t)); });
 }
 extern "C" ec_status ec_max_value(ec_dtype t, ec_value* out) {
     if (!out) return set_error(EC_ERR_ARG, "ec_max_value: null out");
-#define EC_ROW(ID, T) case ID: put_value<T>(out, ID, Limits<T>::hi); return EC_OK;
-    switch (t) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_max_value: bad dtype %d", int(t));
+    return ecl::with_cell_type(t, [&](auto c) -> ec_status { using T = ecl::cell_t<decltype(c)>; put_value<T>(out, t, Limits<T>::hi); return EC_OK; },
+                               [&] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_max_value: bad dtype %d", int(t)); });
 }
 extern "C" ec_status ec_nodata_default(ec_dtype t, ec_value* out) {
     if (!out) return set_error(EC_ERR_ARG, "ec_nodata_default: null out");
@@ -152,21 +121,9 @@ extern "C" ec_status ec_nodata_default(ec_dtype t, ec_value* out) {
     return ec_min_value(t, out);                                                            // <int>::MIN
 }
 
-template <typename T>
-static double value_as_f64(const ec_value* v) { T x; std::memcpy(&x, &v->v, sizeof x); return static_cast<double>(x); }
-
 extern "C" double ec_value_to_f64(const ec_value* v) {
     if (!v) return 0.0;
-#define EC_ROW(ID, T) case ID: return value_as_f64<T>(v);
-    switch (v->dtype) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return 0.0;
-}
-
-template <typename Sx, typename Dx>
-static void value_cast(const ec_value* v, ec_value* out) {
-    Sx x; std::memcpy(&x, &v->v, sizeof x);
-    put_value<Dx>(out, ecl::dtype_of<Dx>::value, static_cast<Dx>(x));
+    return ecl::with_cell_type(v->dtype, [&](auto c) { return static_cast<double>(value_as<ecl::cell_t<decltype(c)>>(*v)); }, 0.0);
 }
 
 extern "C" ec_status ec_value_convert(const ec_value* v, ec_dtype dst, ec_value* out) {
@@ -174,24 +131,11 @@ extern "C" ec_status ec_value_convert(const ec_value* v, ec_dtype dst, ec_value*
     if (!ecl::valid(v->dtype) || !ecl::valid(dst)) return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_value_convert: bad dtype");
     if (!ecl::can_fit_into(v->dtype, dst)) return set_narrowing(v->dtype, dst);  // value.rs:79-81
     if (v->dtype == dst) { *out = *v; return EC_OK; }                            // value.rs:83-85
-#define EC_ROW(SID, ST)                                                \
-    case SID:                                                          \
-        switch (dst) {                                                 \
-            case EC_U8: value_cast<ST, uint8_t>(v, out); return EC_OK; \
-            case EC_U16: value_cast<ST, uint16_t>(v, out); return EC_OK; \
-            case EC_U32: value_cast<ST, uint32_t>(v, out); return EC_OK; \
-            case EC_U64: value_cast<ST, uint64_t>(v, out); return EC_OK; \
-            case EC_I8: value_cast<ST, int8_t>(v, out); return EC_OK;  \
-            case EC_I16: value_cast<ST, int16_t>(v, out); return EC_OK; \
-            case EC_I32: value_cast<ST, int32_t>(v, out); return EC_OK; \
-            case EC_I64: value_cast<ST, int64_t>(v, out); return EC_OK; \
-            case EC_F32: value_cast<ST, float>(v, out); return EC_OK;  \
-            case EC_F64: value_cast<ST, double>(v, out); return EC_OK; \
-        }                                                              \
-        break;
-    switch (v->dtype) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_value_convert: bad dtype");
+    return ecl::with_cell_types(v->dtype, dst, [&](auto sc, auto dc) -> ec_status {
+        using Dx = ecl::cell_t<decltype(dc)>;
+        put_value<Dx>(out, dst, static_cast<Dx>(value_as<ecl::cell_t<decltype(sc)>>(*v)));
+        return EC_OK;
+    }, [] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_value_convert: bad dtype"); });
 }
 
 extern "C" ec_status ec_shard_range(uint64_t n_rows, uint64_t n_cols, uint32_t shard, uint32_t n_shards,
@@ -263,14 +207,11 @@ extern "C" ec_status ec_neg(ec_dtype t, const void* in, size_t n, void* out, ec_
     if (!ecl::valid(t)) return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_neg: bad dtype %d", int(t));
     if (n == 0) return EC_OK;
     if (!in || !out) return set_error(EC_ERR_ARG, "ec_neg: null pointer");
-#define EC_ROW(ID, T)                                                                             \
-    case ID: {                                                                                    \
-        NegFn<T> fn{static_cast<const T*>(in), static_cast<typename NegOut<T>::type*>(out)};      \
-        return launch_map(fn, n, aligned16(in, out, out), S(stream), "neg");                      \
-    }
-    switch (t) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return EC_OK;
+    return ecl::with_cell_type(t, [&](auto c) {
+        using T = ecl::cell_t<decltype(c)>;
+        NegFn<T> fn{static_cast<const T*>(in), static_cast<typename NegOut<T>::type*>(out)};
+        return launch_map(fn, n, aligned16(in, out, out), S(stream), "neg");
+    }, kTypeChecked);
 }
 
 extern "C" ec_status ec_convert(ec_dtype st, const void* src, ec_dtype dt, void* dst, size_t n, ec_stream stream) {
@@ -285,8 +226,7 @@ extern "C" ec_status ec_convert(ec_dtype st, const void* src, ec_dtype dt, void*
 
 template <typename W>
 static ec_status fill_w(void* dst, size_t n, const ec_value* v, hipStream_t s) {
-    W w; std::memcpy(&w, &v->v, sizeof w);
-    FillFn<W> fn{static_cast<W*>(dst), w};
+    FillFn<W> fn{static_cast<W*>(dst), value_as<W>(*v)};
     return launch_map(fn, n, aligned16(dst, dst, dst), s, "fill");
 }
 
@@ -295,12 +235,7 @@ extern "C" ec_status ec_fill(ec_dtype t, void* dst, size_t n, const ec_value* va
     if (!ecl::valid(t) || !value || value->dtype != t) return set_error(EC_ERR_ARG, "ec_fill: value dtype must equal t");
     if (n == 0) return EC_OK;
     if (!dst) return set_error(EC_ERR_ARG, "ec_fill: null pointer");
-    switch (ecl::size_of(t)) {
-        case 1: return fill_w<uint8_t>(dst, n, value, S(stream));
-        case 2: return fill_w<uint16_t>(dst, n, value, S(stream));
-        case 4: return fill_w<uint32_t>(dst, n, value, S(stream));
-        default: return fill_w<uint64_t>(dst, n, value, S(stream));
-    }
+    return ecl::with_cell_width(ecl::size_of(t), [&](auto w) { return fill_w<ecl::cell_t<decltype(w)>>(dst, n, value, S(stream)); }, kTypeChecked);
 }
 
 // =================================================================== min/max
@@ -313,10 +248,8 @@ extern "C" ec_status ec_min_max_keys(ec_dtype t, const void* p, const uint8_t* m
 
 extern "C" ec_status ec_min_max_decode(ec_dtype t, const int64_t keys2_host[2], ec_value* mn, ec_value* mx) {
     if (!keys2_host || !mn || !mx) return set_error(EC_ERR_ARG, "ec_min_max_decode: null pointer");
-#define EC_ROW(ID, T) case ID: decode_keys<T>(keys2_host, mn, mx); return EC_OK;
-    switch (t) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_min_max_decode: bad dtype %d", int(t));
+    return ecl::with_cell_type(t, [&](auto c) -> ec_status { decode_keys<ecl::cell_t<decltype(c)>>(keys2_host, mn, mx); return EC_OK; },
+                               [&] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_min_max_decode: bad dtype %d", int(t)); });
 }
 
 extern "C" ec_status ec_min_max(ec_dtype t, const void* p, const uint8_t* mask_or_null, size_t n, ec_value* mn, ec_value* mx,
@@ -351,13 +284,7 @@ extern "C" ec_status ec_first_difference(ec_dtype t, const void* l, const void* 
     uint64_t first = 0;
     ec_status st = sync_result(S(stream), kResultWords, &first, sizeof first, [&](const Scratch& sc, int64_t* words) {
         unsigned grid = 0;
-        ec_status st2;
-        switch (ecl::size_of(t)) {
-            case 1: st2 = first_diff_w<uint8_t>(l, r, n, sc, S(stream), &grid); break;
-            case 2: st2 = first_diff_w<uint16_t>(l, r, n, sc, S(stream), &grid); break;
-            case 4: st2 = first_diff_w<uint32_t>(l, r, n, sc, S(stream), &grid); break;
-            default: st2 = first_diff_w<uint64_t>(l, r, n, sc, S(stream), &grid); break;
-        }
+        const ec_status st2 = ecl::with_cell_width(ecl::size_of(t), [&](auto w) { return first_diff_w<ecl::cell_t<decltype(w)>>(l, r, n, sc, S(stream), &grid); }, kTypeChecked);
         if (st2 != EC_OK) return st2;
         k_first_diff_finalize<<<1, kFinalizeBlock, 0, S(stream)>>>(reinterpret_cast<const uint64_t*>(sc.at(kScratchPartials)), static_cast<int>(grid),
                                                            reinterpret_cast<uint64_t*>(words));
@@ -394,17 +321,14 @@ extern "C" ec_status ec_buffer_cmp(ec_dtype lt, const void* l, size_t nl, ec_dty
     if (st != EC_OK) return st;
     st = ec_download(b, static_cast<const char*>(r) + idx * sz, sz, stream);
     if (st != EC_OK) return st;
-#define EC_ROW(ID, T) case ID: *ordering = order_cmp<T>(a, b); return EC_OK;
-    switch (lt) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
+    *ordering = ecl::with_cell_type(lt, [&](auto c) { return order_cmp<ecl::cell_t<decltype(c)>>(a, b); }, 0);  // lt was checked above
     return EC_OK;
 }
 
 // =================================================================== masks
 template <typename W>
 static ec_status mask_from_nd_w(const void* p, size_t n, const ec_value* nd, uint8_t* mask, hipStream_t s) {
-    W w; std::memcpy(&w, &nd->v, sizeof w);
-    MaskFromNodataFn<W> fn{static_cast<const W*>(p), mask, w};
+    MaskFromNodataFn<W> fn{static_cast<const W*>(p), mask, value_as<W>(*nd)};
     const bool al = aligned16(p, p, p) && aligned_to(mask, 16 / sizeof(W));
     return launch_map(fn, n, al, s, "mask_from_nodata");
 }
@@ -418,18 +342,12 @@ extern "C" ec_status ec_mask_from_nodata(ec_dtype t, const void* p, size_t n, co
     if (!p || !mask) return set_error(EC_ERR_ARG, "ec_mask_from_nodata: null pointer");
     if (!nd_or_null)  // NoData::None: nothing matches (nodata.rs:43-48) -> all true
         return check_hip(hipMemsetAsync(mask, 1, n, S(stream)), "hipMemsetAsync");
-    switch (ecl::size_of(t)) {
-        case 1: return mask_from_nd_w<uint8_t>(p, n, nd_or_null, mask, S(stream));
-        case 2: return mask_from_nd_w<uint16_t>(p, n, nd_or_null, mask, S(stream));
-        case 4: return mask_from_nd_w<uint32_t>(p, n, nd_or_null, mask, S(stream));
-        default: return mask_from_nd_w<uint64_t>(p, n, nd_or_null, mask, S(stream));
-    }
+    return ecl::with_cell_width(ecl::size_of(t), [&](auto w) { return mask_from_nd_w<ecl::cell_t<decltype(w)>>(p, n, nd_or_null, mask, S(stream)); }, kTypeChecked);
 }
 
 template <typename W>
 static ec_status mask_select_w(const void* p, const uint8_t* mask, size_t n, const ec_value* nd, void* out, hipStream_t s) {
-    W w; std::memcpy(&w, &nd->v, sizeof w);
-    MaskSelectFn<W> fn{static_cast<const W*>(p), mask, static_cast<W*>(out), w};
+    MaskSelectFn<W> fn{static_cast<const W*>(p), mask, static_cast<W*>(out), value_as<W>(*nd)};
     const bool al = aligned16(p, out, out) && aligned_to(mask, 16 / sizeof(W));
     return launch_map(fn, n, al, s, "mask_select");
 }
@@ -443,12 +361,7 @@ extern "C" ec_status ec_mask_select(ec_dtype t, const void* p, const uint8_t* ma
     if (!p || !out) return set_error(EC_ERR_ARG, "ec_mask_select: null pointer");
     if (!nd_or_null) return ec_copy(out, p, n * ecl::size_of(t), stream);  // masked_buffer.rs:149-151
     if (!mask) return set_error(EC_ERR_ARG, "ec_mask_select: null mask");
-    switch (ecl::size_of(t)) {
-        case 1: return mask_select_w<uint8_t>(p, mask, n, nd_or_null, out, S(stream));
-        case 2: return mask_select_w<uint16_t>(p, mask, n, nd_or_null, out, S(stream));
-        case 4: return mask_select_w<uint32_t>(p, mask, n, nd_or_null, out, S(stream));
-        default: return mask_select_w<uint64_t>(p, mask, n, nd_or_null, out, S(stream));
-    }
+    return ecl::with_cell_width(ecl::size_of(t), [&](auto w) { return mask_select_w<ecl::cell_t<decltype(w)>>(p, mask, n, nd_or_null, out, S(stream)); }, kTypeChecked);
 }
 
 extern "C" ec_status ec_mask_and(const uint8_t* l, const uint8_t* r, size_t n, uint8_t* out, ec_stream stream) {

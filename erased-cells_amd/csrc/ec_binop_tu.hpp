@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "ec_binop_kernels.hpp"
+#include "ec_dispatch.hpp"
 #include "ec_runtime.hpp"
 
 namespace ecd {
@@ -110,58 +111,24 @@ static ec_status launch_scalar(const void* l, double rhs, size_t n, double* out,
     return check_launch("binop_scalar(direct)");
 }
 
-// Type-erased dispatch: the 10-way × 10-way match `with_ct!` stamps in the reference.
+// Type-erased dispatch: the 10-way × 10-way match `with_ct!` stamps in the reference (with_cell_types, ec_dispatch.hpp).
 template <int OP>
 ec_status dispatch_binop(int lt, const void* l, int rt, const void* r, size_t n, double* out, hipStream_t s) {
-#define EC_ROW(LID, LT)                                                                         \
-    case LID:                                                                                   \
-        switch (rt) {                                                                           \
-            case EC_U8: return launch_binop_pair<LT, uint8_t, OP>(l, r, n, out, s);             \
-            case EC_U16: return launch_binop_pair<LT, uint16_t, OP>(l, r, n, out, s);           \
-            case EC_U32: return launch_binop_pair<LT, uint32_t, OP>(l, r, n, out, s);           \
-            case EC_U64: return launch_binop_pair<LT, uint64_t, OP>(l, r, n, out, s);           \
-            case EC_I8: return launch_binop_pair<LT, int8_t, OP>(l, r, n, out, s);              \
-            case EC_I16: return launch_binop_pair<LT, int16_t, OP>(l, r, n, out, s);            \
-            case EC_I32: return launch_binop_pair<LT, int32_t, OP>(l, r, n, out, s);            \
-            case EC_I64: return launch_binop_pair<LT, int64_t, OP>(l, r, n, out, s);            \
-            case EC_F32: return launch_binop_pair<LT, float, OP>(l, r, n, out, s);              \
-            case EC_F64: return launch_binop_pair<LT, double, OP>(l, r, n, out, s);             \
-        }                                                                                       \
-        break;
-    switch (lt) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "binop: bad dtype");
+    return ecl::with_cell_types(lt, rt, [&](auto lc, auto rc) { return launch_binop_pair<ecl::cell_t<decltype(lc)>, ecl::cell_t<decltype(rc)>, OP>(l, r, n, out, s); },
+                                [] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "binop: bad dtype"); });
 }
 
 template <int OP>
 ec_status dispatch_masked_binop(int lt, const void* l, const uint8_t* lm, int rt, const void* r, const uint8_t* rm,
                                 size_t n, double* out, uint8_t* om, hipStream_t s) {
-#define EC_ROW(LID, LT)                                                                                   \
-    case LID:                                                                                             \
-        switch (rt) {                                                                                     \
-            case EC_U8: return launch_masked_pair<LT, uint8_t, OP>(l, lm, r, rm, n, out, om, s);          \
-            case EC_U16: return launch_masked_pair<LT, uint16_t, OP>(l, lm, r, rm, n, out, om, s);        \
-            case EC_U32: return launch_masked_pair<LT, uint32_t, OP>(l, lm, r, rm, n, out, om, s);        \
-            case EC_U64: return launch_masked_pair<LT, uint64_t, OP>(l, lm, r, rm, n, out, om, s);        \
-            case EC_I8: return launch_masked_pair<LT, int8_t, OP>(l, lm, r, rm, n, out, om, s);           \
-            case EC_I16: return launch_masked_pair<LT, int16_t, OP>(l, lm, r, rm, n, out, om, s);         \
-            case EC_I32: return launch_masked_pair<LT, int32_t, OP>(l, lm, r, rm, n, out, om, s);         \
-            case EC_I64: return launch_masked_pair<LT, int64_t, OP>(l, lm, r, rm, n, out, om, s);         \
-            case EC_F32: return launch_masked_pair<LT, float, OP>(l, lm, r, rm, n, out, om, s);           \
-            case EC_F64: return launch_masked_pair<LT, double, OP>(l, lm, r, rm, n, out, om, s);          \
-        }                                                                                                 \
-        break;
-    switch (lt) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "masked_binop: bad dtype");
+    return ecl::with_cell_types(lt, rt, [&](auto lc, auto rc) { return launch_masked_pair<ecl::cell_t<decltype(lc)>, ecl::cell_t<decltype(rc)>, OP>(l, lm, r, rm, n, out, om, s); },
+                                [] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "masked_binop: bad dtype"); });
 }
 
 template <int OP>
 ec_status dispatch_binop_scalar(int lt, const void* l, double rhs, size_t n, double* out, hipStream_t s) {
-#define EC_ROW(LID, LT) case LID: return launch_scalar<LT, OP>(l, rhs, n, out, s);
-    switch (lt) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "binop_scalar: bad dtype");
+    return ecl::with_cell_type(lt, [&](auto lc) { return launch_scalar<ecl::cell_t<decltype(lc)>, OP>(l, rhs, n, out, s); },
+                               [] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "binop_scalar: bad dtype"); });
 }
 
 }  // namespace ecd

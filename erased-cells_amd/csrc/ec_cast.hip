@@ -4,20 +4,19 @@
 // Every refusal is decided on the host before any device work and before the library asks for a device.  The 41 pairs ec_convert
 // accepts go to ec_convert (the existing kernels, the existing copy for st == dt); the 59 others are CastFn, in both modes only
 // where the modes differ (an integer destination: 54 pairs).  The family launches at the default tile shape only
-// (launch_map_default_u), as ec_compare does.
+// (launch_map<kDefaultU>), as ec_compare does.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 
 #include "ec_cast_kernels.hpp"
+#include "ec_dispatch.hpp"
 #include "ec_lattice.hpp"
 #include "ec_map_launch.hpp"
 #include "ec_runtime.hpp"
 
 namespace ecd {
-
-static inline hipStream_t S(ec_stream s) { return static_cast<hipStream_t>(s); }
 
 constexpr bool valid_cast_mode(int mode) { return mode == EC_CAST_AS || mode == EC_CAST_ROUND; }
 
@@ -35,11 +34,11 @@ static ec_status launch_cast(int mode, const void* src, void* dst, size_t n, hip
         if constexpr (!is_fp<Dx>::value) {
             if (mode == EC_CAST_AS) {
                 CastFn<Sx, Dx, false> fn{static_cast<const Sx*>(src), static_cast<Dx*>(dst)};
-                return launch_map_default_u(fn, n, al, s, "cast(as)");
+                return launch_map<kDefaultU>(fn, n, al, s, "cast(as)");
             }
         }
         CastFn<Sx, Dx, true> fn{static_cast<const Sx*>(src), static_cast<Dx*>(dst)};  // into f32 the two modes are one kernel
-        return launch_map_default_u(fn, n, al, s, "cast(round)");
+        return launch_map<kDefaultU>(fn, n, al, s, "cast(round)");
     } else {
         (void)mode; (void)src; (void)dst; (void)n; (void)s;
         return set_error(EC_ERR_ARG, "cast: pair not instantiated");  // unreachable: the fitting pairs went to ec_convert
@@ -47,24 +46,8 @@ static ec_status launch_cast(int mode, const void* src, void* dst, size_t n, hip
 }
 
 static ec_status dispatch_cast(int mode, int st, const void* src, int dt, void* dst, size_t n, hipStream_t s) {
-#define EC_ROW(SID, ST)                                                          \
-    case SID:                                                                    \
-        switch (dt) {                                                            \
-            case EC_U8: return launch_cast<ST, uint8_t>(mode, src, dst, n, s);   \
-            case EC_U16: return launch_cast<ST, uint16_t>(mode, src, dst, n, s); \
-            case EC_U32: return launch_cast<ST, uint32_t>(mode, src, dst, n, s); \
-            case EC_U64: return launch_cast<ST, uint64_t>(mode, src, dst, n, s); \
-            case EC_I8: return launch_cast<ST, int8_t>(mode, src, dst, n, s);    \
-            case EC_I16: return launch_cast<ST, int16_t>(mode, src, dst, n, s);  \
-            case EC_I32: return launch_cast<ST, int32_t>(mode, src, dst, n, s);  \
-            case EC_I64: return launch_cast<ST, int64_t>(mode, src, dst, n, s);  \
-            case EC_F32: return launch_cast<ST, float>(mode, src, dst, n, s);    \
-            case EC_F64: return launch_cast<ST, double>(mode, src, dst, n, s);   \
-        }                                                                        \
-        break;
-    switch (st) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "cast: bad dtype");
+    return ecl::with_cell_types(st, dt, [&](auto sc, auto dc) { return launch_cast<ecl::cell_t<decltype(sc)>, ecl::cell_t<decltype(dc)>>(mode, src, dst, n, s); },
+                                [] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "cast: bad dtype"); });
 }
 
 template <typename Sx, typename Dx>
@@ -73,34 +56,17 @@ static ec_status launch_cast_scaled(const void* src, const uint8_t* mask, size_t
     constexpr int cpl = CastScaledFn<Sx, Dx, true>::CPL;
     const bool al = cast_aligned<Sx, Dx, cpl>(src, mask, dst);
     if (mask) {
-        Dx nd; std::memcpy(&nd, &nodata->v, sizeof nd);
-        CastScaledFn<Sx, Dx, true> fn{static_cast<const Sx*>(src), mask, static_cast<Dx*>(dst), scale, offset, nd};
-        return launch_map_default_u(fn, n, al, s, "cast_scaled(masked)");
+        CastScaledFn<Sx, Dx, true> fn{static_cast<const Sx*>(src), mask, static_cast<Dx*>(dst), scale, offset, ecl::value_as<Dx>(*nodata)};
+        return launch_map<kDefaultU>(fn, n, al, s, "cast_scaled(masked)");
     }
     CastScaledFn<Sx, Dx, false> fn{static_cast<const Sx*>(src), nullptr, static_cast<Dx*>(dst), scale, offset, Dx(0)};
-    return launch_map_default_u(fn, n, al, s, "cast_scaled");
+    return launch_map<kDefaultU>(fn, n, al, s, "cast_scaled");
 }
 
 static ec_status dispatch_cast_scaled(int st, const void* src, const uint8_t* mask, size_t n, double scale, double offset, int dt,
                                       const ec_value* nodata, void* dst, hipStream_t s) {
-#define EC_ROW(SID, ST)                                                                                          \
-    case SID:                                                                                                    \
-        switch (dt) {                                                                                            \
-            case EC_U8: return launch_cast_scaled<ST, uint8_t>(src, mask, n, scale, offset, nodata, dst, s);     \
-            case EC_U16: return launch_cast_scaled<ST, uint16_t>(src, mask, n, scale, offset, nodata, dst, s);   \
-            case EC_U32: return launch_cast_scaled<ST, uint32_t>(src, mask, n, scale, offset, nodata, dst, s);   \
-            case EC_U64: return launch_cast_scaled<ST, uint64_t>(src, mask, n, scale, offset, nodata, dst, s);   \
-            case EC_I8: return launch_cast_scaled<ST, int8_t>(src, mask, n, scale, offset, nodata, dst, s);      \
-            case EC_I16: return launch_cast_scaled<ST, int16_t>(src, mask, n, scale, offset, nodata, dst, s);    \
-            case EC_I32: return launch_cast_scaled<ST, int32_t>(src, mask, n, scale, offset, nodata, dst, s);    \
-            case EC_I64: return launch_cast_scaled<ST, int64_t>(src, mask, n, scale, offset, nodata, dst, s);    \
-            case EC_F32: return launch_cast_scaled<ST, float>(src, mask, n, scale, offset, nodata, dst, s);      \
-            case EC_F64: return launch_cast_scaled<ST, double>(src, mask, n, scale, offset, nodata, dst, s);     \
-        }                                                                                                        \
-        break;
-    switch (st) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "cast_scaled: bad dtype");
+    return ecl::with_cell_types(st, dt, [&](auto sc, auto dc) { return launch_cast_scaled<ecl::cell_t<decltype(sc)>, ecl::cell_t<decltype(dc)>>(src, mask, n, scale, offset, nodata, dst, s); },
+                                [] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "cast_scaled: bad dtype"); });
 }
 
 }  // namespace ecd

@@ -2,20 +2,19 @@
 // predicates as masks and the pick of cells by a mask, in a translation unit of their own so the build stays parallel.
 //
 // Every refusal is decided on the host before any device work and before the library asks for a device.  The family
-// launches at the default tile shape only (launch_map_default_u): 100 type pairs x 3 mask counts would otherwise triple
+// launches at the default tile shape only (launch_map<kDefaultU>): 100 type pairs x 3 mask counts would otherwise triple
 // over the "map_u" knob.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
 #include "ec_compare_kernels.hpp"
+#include "ec_dispatch.hpp"
 #include "ec_lattice.hpp"
 #include "ec_map_launch.hpp"
 #include "ec_runtime.hpp"
 
 namespace ecd {
-
-static inline hipStream_t S(ec_stream s) { return static_cast<hipStream_t>(s); }
 
 // the operands of a compare after the checks: up to two masks, in the order given
 struct CompareMasks {
@@ -32,7 +31,7 @@ static ec_status launch_compare_n(uint32_t rel, const void* l, const void* r, co
     CompareFn<L, R, NMASK> fn{static_cast<const L*>(l), static_cast<const R*>(r), ms.m[0], ms.m[1], out, rel};
     constexpr size_t cpl = CompareFn<L, R, NMASK>::CPL;
     const bool al = aligned16(l, r, l) && aligned_to(out, cpl) && (NMASK < 1 || aligned_to(ms.m[0], cpl)) && (NMASK < 2 || aligned_to(ms.m[1], cpl));
-    return launch_map_default_u(fn, n, al, s, "compare");
+    return launch_map<kDefaultU>(fn, n, al, s, "compare");
 }
 
 template <typename L, typename R>
@@ -46,38 +45,22 @@ static ec_status launch_compare(uint32_t rel, const void* l, const void* r, cons
 
 static ec_status dispatch_compare(uint32_t rel, int lt, const void* l, int rt, const void* r, const CompareMasks& ms, size_t n, uint8_t* out,
                                   hipStream_t s) {
-#define EC_ROW(LID, LT)                                                                  \
-    case LID:                                                                            \
-        switch (rt) {                                                                    \
-            case EC_U8: return launch_compare<LT, uint8_t>(rel, l, r, ms, n, out, s);    \
-            case EC_U16: return launch_compare<LT, uint16_t>(rel, l, r, ms, n, out, s);  \
-            case EC_U32: return launch_compare<LT, uint32_t>(rel, l, r, ms, n, out, s);  \
-            case EC_U64: return launch_compare<LT, uint64_t>(rel, l, r, ms, n, out, s);  \
-            case EC_I8: return launch_compare<LT, int8_t>(rel, l, r, ms, n, out, s);     \
-            case EC_I16: return launch_compare<LT, int16_t>(rel, l, r, ms, n, out, s);   \
-            case EC_I32: return launch_compare<LT, int32_t>(rel, l, r, ms, n, out, s);   \
-            case EC_I64: return launch_compare<LT, int64_t>(rel, l, r, ms, n, out, s);   \
-            case EC_F32: return launch_compare<LT, float>(rel, l, r, ms, n, out, s);     \
-            case EC_F64: return launch_compare<LT, double>(rel, l, r, ms, n, out, s);    \
-        }                                                                                \
-        break;
-    switch (lt) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "compare: bad dtype");
+    return ecl::with_cell_types(lt, rt, [&](auto lc, auto rc) { return launch_compare<ecl::cell_t<decltype(lc)>, ecl::cell_t<decltype(rc)>>(rel, l, r, ms, n, out, s); },
+                                [] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "compare: bad dtype"); });
 }
 
 template <typename L, typename UT>
 static ec_status launch_compare_scalar(uint32_t rel, const void* l, const uint8_t* mask, size_t n, const ec_value* rhs_u, uint8_t* out, hipStream_t s) {
     if constexpr (ecl::can_fit_into(ecl::dtype_of<L>::value, ecl::dtype_of<UT>::value)) {
-        UT v; std::memcpy(&v, &rhs_u->v, sizeof v);
+        const UT v = ecl::value_as<UT>(*rhs_u);
         constexpr size_t cpl = 16 / sizeof(L);
         const bool al = aligned16(l, l, l) && aligned_to(out, cpl) && (!mask || aligned_to(mask, cpl));
         if (mask) {
             CompareScalarFn<L, UT, 1> fn{static_cast<const L*>(l), mask, out, v, rel};
-            return launch_map_default_u(fn, n, al, s, "compare_scalar");
+            return launch_map<kDefaultU>(fn, n, al, s, "compare_scalar");
         }
         CompareScalarFn<L, UT, 0> fn{static_cast<const L*>(l), nullptr, out, v, rel};
-        return launch_map_default_u(fn, n, al, s, "compare_scalar");
+        return launch_map<kDefaultU>(fn, n, al, s, "compare_scalar");
     } else {
         (void)rel; (void)l; (void)mask; (void)n; (void)rhs_u; (void)out; (void)s;
         return set_error(EC_ERR_ARG, "compare_scalar: pair not instantiated");  // unreachable: ut is a union with lt
@@ -86,24 +69,8 @@ static ec_status launch_compare_scalar(uint32_t rel, const void* l, const uint8_
 
 static ec_status dispatch_compare_scalar(uint32_t rel, int lt, const void* l, const uint8_t* mask, size_t n, int ut, const ec_value* rhs_u,
                                          uint8_t* out, hipStream_t s) {
-#define EC_ROW(LID, LT)                                                                              \
-    case LID:                                                                                        \
-        switch (ut) {                                                                                \
-            case EC_U8: return launch_compare_scalar<LT, uint8_t>(rel, l, mask, n, rhs_u, out, s);   \
-            case EC_U16: return launch_compare_scalar<LT, uint16_t>(rel, l, mask, n, rhs_u, out, s); \
-            case EC_U32: return launch_compare_scalar<LT, uint32_t>(rel, l, mask, n, rhs_u, out, s); \
-            case EC_U64: return launch_compare_scalar<LT, uint64_t>(rel, l, mask, n, rhs_u, out, s); \
-            case EC_I8: return launch_compare_scalar<LT, int8_t>(rel, l, mask, n, rhs_u, out, s);    \
-            case EC_I16: return launch_compare_scalar<LT, int16_t>(rel, l, mask, n, rhs_u, out, s);  \
-            case EC_I32: return launch_compare_scalar<LT, int32_t>(rel, l, mask, n, rhs_u, out, s);  \
-            case EC_I64: return launch_compare_scalar<LT, int64_t>(rel, l, mask, n, rhs_u, out, s);  \
-            case EC_F32: return launch_compare_scalar<LT, float>(rel, l, mask, n, rhs_u, out, s);    \
-            case EC_F64: return launch_compare_scalar<LT, double>(rel, l, mask, n, rhs_u, out, s);   \
-        }                                                                                            \
-        break;
-    switch (lt) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "compare_scalar: bad dtype");
+    return ecl::with_cell_types(lt, ut, [&](auto lc, auto uc) { return launch_compare_scalar<ecl::cell_t<decltype(lc)>, ecl::cell_t<decltype(uc)>>(rel, l, mask, n, rhs_u, out, s); },
+                                [] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "compare_scalar: bad dtype"); });
 }
 
 template <typename W, bool MASKED>
@@ -113,18 +80,13 @@ static ec_status launch_select(const void* a, const uint8_t* am, const void* b, 
     constexpr size_t cpl = 16 / sizeof(W);
     const bool al = aligned16(a, b, out) && aligned_to(sel, cpl) &&
                     (!MASKED || (aligned_to(am, cpl) && aligned_to(bm, cpl) && aligned_to(om, cpl)));
-    return launch_map_default_u(fn, n, al, s, MASKED ? "masked_select" : "select");
+    return launch_map<kDefaultU>(fn, n, al, s, MASKED ? "masked_select" : "select");
 }
 
 template <bool MASKED>
 static ec_status dispatch_select(int t, const void* a, const uint8_t* am, const void* b, const uint8_t* bm, const uint8_t* sel, size_t n, void* out,
                                  uint8_t* om, hipStream_t s) {
-    switch (ecl::size_of(t)) {
-        case 1: return launch_select<uint8_t, MASKED>(a, am, b, bm, sel, n, out, om, s);
-        case 2: return launch_select<uint16_t, MASKED>(a, am, b, bm, sel, n, out, om, s);
-        case 4: return launch_select<uint32_t, MASKED>(a, am, b, bm, sel, n, out, om, s);
-        default: return launch_select<uint64_t, MASKED>(a, am, b, bm, sel, n, out, om, s);
-    }
+    return ecl::with_cell_width(ecl::size_of(t), [&](auto w) { return launch_select<ecl::cell_t<decltype(w)>, MASKED>(a, am, b, bm, sel, n, out, om, s); }, kTypeChecked);
 }
 
 }  // namespace ecd

@@ -17,16 +17,9 @@
 
 namespace ecd {
 
-template <int ID> struct cell_of;
-#define EC_CELL_OF(ID, T) template <> struct cell_of<ID> { using type = T; };
-EC_CELL_OF(EC_U8, uint8_t) EC_CELL_OF(EC_U16, uint16_t) EC_CELL_OF(EC_U32, uint32_t) EC_CELL_OF(EC_U64, uint64_t)
-EC_CELL_OF(EC_I8, int8_t) EC_CELL_OF(EC_I16, int16_t) EC_CELL_OF(EC_I32, int32_t) EC_CELL_OF(EC_I64, int64_t)
-EC_CELL_OF(EC_F32, float) EC_CELL_OF(EC_F64, double)
-#undef EC_CELL_OF
-
 template <typename L, typename R>
 struct union_cell {
-    using type = typename cell_of<ecl::union_of(ecl::dtype_of<L>::value, ecl::dtype_of<R>::value)>::type;
+    using type = typename ecl::cell_of<ecl::union_of(ecl::dtype_of<L>::value, ecl::dtype_of<R>::value)>::type;
 };
 
 constexpr bool valid_relation(int rel) { return rel >= 1 && rel <= 6; }

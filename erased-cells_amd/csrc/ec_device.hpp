@@ -22,19 +22,6 @@ namespace ecd {
 template <typename T, int N>
 using vec = T __attribute__((ext_vector_type(N)));
 
-// with_ct! (src/lib.rs:85-101): X(dtype code, C type)
-#define EC_WITH_CT(X)      \
-    X(EC_U8, uint8_t)      \
-    X(EC_U16, uint16_t)    \
-    X(EC_U32, uint32_t)    \
-    X(EC_U64, uint64_t)    \
-    X(EC_I8, int8_t)       \
-    X(EC_I16, int16_t)     \
-    X(EC_I32, int32_t)     \
-    X(EC_I64, int64_t)     \
-    X(EC_F32, float)       \
-    X(EC_F64, double)
-
 constexpr uint64_t kNegQNaN = 0xFFF8000000000000ull;  // x86-64 SSE default NaN
 constexpr uint64_t kQuietBit = 0x0008000000000000ull;
 

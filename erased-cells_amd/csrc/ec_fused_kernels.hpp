@@ -16,6 +16,7 @@
 // u16 + f32 0.77 vs 0.81, config 3 0.80 vs 0.79) and were removed; tools/legacy_fused_kernels.hpp keeps them for the A/B.)
 #pragma once
 
+#include "ec_lattice.hpp"  // EC_WITH_CT
 #include "ec_stream_tile.hpp"
 
 namespace ecd {

@@ -1,13 +1,27 @@
 // ec_lattice.hpp — CellType lattice as constexpr host functions.
 // Restates CellType::{is_integral,is_signed,size_of,union,can_fit_into}
 // (src/ctype.rs:55-131 of the reference); evaluated once per operation on the
-// host instead of ≥4 times per cell.
+// host instead of ≥4 times per cell.  Also the list of the ten cell types (EC_WITH_CT) and the type <-> code
+// maps generated from it; ec_dispatch.hpp switches over the same list.  No HIP include.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
 
 #include "erased_cells.h"
+
+// with_ct! (src/lib.rs:85-101): X(dtype code, C type) — the ten cell types, listed here and nowhere else
+#define EC_WITH_CT(X)      \
+    X(EC_U8, uint8_t)      \
+    X(EC_U16, uint16_t)    \
+    X(EC_U32, uint32_t)    \
+    X(EC_U64, uint64_t)    \
+    X(EC_I8, int8_t)       \
+    X(EC_I16, int16_t)     \
+    X(EC_I32, int32_t)     \
+    X(EC_I64, int64_t)     \
+    X(EC_F32, float)       \
+    X(EC_F64, double)
 
 namespace ecl {
 
@@ -44,11 +58,13 @@ constexpr int neg_result(int t) {                                               
     return t == EC_U8 ? EC_I16 : t == EC_U16 ? EC_I32 : (t == EC_U32 || t == EC_U64) ? EC_F64 : t;
 }
 
+// type -> code and code -> type, stamped from the list
 template <typename T> struct dtype_of;
-#define EC_DT(ID, T) template <> struct dtype_of<T> { static constexpr int value = ID; };
-EC_DT(EC_U8, uint8_t) EC_DT(EC_U16, uint16_t) EC_DT(EC_U32, uint32_t) EC_DT(EC_U64, uint64_t)
-EC_DT(EC_I8, int8_t) EC_DT(EC_I16, int16_t) EC_DT(EC_I32, int32_t) EC_DT(EC_I64, int64_t)
-EC_DT(EC_F32, float) EC_DT(EC_F64, double)
-#undef EC_DT
+template <int ID> struct cell_of;
+#define EC_CT(ID, T)                                                       \
+    template <> struct dtype_of<T> { static constexpr int value = ID; };   \
+    template <> struct cell_of<ID> { using type = T; };
+EC_WITH_CT(EC_CT)
+#undef EC_CT
 
 }  // namespace ecl

@@ -24,29 +24,24 @@ static void launch_map_u(const Fn& fn, size_t n, hipStream_t s) {
     k_map<Fn, U><<<grid_for(tiles), kBlock, lds, s>>>(fn, n, cache_plan(stream_bytes, 2));
 }
 
-template <typename Fn>
+// KNOB_U = false: the default tile shape only ("map_u" = 2, whatever the knob says) — for the kernel families with many type
+// pairs (ec_compare.hip, ec_cast.hip), which would otherwise triple their instantiation count over the knob.
+template <bool KNOB_U = true, typename Fn>
 static ec_status launch_map(const Fn& fn, size_t n, bool aligned, hipStream_t s, const char* what) {
     if (n == 0) return EC_OK;
     if (!aligned) {
         k_map_cellwise<Fn><<<grid_capped((n + kBlock - 1) / kBlock, 8), kBlock, 0, s>>>(fn, n);
-    } else {
+    } else if constexpr (KNOB_U) {
         switch (tuning().map_u) {  // groups of 16 B per lane per tile
             case 1: launch_map_u<Fn, 1>(fn, n, s); break;
             case 4: launch_map_u<Fn, 4>(fn, n, s); break;
             default: launch_map_u<Fn, 2>(fn, n, s); break;
         }
+    } else {
+        launch_map_u<Fn, 2>(fn, n, s);
     }
     return check_launch(what);
 }
-
-// The same at the default tile shape only ("map_u" = 2, whatever the knob says): for kernel families with many type pairs
-// (ec_compare.hip), which would otherwise triple their instantiation count over the knob.
-template <typename Fn>
-static ec_status launch_map_default_u(const Fn& fn, size_t n, bool aligned, hipStream_t s, const char* what) {
-    if (n == 0) return EC_OK;
-    if (!aligned) k_map_cellwise<Fn><<<grid_capped((n + kBlock - 1) / kBlock, 8), kBlock, 0, s>>>(fn, n);
-    else launch_map_u<Fn, 2>(fn, n, s);
-    return check_launch(what);
-}
+constexpr bool kDefaultU = false;  // launch_map<kDefaultU>(fn, ...)
 
 }  // namespace ecd

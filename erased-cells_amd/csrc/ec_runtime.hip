@@ -247,8 +247,6 @@ static void set_pool_threshold(hipMemPool_t pool) {
     (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
 }
 
-static inline hipStream_t S(ec_stream s) { return static_cast<hipStream_t>(s); }
-
 }  // namespace ecd
 
 using namespace ecd;

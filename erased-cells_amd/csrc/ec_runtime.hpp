@@ -74,6 +74,9 @@ ec_status set_narrowing(int src, int dst);
 std::atomic<int64_t>& lds_rule_launches();  // binop launches that took the LDS-staged variant by rule (ec_stat_get "binop_lds_rule_launches")
 ec_status check_launch(const char* what);
 ec_status check_hip(hipError_t e, const char* what);
+// `otherwise` of a dispatch (ec_dispatch.hpp) whose entry point refused a bad dtype with its own text before: never returned
+constexpr ec_status kTypeChecked = EC_ERR_UNSUPPORTED_TYPE;
+inline hipStream_t S(ec_stream s) { return static_cast<hipStream_t>(s); }  // the C ABI's stream handle as HIP's
 
 // Work on other devices from a thread that may have one of its own: remembers the calling thread's library device, if it has
 // one, and puts it back on destruction if it changed — on every path out of the scope, and without touching the thread's last

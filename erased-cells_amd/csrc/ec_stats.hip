@@ -5,6 +5,7 @@
 
 #include <cstring>
 
+#include "ec_dispatch.hpp"
 #include "ec_lattice.hpp"
 #include "ec_reduce_launch.hpp"
 #include "ec_runtime.hpp"
@@ -33,10 +34,8 @@ struct StatsReduction {
 };
 
 static ec_status dispatch_stats(int t, const void* p, const uint8_t* mask, size_t n, ec_moments* rec_dev, hipStream_t s) {
-#define EC_ROW(ID, T) case ID: return launch_reduction<StatsReduction<T>, kReduceU, kRBlock, 4>(p, mask, n, rec_dev, s);
-    switch (t) { EC_WITH_CT(EC_ROW) }
-#undef EC_ROW
-    return set_error(EC_ERR_UNSUPPORTED_TYPE, "stats: bad dtype");
+    return ecl::with_cell_type(t, [&](auto c) { return launch_reduction<StatsReduction<ecl::cell_t<decltype(c)>>, kReduceU, kRBlock, 4>(p, mask, n, rec_dev, s); },
+                               [] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "stats: bad dtype"); });
 }
 
 ec_status check_stats_cells(const char* who, int shard, int t, size_t n, const char* advice) {

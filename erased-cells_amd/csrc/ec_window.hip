@@ -2,6 +2,7 @@
 // (ec_window_kernels.hpp).  Every argument check comes before any device work, so a bad call fails the same way with or without a device.
 #include <hip/hip_runtime.h>
 
+#include "ec_dispatch.hpp"
 #include "ec_lattice.hpp"
 #include "ec_runtime.hpp"
 #include "ec_window_checks.hpp"
@@ -52,14 +53,10 @@ static ec_status launch_window(int kind, const WindowArgs& args, const WindowAxi
 
 static ec_status dispatch_window(size_t cell, bool masked, int kind, const WindowArgs& a, const WindowAxis* ax, const WindowAxis* ay, bool vector,
                                  hipStream_t s) {
-#define EC_WIN(W) return masked ? launch_window<W, true>(kind, a, ax, ay, vector, s) : launch_window<W, false>(kind, a, ax, ay, vector, s)
-    switch (cell) {
-        case 1: EC_WIN(1);
-        case 2: EC_WIN(2);
-        case 4: EC_WIN(4);
-        default: EC_WIN(8);
-    }
-#undef EC_WIN
+    return ecl::with_cell_width(cell, [&](auto w) {
+        constexpr int W = sizeof(ecl::cell_t<decltype(w)>);
+        return masked ? launch_window<W, true>(kind, a, ax, ay, vector, s) : launch_window<W, false>(kind, a, ax, ay, vector, s);
+    }, kTypeChecked);
 }
 
 }  // namespace ecd

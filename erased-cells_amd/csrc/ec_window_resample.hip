@@ -4,6 +4,7 @@
 // ec_window.hip instead of adding to it.
 #include <hip/hip_runtime.h>
 
+#include "ec_dispatch.hpp"
 #include "ec_window_checks.hpp"
 #include "ec_window_resample_kernels.hpp"
 
@@ -55,13 +56,10 @@ static ec_status launch_resample(const ResampleArgs& args, uint64_t win_cells, h
 
 static ec_status dispatch_resample(ec_dtype t, const ResampleArgs& a, uint64_t win_cells, hipStream_t s) {
     const bool masked = a.w.in_mask != nullptr;
-    switch (t) {
-#define X(code, T) \
-    case code: return masked ? launch_resample<T, true>(a, win_cells, s) : launch_resample<T, false>(a, win_cells, s);
-        EC_WITH_CT(X)
-#undef X
-        default: return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_window_resample: bad dtype %d", int(t));
-    }
+    return ecl::with_cell_type(t, [&](auto c) {
+        using T = ecl::cell_t<decltype(c)>;
+        return masked ? launch_resample<T, true>(a, win_cells, s) : launch_resample<T, false>(a, win_cells, s);
+    }, [&] { return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_window_resample: bad dtype %d", int(t)); });
 }
 
 }  // namespace ecd
