@@ -336,6 +336,7 @@ struct Stats {
 
 // ---------------------------------------------------------------- CellBuffer (src/buffer.rs)
 class Mask;
+class MaskedCellBuffer;
 
 class CellBuffer {
     CellType ct_ = CellType::UInt8;
@@ -551,6 +552,27 @@ public:
     Mask compare(ec_cmp rel, const CellBuffer& rhs) const;
     Mask compare(ec_cmp rel, const CellValue& rhs) const;
 
+    // Moving windows (ec_focal / ec_focal_convolve; the rule is in include/erased_cells.h): this buffer read as rows of `cols` cells,
+    // radius = (rx, ry), footprints clipped at the raster's edges.  focal: Float64 for SUM / MEAN, this type for MIN / MAX.  The
+    // _whole forms count only cells whose whole footprint exists, and a MaskedCellBuffer says which.  convolve: `weights` is
+    // (2 ry + 1) x (2 rx + 1) doubles, row-major (a correlation); normalize divides by the sum of the weights counted.
+    CellBuffer focal(size_t cols, ec_focal_op op, std::pair<uint32_t, uint32_t> radius = {1, 1}) const {
+        if (cols ? n_ % cols != 0 : n_ != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
+        CellBuffer out(static_cast<CellType>(ec_focal_result_type(op, static_cast<ec_dtype>(ct_))), n_);
+        if (n_) check(ec_focal(op, static_cast<ec_dtype>(ct_), ptr(), nullptr, cols, n_ / cols, radius.first, radius.second, 0, out.ptr(), nullptr, current_stream()));
+        return out;
+    }
+    CellBuffer convolve(size_t cols, const std::vector<double>& weights, std::pair<uint32_t, uint32_t> radius, bool normalize = false) const {
+        if (cols ? n_ % cols != 0 : n_ != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
+        if (weights.size() != size_t(2 * radius.first + 1) * (2 * radius.second + 1)) throw std::logic_error("weights are not (2 ry + 1) x (2 rx + 1)");
+        CellBuffer out(CellType::Float64, n_);
+        if (n_) check(ec_focal_convolve(static_cast<ec_dtype>(ct_), ptr(), nullptr, cols, n_ / cols, weights.data(), radius.first, radius.second,
+                                        normalize ? EC_FOCAL_NORMALIZE : 0, out.ptr(), nullptr, current_stream()));
+        return out;
+    }
+    MaskedCellBuffer focal_whole(size_t cols, ec_focal_op op, std::pair<uint32_t, uint32_t> radius = {1, 1}) const;
+    MaskedCellBuffer convolve_whole(size_t cols, const std::vector<double>& weights, std::pair<uint32_t, uint32_t> radius, bool normalize = false) const;
+
     // ---- Ord/Eq (buffer.rs:373-436): cell type first, then lexicographic total order, then length
     int cmp(const CellBuffer& o) const {  // decided on the device: first differing cell, no download
         int32_t res = 0;
@@ -586,6 +608,15 @@ public:
     Mask& operator=(const Mask&) = delete;
     uint8_t* ptr() const { return static_cast<uint8_t*>(mem_->ptr()); }
 
+private:
+    Mask morph(size_t cols, ec_focal_op op, std::pair<uint32_t, uint32_t> radius) const {
+        if (cols ? n_ % cols != 0 : n_ != 0) throw std::logic_error("the mask is not rows of " + std::to_string(cols) + " bytes");
+        Mask m(n_);
+        if (n_) check(ec_focal(op, EC_U8, ptr(), nullptr, cols, n_ / cols, radius.first, radius.second, 0, m.ptr(), nullptr, current_stream()));
+        return m;
+    }
+
+public:
     static Mask new_(const std::vector<bool>& values) {  // mask.rs:16-18
         std::vector<uint8_t> b(values.begin(), values.end());
         Mask m(b.size());
@@ -657,6 +688,11 @@ public:
         else fetch(0, n_);
         return "Mask(" + elided(items) + ")";
     }
+
+    // Morphology of a mask read as rows of `cols` bytes: ec_focal MAX / MIN over the bytes as UInt8 cells.  A byte of dilate's result
+    // is set iff ANY byte of its footprint (radius = (rx, ry), clipped at the raster's edges) is — the cloud-mask buffer; erode: iff ALL are.
+    Mask dilate(size_t cols, std::pair<uint32_t, uint32_t> radius = {1, 1}) const { return morph(cols, EC_FOCAL_MAX, radius); }
+    Mask erode(size_t cols, std::pair<uint32_t, uint32_t> radius = {1, 1}) const { return morph(cols, EC_FOCAL_MIN, radius); }
 
     Mask operator!() const& {  // Not for &Mask (mask.rs:111-116)
         Mask m(n_);
@@ -762,6 +798,26 @@ public:
         Mask m(out.first * out.second);
         check(window_call(alg, static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), cols, cols ? len() / cols : 0, window, window_size, out,
                           b.ptr(), m.ptr(), current_stream()));
+        return MaskedCellBuffer(std::move(b), std::move(m));
+    }
+    // CellBuffer::focal / convolve over the cells whose mask byte is set: a masked-out cell contributes nothing, and one with a valid
+    // neighbour is filled from it (AND the result's mask with this one to keep the holes).
+    MaskedCellBuffer focal(size_t cols, ec_focal_op op, std::pair<uint32_t, uint32_t> radius = {1, 1}, bool whole = false) const {
+        if (cols ? len() % cols != 0 : len() != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
+        CellBuffer b(static_cast<CellType>(ec_focal_result_type(op, static_cast<ec_dtype>(cell_type()))), len());
+        Mask m(len());
+        if (len()) check(ec_focal(op, static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), cols, len() / cols, radius.first, radius.second,
+                                  whole ? EC_FOCAL_WHOLE : 0, b.ptr(), m.ptr(), current_stream()));
+        return MaskedCellBuffer(std::move(b), std::move(m));
+    }
+    MaskedCellBuffer convolve(size_t cols, const std::vector<double>& weights, std::pair<uint32_t, uint32_t> radius, bool normalize = false,
+                              bool whole = false) const {
+        if (cols ? len() % cols != 0 : len() != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
+        if (weights.size() != size_t(2 * radius.first + 1) * (2 * radius.second + 1)) throw std::logic_error("weights are not (2 ry + 1) x (2 rx + 1)");
+        CellBuffer b(CellType::Float64, len());
+        Mask m(len());
+        if (len()) check(ec_focal_convolve(static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), cols, len() / cols, weights.data(), radius.first,
+                                           radius.second, (whole ? EC_FOCAL_WHOLE : 0) | (normalize ? EC_FOCAL_NORMALIZE : 0), b.ptr(), m.ptr(), current_stream()));
         return MaskedCellBuffer(std::move(b), std::move(m));
     }
     void put_window(size_t cols, std::pair<size_t, size_t> window, std::pair<size_t, size_t> window_size, const MaskedCellBuffer& tile) {
@@ -882,6 +938,23 @@ public:
     bool operator>(const MaskedCellBuffer& o) const { return cmp(o) > 0; }
     bool operator!=(const MaskedCellBuffer& o) const { return !(*this == o); }
 };
+
+inline MaskedCellBuffer CellBuffer::focal_whole(size_t cols, ec_focal_op op, std::pair<uint32_t, uint32_t> radius) const {
+    if (cols ? n_ % cols != 0 : n_ != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
+    CellBuffer b(static_cast<CellType>(ec_focal_result_type(op, static_cast<ec_dtype>(ct_))), n_);
+    Mask m(n_);
+    if (n_) check(ec_focal(op, static_cast<ec_dtype>(ct_), ptr(), nullptr, cols, n_ / cols, radius.first, radius.second, EC_FOCAL_WHOLE, b.ptr(), m.ptr(), current_stream()));
+    return MaskedCellBuffer(std::move(b), std::move(m));
+}
+inline MaskedCellBuffer CellBuffer::convolve_whole(size_t cols, const std::vector<double>& weights, std::pair<uint32_t, uint32_t> radius, bool normalize) const {
+    if (cols ? n_ % cols != 0 : n_ != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
+    if (weights.size() != size_t(2 * radius.first + 1) * (2 * radius.second + 1)) throw std::logic_error("weights are not (2 ry + 1) x (2 rx + 1)");
+    CellBuffer b(CellType::Float64, n_);
+    Mask m(n_);
+    if (n_) check(ec_focal_convolve(static_cast<ec_dtype>(ct_), ptr(), nullptr, cols, n_ / cols, weights.data(), radius.first, radius.second,
+                                    EC_FOCAL_WHOLE | (normalize ? EC_FOCAL_NORMALIZE : 0), b.ptr(), m.ptr(), current_stream()));
+    return MaskedCellBuffer(std::move(b), std::move(m));
+}
 
 #define EC_MCB_OP(OPSYM, OPC)                                                                                          \
     inline MaskedCellBuffer operator OPSYM(const MaskedCellBuffer& l, const MaskedCellBuffer& r) { return l.binop(OPC, r); } \

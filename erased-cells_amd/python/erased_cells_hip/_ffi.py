@@ -22,6 +22,9 @@ EC_WINDOW_MAX_REDUCTION = 64
 # ec_cmp: a relation is the truth table over Ordering — bit 0 Less, bit 1 Equal, bit 2 Greater
 EC_CMP_LT, EC_CMP_EQ, EC_CMP_LE, EC_CMP_GT, EC_CMP_NE, EC_CMP_GE = 1, 2, 3, 4, 5, 6
 EC_CAST_AS, EC_CAST_ROUND = 0, 1  # ec_cast_mode: Rust's `as` / the storing rule (clamp, round half away from zero)
+EC_FOCAL_SUM, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_MAX = range(4)  # ec_focal_op
+EC_FOCAL_RADIUS_CAP = 7
+EC_FOCAL_WHOLE, EC_FOCAL_NORMALIZE = 1, 2  # flags of ec_focal / ec_focal_convolve
 
 
 class _Payload(C.Union):
@@ -186,6 +189,9 @@ SIGNATURES = {
     "ec_window": (I32, [C.c_uint8, VP, U8P] + [C.c_uint64] * 8 + [VP, U8P, VP]),
     "ec_window_resample": (I32, [I32, C.c_uint8, VP, U8P] + [C.c_uint64] * 8 + [VP, U8P, VP]),
     "ec_window_put": (I32, [C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, VP, U8P] + [C.c_uint64] * 4 + [VP]),
+    "ec_focal_result_type": (C.c_uint8, [I32, C.c_uint8]),
+    "ec_focal": (I32, [I32, C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, VP, U8P, VP]),
+    "ec_focal_convolve": (I32, [C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_uint32, VP, U8P, VP]),
     "ec_synth_fill": (I32, [C.c_uint8, VP, SZ, C.c_uint64, C.c_uint64, C.c_double, C.c_double, VP]),
     "ec_synth_mask": (I32, [U8P, SZ, C.c_uint64, C.c_uint64, C.c_uint32, VP]),
     "ec_tune_set": (I32, [C.c_char_p, C.c_int64]),

@@ -20,7 +20,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_RESAMPLE_AVERAGE, EC_RESAMPLE_BILINEAR, EcError, EcStats, EcValue, check, lib
+from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_RESAMPLE_BILINEAR, EcError, EcStats, EcValue, check, lib
 
 # CellType (src/ctype.rs:11-20; order of with_ct!, src/lib.rs:89-98)
 UInt8, UInt16, UInt32, UInt64, Int8, Int16, Int32, Int64, Float32, Float64 = range(10)
@@ -423,6 +423,60 @@ def _to_scaled(buf: "CellBuffer", mask, ct: int, scale, offset, nd) -> "CellBuff
     return out
 
 
+# the spellings of an ec_focal_op
+FOCAL_OPS = {"sum": EC_FOCAL_SUM, "mean": EC_FOCAL_MEAN, "min": EC_FOCAL_MIN, "max": EC_FOCAL_MAX}
+
+
+def _focal_op(op) -> int:
+    """the ec_focal_op number of "sum" "mean" "min" "max" or of an ec_focal_op value; anything else is refused"""
+    o = FOCAL_OPS.get(op, op) if isinstance(op, str) else op
+    if isinstance(o, bool) or not isinstance(o, (int, np.integer)) or not 0 <= int(o) <= 3:
+        raise EcError(EC_ERR_ARG, f"focal: operation {op!r} is not one of {sorted(FOCAL_OPS)} or an ec_focal_op value 0..3")
+    return int(o)
+
+
+def _raster_rows(n: int, cols: int) -> int:
+    if cols < 0 or (cols == 0 and n != 0) or (cols and n % cols):
+        raise AssertionError(f"a buffer of {n} cells is not a raster of rows of {cols} cells")
+    return n // cols if cols else 0
+
+
+def _radius(radius):
+    rx, ry = radius
+    if not 0 <= min(rx, ry) <= max(rx, ry) <= EC_FOCAL_RADIUS_CAP:  # here, not in C: a radius of 2^32 + 1 would arrive there as 1
+        raise EcError(EC_ERR_ARG, f"focal: radius {(rx, ry)} is not within 0 .. EC_FOCAL_RADIUS_CAP ({EC_FOCAL_RADIUS_CAP})")
+    return int(rx), int(ry)
+
+
+def _focal(buf: "CellBuffer", mask, cols: int, op, radius, whole: bool):
+    """ec_focal of `buf` (under `mask`, or None) read as rows of `cols` cells -> (result buffer, result Mask or None).  A mask comes back
+    when there is a source mask or `whole` is set: only then can a cell be invalid."""
+    o, (rx, ry), rows = _focal_op(op), _radius(radius), _raster_rows(buf.n, cols)
+    out = CellBuffer.empty(buf.n, lib().ec_focal_result_type(o, buf.ct))
+    om = Mask.empty(buf.n) if (mask is not None or whole) else None
+    if buf.n:  # an empty buffer has no memory to point at
+        check(lib().ec_focal(o, buf.ct, buf.mem.ptr, mask.mem.ptr if mask is not None else None, cols, rows, rx, ry, EC_FOCAL_WHOLE if whole else 0,
+                             out.mem.ptr, om.mem.ptr if om is not None else None, _stream))
+    return out, om
+
+
+def _convolve(buf: "CellBuffer", mask, cols: int, weights, normalize: bool, whole: bool):
+    """ec_focal_convolve with the 2-D `weights` (odd shape (2 ry + 1, 2 rx + 1)) -> (Float64 buffer, Mask or None).  With `normalize`
+    and no mask back, a cell whose counted weights sum to 0.0 holds zero bits (include/erased_cells.h)."""
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.ndim != 2 or w.shape[0] % 2 == 0 or w.shape[1] % 2 == 0:
+        raise EcError(EC_ERR_ARG, f"convolve: weights of shape {w.shape} are not a 2-D array of odd shape")
+    rx, ry = _radius((w.shape[1] // 2, w.shape[0] // 2))
+    rows = _raster_rows(buf.n, cols)
+    out = CellBuffer.empty(buf.n, Float64)
+    om = Mask.empty(buf.n) if (mask is not None or whole) else None
+    flags = (EC_FOCAL_WHOLE if whole else 0) | (EC_FOCAL_NORMALIZE if normalize else 0)
+    if buf.n:
+        check(lib().ec_focal_convolve(buf.ct, buf.mem.ptr, mask.mem.ptr if mask is not None else None, cols, rows, w.ctypes.data_as(C.POINTER(C.c_double)),
+                                      rx, ry, flags, out.mem.ptr, om.mem.ptr if om is not None else None, _stream))
+    return out, om
+
+
 # --------------------------------------------------------------------------- CellBuffer
 @dataclasses.dataclass(frozen=True)
 class Stats:
@@ -520,6 +574,20 @@ class CellBuffer:
         out = CellBuffer.empty(ow * oh, self.ct)
         _cut(alg, self.ct, self.mem.ptr, None, cols, rows, x, y, w, h, ow, oh, out.mem.ptr, None)
         return out
+
+    def focal(self, cols: int, op, radius=(1, 1), whole: bool = False):
+        """The moving-window `op` ("sum" "mean" "min" "max" or an ec_focal_op) over the (2 ry + 1) x (2 rx + 1) footprint of every cell of
+        this buffer read as rows of `cols` cells, `radius` = (rx, ry), clipped at the raster's edges — the rule is at ec_focal in
+        include/erased_cells.h.  A CellBuffer of ec_focal_result_type (Float64 for sum / mean); with `whole` only cells whose whole
+        footprint exists are valid and a MaskedCellBuffer says which.  One launch, no download."""
+        out, om = _focal(self, None, cols, op, radius, whole)
+        return out if om is None else MaskedCellBuffer(out, om)
+
+    def convolve(self, cols: int, weights, normalize: bool = False, whole: bool = False):
+        """The weighted moving-window sum (a correlation) with the 2-D `weights` of odd shape (2 ry + 1, 2 rx + 1), as Float64 cells;
+        `normalize` divides by the sum of the weights counted.  A MaskedCellBuffer with `whole`, as `focal`."""
+        out, om = _convolve(self, None, cols, weights, normalize, whole)
+        return out if om is None else MaskedCellBuffer(out, om)
 
     def put_window(self, cols: int, window, tile: "CellBuffer", window_size) -> None:
         """Writes `tile` (`window_size` = (w, h) contiguous cells of this buffer's type) into the window at `window` = (x, y) of this
@@ -794,6 +862,22 @@ class Mask:
         check(lib().ec_copy(out.mem.ptr, self.mem.ptr, self.n, _stream))
         return out
 
+    def _morph(self, cols: int, op: int, radius) -> "Mask":
+        (rx, ry), rows = _radius(radius), _raster_rows(self.n, cols)
+        out = Mask.empty(self.n)
+        if self.n:
+            check(lib().ec_focal(op, UInt8, self.mem.ptr, None, cols, rows, rx, ry, 0, out.mem.ptr, None, _stream))
+        return out
+
+    def dilate(self, cols: int, radius=(1, 1)) -> "Mask":
+        """A byte of the result is set iff ANY byte of its footprint — `radius` = (rx, ry), clipped at the raster's edges — is: the
+        cloud-mask buffer.  ec_focal MAX over the mask's bytes as UInt8 cells."""
+        return self._morph(cols, EC_FOCAL_MAX, radius)
+
+    def erode(self, cols: int, radius=(1, 1)) -> "Mask":
+        """A byte of the result is set iff ALL bytes of its clipped footprint are (ec_focal MIN)."""
+        return self._morph(cols, EC_FOCAL_MIN, radius)
+
     def counts(self) -> tuple[int, int]:
         """(data, nodata) — mask.rs:72-80."""
         a, b = C.c_uint64(), C.c_uint64()
@@ -927,6 +1011,15 @@ class MaskedCellBuffer:
         out, om = CellBuffer.empty(ow * oh, self.cell_type()), Mask.empty(ow * oh)
         _cut(alg, self.cell_type(), self._buf.mem.ptr, self._mask.mem.ptr, cols, rows, x, y, w, h, ow, oh, out.mem.ptr, om.mem.ptr)
         return MaskedCellBuffer(out, om)
+
+    def focal(self, cols: int, op, radius=(1, 1), whole: bool = False) -> "MaskedCellBuffer":
+        """`CellBuffer.focal` over the cells whose mask byte is set: a masked-out cell contributes nothing, and one with a valid
+        neighbour is filled from it (AND the result's mask with this one to keep the holes)."""
+        return MaskedCellBuffer(*_focal(self._buf, self._mask, cols, op, radius, whole))
+
+    def convolve(self, cols: int, weights, normalize: bool = False, whole: bool = False) -> "MaskedCellBuffer":
+        """`CellBuffer.convolve` over the cells whose mask byte is set."""
+        return MaskedCellBuffer(*_convolve(self._buf, self._mask, cols, weights, normalize, whole))
 
     def put_window(self, cols: int, window, tile: "MaskedCellBuffer", window_size) -> None:
         """CellBuffer.put_window for values and mask in one launch."""

@@ -119,6 +119,30 @@ impl CellBuffer {
     }
 }
 
+/// What [`CellBuffer::focal`] computes over a footprint (`ec_focal_op`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum FocalOp {
+    /// The sum of the taps as `Float64`, one partial sum per footprint row.
+    Sum = EC_FOCAL_SUM,
+    /// The sum divided by the number of taps.
+    Mean = EC_FOCAL_MEAN,
+    /// The least tap under the total order of `min_max`, its bits copied.
+    Min = EC_FOCAL_MIN,
+    /// The greatest tap.
+    Max = EC_FOCAL_MAX,
+}
+
+impl FocalOp {
+    /// `Float64` for `Sum` and `Mean` (the widening rule of the operators), `cell_type` for `Min` and `Max`.
+    pub fn result_type(self, cell_type: CellType) -> CellType {
+        match self {
+            FocalOp::Sum | FocalOp::Mean => CellType::Float64,
+            FocalOp::Min | FocalOp::Max => cell_type,
+        }
+    }
+}
+
 /// How [`CellBuffer::cast`] turns a cell into a narrower type (`ec_cast_mode`).
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 #[repr(i32)]
@@ -281,6 +305,65 @@ impl CellBuffer {
             )
         })?;
         Ok(cut)
+    }
+
+    /// `ec_focal` with a mask pair (both, or null pointers) and the flags given.
+    pub(crate) fn focal_raw(&self, cols: usize, op: FocalOp, radius: (u32, u32), flags: u32, mask: *const u8, out_mask: *mut u8) -> Result<Self> {
+        assert!(if cols == 0 { self.len == 0 } else { self.len % cols == 0 }, "{} cells are not rows of {cols} cells", self.len);
+        let rows = if cols == 0 { 0 } else { self.len / cols };
+        let out = Self::uninit(op.result_type(self.ct), self.len);
+        if self.len != 0 {
+            check(unsafe {
+                ec_focal(op as i32, self.ct as u8, self.dev_ptr(), mask, cols as u64, rows as u64, radius.0, radius.1, flags, out.mem.ptr(), out_mask, stream())
+            })?;
+        }
+        Ok(out)
+    }
+
+    /// `ec_focal_convolve`; `weights` is (2 ry + 1) x (2 rx + 1), row-major, read before the call returns.
+    pub(crate) fn convolve_raw(&self, cols: usize, weights: &[f64], radius: (u32, u32), flags: u32, mask: *const u8, out_mask: *mut u8) -> Result<Self> {
+        assert!(if cols == 0 { self.len == 0 } else { self.len % cols == 0 }, "{} cells are not rows of {cols} cells", self.len);
+        assert_eq!(weights.len(), (2 * radius.0 as usize + 1) * (2 * radius.1 as usize + 1), "the weights are not (2 ry + 1) x (2 rx + 1)");
+        let rows = if cols == 0 { 0 } else { self.len / cols };
+        let out = Self::uninit(CellType::Float64, self.len);
+        if self.len != 0 {
+            check(unsafe {
+                ec_focal_convolve(
+                    self.ct as u8, self.dev_ptr(), mask, cols as u64, rows as u64, weights.as_ptr(), radius.0, radius.1, flags, out.mem.ptr(), out_mask,
+                    stream(),
+                )
+            })?;
+        }
+        Ok(out)
+    }
+
+    /// The moving-window `op` over the (2 ry + 1) x (2 rx + 1) footprint of every cell of this buffer read as rows of `cols` cells,
+    /// `radius` = (rx, ry), clipped at the raster's edges; the rule is at `ec_focal` in include/erased_cells.h.  One launch.
+    pub fn focal(&self, cols: usize, op: FocalOp, radius: (u32, u32)) -> Result<Self> {
+        self.focal_raw(cols, op, radius, 0, std::ptr::null(), std::ptr::null_mut())
+    }
+
+    /// [`CellBuffer::focal`] where only a cell whose whole footprint lies inside the raster is valid: the cells and the mask that says which.
+    pub fn focal_whole(&self, cols: usize, op: FocalOp, radius: (u32, u32)) -> Result<(Self, Mask)> {
+        let mask = Mask::uninit(self.len);
+        let out = self.focal_raw(cols, op, radius, EC_FOCAL_WHOLE, std::ptr::null(), mask.dev_ptr_mut())?;
+        Ok((out, mask))
+    }
+
+    /// The weighted moving-window sum (a correlation: weight `[dy][dx]` meets cell `(i - ry + dy, j - rx + dx)`) as `Float64` cells;
+    /// `normalize` divides by the sum of the weights counted.  One launch; the weights travel in the kernel's arguments.
+    pub fn convolve(&self, cols: usize, weights: &[f64], radius: (u32, u32), normalize: bool) -> Result<Self> {
+        let flags = if normalize { EC_FOCAL_NORMALIZE } else { 0 };
+        self.convolve_raw(cols, weights, radius, flags, std::ptr::null(), std::ptr::null_mut())
+    }
+
+    /// [`CellBuffer::convolve`] where only a cell whose whole footprint lies inside the raster is valid — what a gradient kernel wants
+    /// at the borders: the cells and the mask that says which.
+    pub fn convolve_whole(&self, cols: usize, weights: &[f64], radius: (u32, u32), normalize: bool) -> Result<(Self, Mask)> {
+        let mask = Mask::uninit(self.len);
+        let flags = EC_FOCAL_WHOLE | if normalize { EC_FOCAL_NORMALIZE } else { 0 };
+        let out = self.convolve_raw(cols, weights, radius, flags, std::ptr::null(), mask.dev_ptr_mut())?;
+        Ok((out, mask))
     }
 
     /// Writes `tile` (`window_size` = (w, h) contiguous cells of this buffer's cell type) into the window at `window` = (x, y)

@@ -9,7 +9,7 @@
 //! into it; every device-side use (`dev_ptr`) first writes a dirty shadow back.  Masks that are only ever built
 //! and combined by kernels never materialise the shadow.
 use crate::device::{download, stream, upload, DeviceMem};
-use crate::error::must;
+use crate::error::{check, must, Result};
 use crate::ffi::*;
 use crate::Elided;
 use std::cell::Cell;
@@ -135,6 +135,33 @@ impl Mask {
         let (mut t, mut f) = (0u64, 0u64);
         must(unsafe { ec_mask_counts(self.dev_ptr(), self.len, &mut t, &mut f, stream()) }, "ec_mask_counts");
         (t as usize, f as usize)
+    }
+
+    /// `ec_focal` MAX or MIN over this mask's bytes as `UInt8` cells, read as rows of `cols` bytes.
+    fn morph(&self, cols: usize, op: i32, radius: (u32, u32)) -> Result<Mask> {
+        assert!(if cols == 0 { self.len == 0 } else { self.len % cols == 0 }, "{} bytes are not rows of {cols} bytes", self.len);
+        let out = Mask::uninit(self.len);
+        if self.len != 0 {
+            let rows = (self.len / cols) as u64;
+            check(unsafe {
+                ec_focal(
+                    op, crate::CellType::UInt8 as u8, self.dev_ptr() as *const c_void, std::ptr::null(), cols as u64, rows, radius.0, radius.1, 0,
+                    out.dev_ptr_mut() as *mut c_void, std::ptr::null_mut(), stream(),
+                )
+            })?;
+        }
+        Ok(out)
+    }
+
+    /// A byte of the result is set iff ANY byte of its footprint — `radius` = (rx, ry), clipped at the raster's edges — is: the
+    /// cloud-mask buffer.  One launch.
+    pub fn dilate(&self, cols: usize, radius: (u32, u32)) -> Result<Mask> {
+        self.morph(cols, EC_FOCAL_MAX, radius)
+    }
+
+    /// A byte of the result is set iff ALL bytes of its clipped footprint are.
+    pub fn erode(&self, cols: usize, radius: (u32, u32)) -> Result<Mask> {
+        self.morph(cols, EC_FOCAL_MIN, radius)
     }
 }
 

@@ -50,6 +50,16 @@ pub const EC_CMP_GE: i32 = 6;
 /// `ec_cast_mode`: Rust's `as`, or the storing rule — clamp, round half away from zero, saturate (`ec_cast` takes it as an `i32`).
 pub const EC_CAST_AS: i32 = 0;
 pub const EC_CAST_ROUND: i32 = 1;
+/// `ec_focal_op`: what `ec_focal` computes over a footprint (it takes it as an `i32`).
+pub const EC_FOCAL_SUM: i32 = 0;
+pub const EC_FOCAL_MEAN: i32 = 1;
+pub const EC_FOCAL_MIN: i32 = 2;
+pub const EC_FOCAL_MAX: i32 = 3;
+/// The largest radius of a footprint on either axis: footprints up to 15 x 15.
+pub const EC_FOCAL_RADIUS_CAP: u32 = 7;
+/// Flags of `ec_focal` / `ec_focal_convolve`: only whole footprints are valid; divide by the weights counted (convolve only).
+pub const EC_FOCAL_WHOLE: u32 = 1;
+pub const EC_FOCAL_NORMALIZE: u32 = 2;
 
 /// Mirrors `ec_value`: tag + 8-byte payload, 16 bytes.
 #[repr(C)]
@@ -292,6 +302,12 @@ extern "C" {
     pub fn ec_window_resample(alg: i32, t: ec_dtype, src: *const c_void, src_mask_or_null: *const u8, src_cols: u64, src_rows: u64,
                               x0: u64, y0: u64, win_cols: u64, win_rows: u64, out_cols: u64, out_rows: u64, dst: *mut c_void,
                               dst_mask_or_null: *mut u8, s: ec_stream) -> ec_status;
+    pub fn ec_focal_result_type(op: i32, t: ec_dtype) -> ec_dtype;
+    pub fn ec_focal(op: i32, t: ec_dtype, src: *const c_void, src_mask_or_null: *const u8, cols: u64, rows: u64, rx: u32, ry: u32,
+                    flags: u32, dst: *mut c_void, dst_mask_or_null: *mut u8, s: ec_stream) -> ec_status;
+    pub fn ec_focal_convolve(t: ec_dtype, src: *const c_void, src_mask_or_null: *const u8, cols: u64, rows: u64,
+                             weights_host: *const f64, rx: u32, ry: u32, flags: u32, dst: *mut c_void, dst_mask_or_null: *mut u8,
+                             s: ec_stream) -> ec_status;
     pub fn ec_window_put(t: ec_dtype, tile: *const c_void, tile_mask_or_null: *const u8, win_cols: u64, win_rows: u64,
                          dst: *mut c_void, dst_mask_or_null: *mut u8, dst_cols: u64, dst_rows: u64, x0: u64, y0: u64,
                          s: ec_stream) -> ec_status;

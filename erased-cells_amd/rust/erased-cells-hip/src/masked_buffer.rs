@@ -11,7 +11,7 @@
 use crate::device::stream;
 use crate::error::{check, must, Result};
 use crate::ffi::*;
-use crate::{BufferOps, CastMode, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Cmp, Mask, NoData, ResampleAlg, Stats};
+use crate::{BufferOps, CastMode, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Cmp, FocalOp, Mask, NoData, ResampleAlg, Stats};
 use std::fmt::{Debug, Formatter};
 use std::ops::{Add, Div, Mul, Neg, Sub};
 
@@ -135,6 +135,24 @@ impl MaskedCellBuffer {
                 window_size.0 as u64, window_size.1 as u64, size.0 as u64, size.1 as u64, cells.mem.ptr(), mask.dev_ptr_mut(), stream(),
             )
         })?;
+        Ok(MaskedCellBuffer(cells, mask))
+    }
+
+    /// [`CellBuffer::focal`] over the cells whose mask byte is set: a masked-out cell contributes nothing, and one with a valid
+    /// neighbour is filled from it (AND the result's mask with this one to keep the holes).  With `whole` only a cell whose whole
+    /// footprint exists and is unmasked is valid.  One launch.
+    pub fn focal(&self, cols: usize, op: FocalOp, radius: (u32, u32), whole: bool) -> Result<Self> {
+        let mask = Mask::uninit(self.0.len());
+        let flags = if whole { EC_FOCAL_WHOLE } else { 0 };
+        let cells = self.0.focal_raw(cols, op, radius, flags, self.1.dev_ptr(), mask.dev_ptr_mut())?;
+        Ok(MaskedCellBuffer(cells, mask))
+    }
+
+    /// [`CellBuffer::convolve`] over the cells whose mask byte is set.
+    pub fn convolve(&self, cols: usize, weights: &[f64], radius: (u32, u32), normalize: bool, whole: bool) -> Result<Self> {
+        let mask = Mask::uninit(self.0.len());
+        let flags = if whole { EC_FOCAL_WHOLE } else { 0 } | if normalize { EC_FOCAL_NORMALIZE } else { 0 };
+        let cells = self.0.convolve_raw(cols, weights, radius, flags, self.1.dev_ptr(), mask.dev_ptr_mut())?;
         Ok(MaskedCellBuffer(cells, mask))
     }
 

@@ -598,6 +598,61 @@ ec_status ec_window_resample(int32_t alg /* an ec_resample */, ec_dtype t, const
                              void *dst, uint8_t *dst_mask_or_null, ec_stream stream);
 
 /* ---------------------------------------------------------------- *
+ * Moving windows (focal operations) on a raster resident on the device: every output cell from its neighbours.
+ * The reference has no counterpart (its buffers are flat, src/buffer.rs); the 2-D framing is ec_window's: `src` is a
+ * row-major raster of cols x rows cells of type t, `dst` one of the same shape, mask bytes move in the same launch.
+ * ---------------------------------------------------------------- */
+/* What ec_focal computes over a footprint.  It crosses the ABI as an int32_t, like ec_op and ec_resample. */
+typedef enum { EC_FOCAL_SUM = 0, EC_FOCAL_MEAN = 1, EC_FOCAL_MIN = 2, EC_FOCAL_MAX = 3 } ec_focal_op;
+enum { EC_FOCAL_RADIUS_CAP = 7 };                    /* rx, ry <= 7: footprints up to 15 x 15 */
+enum { EC_FOCAL_WHOLE = 1, EC_FOCAL_NORMALIZE = 2 }; /* flags; NORMALIZE is ec_focal_convolve's only */
+/* The cell type of ec_focal's result: EC_F64 for SUM and MEAN (the widen-to-f64 rule of the binops), t for MIN and MAX;
+ * 255 for an op or a type that is none. */
+ec_dtype ec_focal_result_type(int32_t op /* an ec_focal_op */, ec_dtype t);
+/* The footprint of output cell (i, j) is the (2 ry + 1) x (2 rx + 1) block of cells around it.  Its TAPS are the cells (y, x)
+ * with i - ry <= y <= i + ry and j - rx <= x <= j + rx that lie inside the raster and, when there is a source mask, have
+ * mask[y, x] != 0 — taken with rows ascending and columns ascending within a row.  The footprint is clipped at the raster's
+ * edges; it never wraps into the neighbouring row.  A cell that is no tap contributes nothing, whatever it holds: a NaN under
+ * a cleared mask byte does not reach the result.  The rule, in individually rounded f64 operations (no FMA), so every cell
+ * has one right answer:
+ *   acc = 0.0; count = 0; [wsum = 0.0]
+ *   for y ascending:  racc = 0.0; [rw = 0.0]
+ *       for x ascending, (y, x) a tap:
+ *           SUM / MEAN  racc = racc + double(cell[y, x])
+ *           convolve    racc = racc + (w[y - i + ry, x - j + rx] * double(cell[y, x]));  rw = rw + w[y - i + ry, x - j + rx]
+ *           count += 1
+ *       acc = acc + racc;  [wsum = wsum + rw]
+ *   SUM: r = acc        MEAN: r = acc / double(count)
+ *   convolve: r = acc, or with EC_FOCAL_NORMALIZE r = acc / wsum, where wsum == 0.0 counts as "nothing counted"
+ *   MIN / MAX: the least / greatest tap under the reference's total order (src/value.rs:248-265, as ec_min_max), its bits copied
+ * double(cell) of a 64-bit integer is the rounding conversion, as in ec_window_resample.  (The sum of a single -0.0 is
+ * 0.0 + -0.0 = +0.0: the rule, not a copy.)
+ * A cell is VALID when count > 0; with EC_FOCAL_WHOLE when count == (2 rx + 1) * (2 ry + 1): every cell of its footprint
+ * exists and is unmasked — what a gradient kernel wants at borders and next to holes.  A valid cell stores r and mask byte 1,
+ * an invalid one all-zero bits and mask byte 0.  The centre cell's own mask byte has no special role, which is what fills
+ * holes from their neighbours; a caller who wants to keep the holes ANDs the result mask with the source mask (ec_mask_and).
+ * dst_mask_or_null may be NULL only when src_mask_or_null is NULL and EC_FOCAL_WHOLE is not set; a non-NULL one is always
+ * written.  rx == ry == 0 is legal: the widening copy (SUM, MEAN) or the copy (MIN, MAX) with masked-out cells zeroed.
+ * dst holds cols * rows cells of ec_focal_result_type(op, t).  No allocation, asynchronous, capturable after
+ * ec_prepare_stream.  There is no sharded form: a row-block shard would need ry rows of its neighbour.
+ * EC_ERR_ARG, before any device work: a null src or dst, an op that is none, unknown flag bits, EC_FOCAL_NORMALIZE, rx or ry
+ * above EC_FOCAL_RADIUS_CAP, dst_mask NULL where it is required, cols * rows beyond 64 bits, more than 2^31 - 1 tiles,
+ * dst == src or dst_mask == src_mask.  The operation is not in-place; any other overlap of an output with an input is the
+ * caller's to avoid.  A bad dtype is EC_ERR_UNSUPPORTED_TYPE.  cols * rows == 0 is EC_OK and launches nothing. */
+ec_status ec_focal(int32_t op /* an ec_focal_op */, ec_dtype t, const void *src, const uint8_t *src_mask_or_null,
+                   uint64_t cols, uint64_t rows, uint32_t rx, uint32_t ry, uint32_t flags,
+                   void *dst, uint8_t *dst_mask_or_null, ec_stream stream);
+/* The weighted form of the rule above (a correlation: weight [dy][dx] meets cell (i - ry + dy, j - rx + dx); flip the
+ * weights for a convolution in the strict sense).  weights_host: (2 ry + 1) x (2 rx + 1) doubles, row-major, in HOST memory;
+ * they are read before the call returns and travel in the kernel's arguments, so the array has no lifetime requirement and
+ * nothing is uploaded.  dst holds cols * rows f64 cells.  With EC_FOCAL_NORMALIZE a cell whose counted weights sum to 0.0 is
+ * invalid (zero bits, mask byte 0), also where dst_mask_or_null is NULL.  Same contract and refusals as ec_focal, with a
+ * null weights_host among them and EC_FOCAL_NORMALIZE accepted. */
+ec_status ec_focal_convolve(ec_dtype t, const void *src, const uint8_t *src_mask_or_null,
+                            uint64_t cols, uint64_t rows, const double *weights_host, uint32_t rx, uint32_t ry,
+                            uint32_t flags, void *dst /* f64 cells */, uint8_t *dst_mask_or_null, ec_stream stream);
+
+/* ---------------------------------------------------------------- *
  * Band statistics: count, min, max, sum, mean and population standard deviation in one pass over a resident buffer.
  * The reference has BufferOps::min_max only (src/buffer.rs:169-173; masked: src/masked/masked_buffer.rs:208-217); its own
  * test of NDVI against GDAL's STATISTICS_MINIMUM / MAXIMUM / MEAN / STDDEV (src/gdal/rasterband.rs:151-156) can therefore
