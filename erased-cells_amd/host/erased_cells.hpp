@@ -965,6 +965,57 @@ EC_MCB_OP(+, EC_ADD) EC_MCB_OP(-, EC_SUB) EC_MCB_OP(*, EC_MUL) EC_MCB_OP(/, EC_D
 #undef EC_MCB_OP
 inline MaskedCellBuffer operator-(const MaskedCellBuffer& b) { return b.neg(); }
 
+// ---------------------------------------------------------------- composites over a stack of layers (ec_composite)
+// One buffer from up to EC_COMPOSITE_MAX_LAYERS co-registered layers of one cell type and length, in one pass: per cell the first /
+// last valid layer, the least / greatest valid cell (the reference's total order, value.rs:248-265), or the sum / mean (Float64) of
+// the valid cells; the rule is in include/erased_cells.h.  `aux` (optional) receives a UInt8 buffer: the layer each cell came from
+// (EC_COMPOSITE_NONE: none), for SUM / MEAN the number of valid layers.
+namespace detail {
+inline void composite_call(ec_composite_op op, CellType ct, size_t n, const std::vector<const void*>& p, const std::vector<const uint8_t*>* m,
+                           uint32_t min_count, CellBuffer& out, Mask* om, CellBuffer* aux) {
+    if (aux) *aux = CellBuffer(CellType::UInt8, n);
+    if (n == 0) return;  // an empty buffer has no memory to point at
+    check(ec_composite(op, static_cast<ec_dtype>(ct), p.data(), m ? m->data() : nullptr, static_cast<int32_t>(p.size()), n, min_count, out.ptr(),
+                       om ? om->ptr() : nullptr, aux ? static_cast<uint8_t*>(aux->ptr()) : nullptr, current_stream()));
+}
+template <typename B>
+inline void composite_stack(const std::vector<const B*>& layers) {  // what the mirror refuses itself, with a clear message
+    if (layers.empty() || layers.size() > EC_COMPOSITE_MAX_LAYERS) throw Error(EC_ERR_ARG, "composite: the stack holds 1 .. EC_COMPOSITE_MAX_LAYERS (64) layers");
+    for (const B* l : layers) {
+        if (!l) throw Error(EC_ERR_ARG, "composite: null layer");
+        if (l->cell_type() != layers[0]->cell_type()) throw Error(EC_ERR_ARG, "composite: layers of different cell types: cast the stack to one first");
+        if (l->len() != layers[0]->len()) throw Error(EC_ERR_LENGTH, "composite: layers of different lengths");
+    }
+}
+}  // namespace detail
+
+// no layer is masked: every cell is valid and the result is a CellBuffer
+inline CellBuffer composite(const std::vector<const CellBuffer*>& layers, ec_composite_op op = EC_COMPOSITE_FIRST, CellBuffer* aux = nullptr) {
+    detail::composite_stack(layers);
+    const CellType ct = layers[0]->cell_type();
+    const size_t n = layers[0]->len();
+    CellBuffer out(static_cast<CellType>(ec_composite_result_type(op, static_cast<ec_dtype>(ct))), n);
+    std::vector<const void*> p;
+    for (const CellBuffer* l : layers) p.push_back(l->ptr());
+    detail::composite_call(op, ct, n, p, nullptr, 1, out, nullptr, aux);
+    return out;
+}
+// a cell is valid when at least `min_count` layers are valid there (1: the ordinary composite; layers.size(): the AND rule)
+inline MaskedCellBuffer composite(const std::vector<const MaskedCellBuffer*>& layers, ec_composite_op op = EC_COMPOSITE_FIRST, uint32_t min_count = 1,
+                                  CellBuffer* aux = nullptr) {
+    detail::composite_stack(layers);
+    const CellType ct = layers[0]->cell_type();
+    const size_t n = layers[0]->len();
+    CellBuffer out(static_cast<CellType>(ec_composite_result_type(op, static_cast<ec_dtype>(ct))), n);
+    Mask om(n);
+    std::vector<const void*> p;
+    std::vector<const uint8_t*> m;
+    for (const MaskedCellBuffer* l : layers) { p.push_back(l->buffer().ptr()); m.push_back(l->mask().ptr()); }
+    if (min_count < 1 || min_count > layers.size()) throw Error(EC_ERR_ARG, "composite: min_count is not within 1 .. the number of layers");
+    detail::composite_call(op, ct, n, p, &m, min_count, out, &om, aux);
+    return MaskedCellBuffer(std::move(out), std::move(om));
+}
+
 // ---------------------------------------------------------------- fused operator chains
 // The reference evaluates `(&nir - &red) / (nir + red)` (src/gdal/rasterband.rs:148) eagerly, one pass and
 // one f64 temporary per operator.  `lazy(buf)` wraps a buffer so that the same operator syntax builds a
@@ -1397,6 +1448,36 @@ public:
         if (mask) for (void* p : mask->ptrs_) m.push_back(static_cast<const uint8_t*>(p));
         check(ec_sharded_cast_scaled(grp_->raw(), static_cast<ec_dtype>(ct_), src.data(), mask ? m.data() : nullptr, lens_.data(), scale, offset,
                                      static_cast<ec_dtype>(cell_type), nodata ? &nodata->raw() : nullptr, out.ptrs_.data()));
+        return out;
+    }
+    // composite of identically sharded layers on every shard (no communication): `masks` empty, or one entry per layer — a UInt8
+    // buffer of 0 / 1 bytes cut the same way, or nullptr for a layer without a mask; `out_mask` is needed when a layer has one
+    static ShardedCellBuffer composite(const std::vector<const ShardedCellBuffer*>& layers, ec_composite_op op = EC_COMPOSITE_FIRST, uint32_t min_count = 1,
+                                       const std::vector<const ShardedCellBuffer*>& masks = {}, std::optional<ShardedCellBuffer>* out_mask = nullptr,
+                                       std::optional<ShardedCellBuffer>* aux = nullptr) {
+        if (layers.empty() || layers.size() > EC_COMPOSITE_MAX_LAYERS) throw Error(EC_ERR_ARG, "composite: the stack holds 1 .. EC_COMPOSITE_MAX_LAYERS (64) layers");
+        if (!masks.empty() && masks.size() != layers.size()) throw Error(EC_ERR_ARG, "composite: one mask entry per layer");
+        const ShardedCellBuffer& first = *layers[0];
+        std::vector<std::vector<const void*>> p(layers.size());
+        std::vector<std::vector<const uint8_t*>> m(layers.size());
+        std::vector<const void* const*> pc;
+        std::vector<const uint8_t* const*> mc;
+        for (size_t k = 0; k < layers.size(); ++k) {
+            if (layers[k]->ct_ != first.ct_ || layers[k]->lens_ != first.lens_) throw Error(EC_ERR_LENGTH, "composite: layers must share a cell type and a sharding");
+            p[k].assign(layers[k]->ptrs_.begin(), layers[k]->ptrs_.end());
+            pc.push_back(p[k].data());
+            const ShardedCellBuffer* mk = masks.empty() ? nullptr : masks[k];
+            if (mk && (mk->ct_ != CellType::UInt8 || mk->lens_ != first.lens_)) throw Error(EC_ERR_LENGTH, "composite: a mask must be UInt8 and sharded like its layer");
+            if (mk) for (void* q : mk->ptrs_) m[k].push_back(static_cast<const uint8_t*>(q));
+            mc.push_back(mk ? m[k].data() : nullptr);
+        }
+        ShardedCellBuffer out(*first.grp_, static_cast<CellType>(ec_composite_result_type(op, static_cast<ec_dtype>(first.ct_))), first.lens_);
+        std::vector<uint8_t*> om, ax;
+        if (out_mask) { out_mask->emplace(ShardedCellBuffer(*first.grp_, CellType::UInt8, first.lens_)); for (void* q : (*out_mask)->ptrs_) om.push_back(static_cast<uint8_t*>(q)); }
+        if (aux) { aux->emplace(ShardedCellBuffer(*first.grp_, CellType::UInt8, first.lens_)); for (void* q : (*aux)->ptrs_) ax.push_back(static_cast<uint8_t*>(q)); }
+        check(ec_sharded_composite(first.grp_->raw(), op, static_cast<ec_dtype>(first.ct_), pc.data(), masks.empty() ? nullptr : mc.data(),
+                                   static_cast<int32_t>(layers.size()), first.lens_.data(), min_count, out.ptrs_.data(), out_mask ? om.data() : nullptr,
+                                   aux ? ax.data() : nullptr));
         return out;
     }
     // BufferOps::min_max of the whole raster (buffer.rs:169-173): per-shard keys, one all-reduce(MAX), decode

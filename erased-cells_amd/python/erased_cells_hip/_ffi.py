@@ -25,6 +25,8 @@ EC_CAST_AS, EC_CAST_ROUND = 0, 1  # ec_cast_mode: Rust's `as` / the storing rule
 EC_FOCAL_SUM, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_MAX = range(4)  # ec_focal_op
 EC_FOCAL_RADIUS_CAP = 7
 EC_FOCAL_WHOLE, EC_FOCAL_NORMALIZE = 1, 2  # flags of ec_focal / ec_focal_convolve
+EC_COMPOSITE_FIRST, EC_COMPOSITE_LAST, EC_COMPOSITE_MIN, EC_COMPOSITE_MAX, EC_COMPOSITE_SUM, EC_COMPOSITE_MEAN = range(6)  # ec_composite_op
+EC_COMPOSITE_MAX_LAYERS, EC_COMPOSITE_NONE = 64, 255
 
 
 class _Payload(C.Union):
@@ -192,6 +194,9 @@ SIGNATURES = {
     "ec_focal_result_type": (C.c_uint8, [I32, C.c_uint8]),
     "ec_focal": (I32, [I32, C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, VP, U8P, VP]),
     "ec_focal_convolve": (I32, [C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_uint32, VP, U8P, VP]),
+    "ec_composite_result_type": (C.c_uint8, [I32, C.c_uint8]),
+    "ec_composite": (I32, [I32, C.c_uint8, PVP, PVP, I32, SZ, C.c_uint32, VP, U8P, U8P, VP]),
+    "ec_sharded_composite": (I32, [VP, I32, C.c_uint8, C.POINTER(PVP), C.POINTER(PVP), I32, PSZ, C.c_uint32, PVP, PVP, PVP]),
     "ec_synth_fill": (I32, [C.c_uint8, VP, SZ, C.c_uint64, C.c_uint64, C.c_double, C.c_double, VP]),
     "ec_synth_mask": (I32, [U8P, SZ, C.c_uint64, C.c_uint64, C.c_uint32, VP]),
     "ec_tune_set": (I32, [C.c_char_p, C.c_int64]),

@@ -20,7 +20,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_RESAMPLE_BILINEAR, EcError, EcStats, EcValue, check, lib
+from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_COMPOSITE_MAX_LAYERS, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_RESAMPLE_BILINEAR, EcError, EcStats, EcValue, check, lib
 
 # CellType (src/ctype.rs:11-20; order of with_ct!, src/lib.rs:89-98)
 UInt8, UInt16, UInt32, UInt64, Int8, Int16, Int32, Int64, Float32, Float64 = range(10)
@@ -1192,3 +1192,62 @@ def select(mask: Mask, a, b):
     check(lib().ec_masked_select(ct, a._buf.mem.ptr, a._mask.mem.ptr, b._buf.mem.ptr, b._mask.mem.ptr, mask.mem.ptr, n,
                                  out.mem.ptr, om.mem.ptr, _stream))
     return MaskedCellBuffer(out, om)
+
+
+# the spellings of an ec_composite_op
+COMPOSITE_OPS = {"first": 0, "last": 1, "min": 2, "max": 3, "sum": 4, "mean": 5}
+
+
+def _composite_op(op) -> int:
+    """the ec_composite_op number of "first" "last" "min" "max" "sum" "mean" or of an ec_composite_op value; anything else is refused"""
+    o = COMPOSITE_OPS.get(op, op) if isinstance(op, str) else op
+    if isinstance(o, bool) or not isinstance(o, (int, np.integer)) or not 0 <= int(o) <= 5:
+        raise EcError(EC_ERR_ARG, f"composite: operation {op!r} is not one of {sorted(COMPOSITE_OPS)} or an ec_composite_op value 0..5")
+    return int(o)
+
+
+def _composite_stack(layers, min_count):
+    """the checks Python makes itself on a stack -> ([(CellBuffer, Mask or None)] in stack order, cell type, length)"""
+    layers = list(layers)
+    if not 1 <= len(layers) <= EC_COMPOSITE_MAX_LAYERS:
+        raise EcError(EC_ERR_ARG, f"composite: {len(layers)} layers, not within 1 .. EC_COMPOSITE_MAX_LAYERS ({EC_COMPOSITE_MAX_LAYERS}); "
+                                  "compose two calls for a taller stack")
+    pairs = []
+    for k, layer in enumerate(layers):
+        if isinstance(layer, MaskedCellBuffer):
+            pairs.append((layer.buffer(), layer.mask()))
+        elif isinstance(layer, CellBuffer):
+            pairs.append((layer, None))
+        else:
+            raise EcError(EC_ERR_ARG, f"composite: layer {k} is a {type(layer).__name__}, not a CellBuffer or a MaskedCellBuffer")
+    ct, n = pairs[0][0].cell_type(), pairs[0][0].len()
+    for k, (b, _) in enumerate(pairs):
+        if b.cell_type() != ct:
+            raise EcError(EC_ERR_ARG, f"composite: layer {k} is {CT_NAMES[b.cell_type()]}, layer 0 {CT_NAMES[ct]}: cast the stack to one cell type first")
+        if b.len() != n:
+            raise EcError(EC_ERR_ARG, f"composite: layer {k} has {b.len()} cells, layer 0 {n}")
+    if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or not 1 <= int(min_count) <= len(pairs):
+        raise EcError(EC_ERR_ARG, f"composite: min_count {min_count!r} is not within 1 .. {len(pairs)}, the number of layers")
+    return pairs, ct, n
+
+
+def composite(layers, op="first", min_count: int = 1, aux: bool = False):
+    """One buffer from a stack of co-registered `layers` (CellBuffers and MaskedCellBuffers, mixed allowed, one cell type and length), in
+    one pass (ec_composite; the rule is in include/erased_cells.h).  `op`: "first" / "last" valid layer, "min" / "max" valid cell, "sum" /
+    "mean" of the valid cells (Float64).  A cell is valid when at least `min_count` layers are.  A CellBuffer when no layer is masked,
+    otherwise a MaskedCellBuffer; with `aux` a pair (result, UInt8 CellBuffer): the layer each cell came from (255: none), for sum / mean
+    the number of valid layers."""
+    o = _composite_op(op)
+    pairs, ct, n = _composite_stack(layers, min_count)
+    masked = any(m is not None for _, m in pairs)
+    out = CellBuffer.empty(n, lib().ec_composite_result_type(o, ct))
+    om = Mask.empty(n) if masked else None
+    ax = CellBuffer.empty(n, UInt8) if aux else None
+    if n:  # an empty buffer has no memory to point at
+        k = len(pairs)
+        lp = (C.c_void_p * k)(*[b.mem.ptr for b, _ in pairs])
+        mp = (C.c_void_p * k)(*[m.mem.ptr if m is not None else None for _, m in pairs])
+        check(lib().ec_composite(o, ct, lp, mp if masked else None, k, n, int(min_count), out.mem.ptr, om.mem.ptr if masked else None,
+                                 ax.mem.ptr if aux else None, _stream))
+    res = MaskedCellBuffer(out, om) if masked else out
+    return (res, ax) if aux else res

@@ -626,6 +626,72 @@ impl<C: CellEncoding> TryFrom<CellBuffer> for Vec<C> {
     }
 }
 
+/// What [`CellBuffer::composite`] keeps of a cell's stack of layers (`ec_composite_op`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum CompositeOp {
+    /// The valid layer with the least index, its bits copied (a priority mosaic).
+    First = EC_COMPOSITE_FIRST,
+    /// The valid layer with the greatest index.
+    Last = EC_COMPOSITE_LAST,
+    /// The least valid cell under the total order of `min_max`, its bits copied; equal cells keep the least index.
+    Min = EC_COMPOSITE_MIN,
+    /// The greatest valid cell.
+    Max = EC_COMPOSITE_MAX,
+    /// The valid cells added in stack order as `Float64`, one rounded addition each.
+    Sum = EC_COMPOSITE_SUM,
+    /// The sum divided by the number of valid layers.
+    Mean = EC_COMPOSITE_MEAN,
+}
+
+impl CompositeOp {
+    /// `Float64` for `Sum` and `Mean` (the widening rule of the operators), `cell_type` for the picks.
+    pub fn result_type(self, cell_type: CellType) -> CellType {
+        match self {
+            CompositeOp::Sum | CompositeOp::Mean => CellType::Float64,
+            _ => cell_type,
+        }
+    }
+}
+
+impl CellBuffer {
+    /// `ec_composite` over `layers` with their mask pointers (`masks` empty: no layer has one; a null entry: that layer has none).
+    /// `aux`: also the `UInt8` buffer of where each cell came from.
+    pub(crate) fn composite_raw(layers: &[&CellBuffer], masks: &[*const u8], op: CompositeOp, min_count: u32, out_mask: *mut u8, aux: bool) -> Result<(Self, Option<Self>)> {
+        assert!(!layers.is_empty() && layers.len() <= EC_COMPOSITE_MAX_LAYERS, "a stack holds 1 .. {EC_COMPOSITE_MAX_LAYERS} layers, not {}", layers.len());
+        assert!(masks.is_empty() || masks.len() == layers.len(), "one mask entry per layer");
+        let (ct, len) = (layers[0].ct, layers[0].len);
+        for l in layers {
+            assert_eq!(l.ct, ct, "the layers of a stack share one cell type: cast first");
+            assert_eq!(l.len, len, "the layers of a stack share one length");
+        }
+        let out = Self::uninit(op.result_type(ct), len);
+        let source = if aux { Some(Self::uninit(CellType::UInt8, len)) } else { None };
+        if len != 0 {
+            let cells: Vec<*const c_void> = layers.iter().map(|l| l.dev_ptr()).collect();
+            let masks_ptr = if masks.is_empty() { std::ptr::null() } else { masks.as_ptr() };
+            let aux_ptr = source.as_ref().map_or(std::ptr::null_mut(), |a| a.mem.ptr() as *mut u8);
+            check(unsafe {
+                ec_composite(op as i32, ct as u8, cells.as_ptr(), masks_ptr, layers.len() as i32, len, min_count, out.mem.ptr(), out_mask, aux_ptr, stream())
+            })?;
+        }
+        Ok((out, source))
+    }
+
+    /// One buffer from a stack of co-registered layers of one cell type and length, in one pass over every layer; the rule is at
+    /// `ec_composite` in include/erased_cells.h.  Every cell is valid here: see `MaskedCellBuffer::composite` for clouds.
+    pub fn composite(layers: &[&CellBuffer], op: CompositeOp) -> Result<Self> {
+        Ok(Self::composite_raw(layers, &[], op, 1, std::ptr::null_mut(), false)?.0)
+    }
+
+    /// [`CellBuffer::composite`] and, as `UInt8` cells, the index of the layer each cell came from (for `Sum` / `Mean` the
+    /// number of layers counted).
+    pub fn composite_with_source(layers: &[&CellBuffer], op: CompositeOp) -> Result<(Self, Self)> {
+        let (out, source) = Self::composite_raw(layers, &[], op, 1, std::ptr::null_mut(), true)?;
+        Ok((out, source.expect("asked for")))
+    }
+}
+
 // api-surface(src/buffer.rs:318-436): the sixteen binary-operator impl headers, the two `Neg` impls and the ordering /
 // equality impl headers of CellBuffer (`&a op &b`, `a op b`, `a op &b`, `a op scalar`; no `scalar op a` in the reference either)
 macro_rules! buffer_operator {

@@ -60,6 +60,16 @@ pub const EC_FOCAL_RADIUS_CAP: u32 = 7;
 /// Flags of `ec_focal` / `ec_focal_convolve`: only whole footprints are valid; divide by the weights counted (convolve only).
 pub const EC_FOCAL_WHOLE: u32 = 1;
 pub const EC_FOCAL_NORMALIZE: u32 = 2;
+/// `ec_composite_op`: what `ec_composite` keeps of a cell's stack of layers (it takes it as an `i32`).
+pub const EC_COMPOSITE_FIRST: i32 = 0;
+pub const EC_COMPOSITE_LAST: i32 = 1;
+pub const EC_COMPOSITE_MIN: i32 = 2;
+pub const EC_COMPOSITE_MAX: i32 = 3;
+pub const EC_COMPOSITE_SUM: i32 = 4;
+pub const EC_COMPOSITE_MEAN: i32 = 5;
+/// The tallest stack of one call, and the aux byte of a cell that no layer gave.
+pub const EC_COMPOSITE_MAX_LAYERS: usize = 64;
+pub const EC_COMPOSITE_NONE: u8 = 255;
 
 /// Mirrors `ec_value`: tag + 8-byte payload, 16 bytes.
 #[repr(C)]
@@ -308,6 +318,12 @@ extern "C" {
     pub fn ec_focal_convolve(t: ec_dtype, src: *const c_void, src_mask_or_null: *const u8, cols: u64, rows: u64,
                              weights_host: *const f64, rx: u32, ry: u32, flags: u32, dst: *mut c_void, dst_mask_or_null: *mut u8,
                              s: ec_stream) -> ec_status;
+    pub fn ec_composite_result_type(op: i32, t: ec_dtype) -> ec_dtype;
+    pub fn ec_composite(op: i32, t: ec_dtype, layers: *const *const c_void, masks_or_null: *const *const u8, n_layers: i32, n: usize,
+                        min_count: u32, dst: *mut c_void, dst_mask_or_null: *mut u8, aux_or_null: *mut u8, s: ec_stream) -> ec_status;
+    pub fn ec_sharded_composite(g: *mut ec_shard_group, op: i32, t: ec_dtype, layers: *const *const *const c_void,
+                                masks_or_null: *const *const *const u8, n_layers: i32, n: *const usize, min_count: u32,
+                                dst: *const *mut c_void, dst_mask_or_null: *const *mut u8, aux_or_null: *const *mut u8) -> ec_status;
     pub fn ec_window_put(t: ec_dtype, tile: *const c_void, tile_mask_or_null: *const u8, win_cols: u64, win_rows: u64,
                          dst: *mut c_void, dst_mask_or_null: *mut u8, dst_cols: u64, dst_rows: u64, x0: u64, y0: u64,
                          s: ec_stream) -> ec_status;

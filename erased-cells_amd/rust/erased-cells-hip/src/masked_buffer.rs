@@ -11,7 +11,7 @@
 use crate::device::stream;
 use crate::error::{check, must, Result};
 use crate::ffi::*;
-use crate::{BufferOps, CastMode, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Cmp, FocalOp, Mask, NoData, ResampleAlg, Stats};
+use crate::{BufferOps, CastMode, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Cmp, CompositeOp, FocalOp, Mask, NoData, ResampleAlg, Stats};
 use std::fmt::{Debug, Formatter};
 use std::ops::{Add, Div, Mul, Neg, Sub};
 
@@ -421,6 +421,26 @@ impl Iterator for MaskedCellBufferIterator<'_> {
         let cell = self.cells.next()?;
         let is_data = self.valid.next()?;
         Some((cell, is_data))
+    }
+}
+
+impl MaskedCellBuffer {
+    /// [`CellBuffer::composite`] over the cells whose mask byte is set: a masked-out cell contributes nothing, whatever it holds.  A
+    /// cell of the result is valid when at least `min_count` layers are valid there (1: the ordinary composite; `layers.len()`: the AND
+    /// rule of the operators); an invalid one is zero.  One launch, where a chain of `or_else` takes one per layer.
+    pub fn composite(layers: &[&MaskedCellBuffer], op: CompositeOp, min_count: u32) -> Result<Self> {
+        Ok(Self::composite_with_source(layers, op, min_count)?.0)
+    }
+
+    /// [`MaskedCellBuffer::composite`] and, as `UInt8` cells, the index of the layer each cell came from — `EC_COMPOSITE_NONE` for an
+    /// invalid cell; for `Sum` / `Mean` the number of valid layers.
+    pub fn composite_with_source(layers: &[&MaskedCellBuffer], op: CompositeOp, min_count: u32) -> Result<(Self, CellBuffer)> {
+        assert!(min_count >= 1 && min_count as usize <= layers.len(), "min_count {min_count} is not within 1 .. {}", layers.len());
+        let cells: Vec<&CellBuffer> = layers.iter().map(|l| &l.0).collect();
+        let masks: Vec<*const u8> = layers.iter().map(|l| l.1.dev_ptr()).collect();
+        let mask = Mask::uninit(cells.first().map_or(0, |c| c.len()));
+        let (out, source) = CellBuffer::composite_raw(&cells, &masks, op, min_count, mask.dev_ptr_mut(), true)?;
+        Ok((MaskedCellBuffer(out, mask), source.expect("asked for")))
     }
 }
 

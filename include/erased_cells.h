@@ -653,6 +653,63 @@ ec_status ec_focal_convolve(ec_dtype t, const void *src, const uint8_t *src_mask
                             uint32_t flags, void *dst /* f64 cells */, uint8_t *dst_mask_or_null, ec_stream stream);
 
 /* ---------------------------------------------------------------- *
+ * Composites: one raster from a stack of K co-registered layers (dates, tiles, sensors), every output cell from the K cells
+ * at its index — the first cloud-free observation, the greatest-value composite, the mean over the clear observations, how
+ * many there were, which layer a cell came from.  The reference has no counterpart: its buffers are flat (src/buffer.rs) and
+ * its operators take two; the validity rule is its masked one (src/masked/masked_buffer.rs:143-148, 208-217) over K layers.
+ * One pass reads every layer once, where a chain of K - 1 ec_masked_select calls re-reads and re-writes the running result.
+ * ---------------------------------------------------------------- */
+/* What ec_composite keeps of a cell's stack.  It crosses the ABI as an int32_t, like ec_op and ec_focal_op. */
+typedef enum { EC_COMPOSITE_FIRST = 0, EC_COMPOSITE_LAST = 1, EC_COMPOSITE_MIN = 2, EC_COMPOSITE_MAX = 3,
+               EC_COMPOSITE_SUM = 4, EC_COMPOSITE_MEAN = 5 } ec_composite_op;
+enum { EC_COMPOSITE_MAX_LAYERS = 64, EC_COMPOSITE_NONE = 255 };
+/* The cell type of ec_composite's result: EC_F64 for SUM and MEAN (the widen-to-f64 rule of the binops), t for the others;
+ * 255 for an op or a type that is none. */
+ec_dtype ec_composite_result_type(int32_t op /* an ec_composite_op */, ec_dtype t);
+/* layers and masks_or_null are HOST arrays of n_layers DEVICE pointers: layer k is n cells of type t at layers[k], with its
+ * mask bytes at masks_or_null[k].  masks_or_null == NULL, or an entry masks_or_null[k] == NULL, means every cell of that
+ * layer is valid.  Both arrays are read before the call returns and travel in the kernel's arguments, so they have no
+ * lifetime requirement and nothing is uploaded.  The same buffer may appear more than once.  A stack of mixed cell types is
+ * cast first (ec_cast).
+ * The rule, so every cell has one right answer.  Layer k is VALID at cell i when it has no mask or masks[k][i] != 0; count is
+ * the number of valid layers at i.  A layer that is not valid contributes nothing, whatever its cell holds: a NaN under a
+ * cleared mask byte does not reach the result.
+ *   FIRST / LAST  the valid layer with the least / greatest k, its bits copied
+ *   MIN / MAX     the least / greatest valid cell under the reference's total order (src/value.rs:248-265, as ec_min_max), its
+ *                 bits copied; a layer replaces the running extreme only when it is strictly better, so among cells of equal
+ *                 keys the least k wins
+ *   SUM           acc = 0.0; for k ascending, layer k valid: acc = acc + double(cell) — every addition one individually
+ *                 rounded f64 operation, never an FMA; double(cell) of a 64-bit integer is the rounding conversion, as in
+ *                 ec_window_resample.  (The sum of a single -0.0 is 0.0 + -0.0 = +0.0: the rule, not a copy.)
+ *   MEAN          acc / double(count)
+ * The cell is valid when count >= min_count: it then stores the result and mask byte 1, otherwise all-zero bits and mask
+ * byte 0.  1 <= min_count <= n_layers: 1 is the ordinary composite, n_layers the AND rule of the masked operators, a value in
+ * between "at least min_count clear observations".
+ * aux_or_null is one byte per cell: for FIRST, LAST, MIN and MAX the index k of the layer whose bits were stored, or
+ * EC_COMPOSITE_NONE for an invalid cell; for SUM and MEAN count, whether or not the cell is valid.
+ * dst holds n cells of ec_composite_result_type(op, t).  dst_mask_or_null may be NULL only when no layer has a mask; a
+ * non-NULL one is always written.  No allocation, asynchronous, capturable after ec_prepare_stream.  n == 0 is EC_OK and
+ * launches nothing (no pointer is looked at).
+ * EC_ERR_ARG, before any device work and in this order: an op that is none; n_layers outside 1 .. EC_COMPOSITE_MAX_LAYERS;
+ * min_count outside 1 .. n_layers; (a bad dtype: EC_ERR_UNSUPPORTED_TYPE;) a null layers, layers[k] or dst; dst_mask NULL
+ * where it is required; more than 2^31 - 1 tiles; dst equal to a layer; dst_mask or aux equal to a mask, to dst or to each
+ * other.  The operation is not in-place; any other overlap of an output with an input is the caller's to avoid.
+ * More than 64 layers: compose two calls.  FIRST, LAST, MIN and MAX re-associate over sub-stacks exactly (composite the
+ * partial results in stack order, their masks as masks); SUM re-associates up to the rounding of its additions, MEAN from
+ * the partial SUMs and counts (aux). */
+ec_status ec_composite(int32_t op /* an ec_composite_op */, ec_dtype t, const void *const *layers,
+                       const uint8_t *const *masks_or_null, int32_t n_layers, size_t n, uint32_t min_count,
+                       void *dst, uint8_t *dst_mask_or_null, uint8_t *aux_or_null, ec_stream stream);
+/* ec_composite on every shard of a group (element-wise: no collective).  layers[k] and masks_or_null[k] are columns of one
+ * pointer per shard, n the shards' lengths, dst, dst_mask_or_null and aux_or_null columns likewise.  masks_or_null == NULL or
+ * masks_or_null[k] == NULL: layer k has no mask on any shard.  The whole-call refusals of ec_composite come first and post
+ * nothing. */
+ec_status ec_sharded_composite(ec_shard_group *g, int32_t op /* an ec_composite_op */, ec_dtype t,
+                               const void *const *const *layers, const uint8_t *const *const *masks_or_null,
+                               int32_t n_layers, const size_t *n, uint32_t min_count, void *const *dst,
+                               uint8_t *const *dst_mask_or_null, uint8_t *const *aux_or_null);
+
+/* ---------------------------------------------------------------- *
  * Band statistics: count, min, max, sum, mean and population standard deviation in one pass over a resident buffer.
  * The reference has BufferOps::min_max only (src/buffer.rs:169-173; masked: src/masked/masked_buffer.rs:208-217); its own
  * test of NDVI against GDAL's STATISTICS_MINIMUM / MAXIMUM / MEAN / STDDEV (src/gdal/rasterband.rs:151-156) can therefore
