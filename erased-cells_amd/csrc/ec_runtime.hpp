@@ -266,6 +266,13 @@ inline ReducePlan plan_reduction(const void* p0, unsigned residue1, size_t cell_
 // for shard `shard` of a group; `advice` closes the refusal's text.  ec_stats.hip.
 ec_status check_stats_cells(const char* who, int shard, int t, size_t n, const char* advice);
 
+// The zonal statistics' forms with a workspace of the library's own (ec_zonal.hip), for ec_sharded.hip: the refusals of
+// ec_zonal_stats_compute, and the n_zones ec_moments of one launch downloaded to HOST address recs (synchronous).
+ec_status check_zonal_host_args(const char* who, ec_dtype t, const void* p, const uint8_t* mask, ec_dtype zt, const void* zones, size_t n,
+                                int32_t n_zones, const void* stats_out);
+ec_status zonal_records_host(ec_dtype t, const void* p, const uint8_t* mask, ec_dtype zt, const void* zones, size_t n, int32_t n_zones,
+                             ec_moments* recs, ec_stream stream);
+
 // binary arithmetic, one translation unit per op
 template <int OP>
 ec_status dispatch_binop(int lt, const void* l, int rt, const void* r, size_t n, double* out, hipStream_t s);

@@ -515,6 +515,20 @@ public:
         check(ec_stats_compute(static_cast<ec_dtype>(ct_), ptr(), nullptr, n_, &out, current_stream()));
         return Stats(out);
     }
+    // stats() per zone of the zone raster `zones` (UInt8, UInt16 or Int32, one id per cell) in one pass: entry z over the cells whose
+    // id is z; an id outside 0 .. n_zones - 1 belongs to no zone (ec_zonal_stats_compute; the rule is in include/erased_cells.h)
+    std::vector<Stats> zonal_stats(const CellBuffer& zones, int32_t n_zones) const { return zonal_stats_of(*this, nullptr, zones, n_zones); }
+    // this buffer as a zone raster, each cell replaced by table[id] (ec_zonal_broadcast): a cell whose id is outside
+    // 0 .. table.len() - 1 is zero and not valid in the result.  Defined below MaskedCellBuffer.
+    MaskedCellBuffer broadcast(const CellBuffer& table) const;
+    static std::vector<Stats> zonal_stats_of(const CellBuffer& values, const uint8_t* mask_or_null, const CellBuffer& zones, int32_t n_zones) {
+        if (zones.n_ != values.n_) throw Error(EC_ERR_LENGTH, "zonal_stats: the zone raster and the values differ in length");
+        if (n_zones < 1 || n_zones > EC_ZONAL_MAX_ZONES) throw Error(EC_ERR_ARG, "zonal_stats: n_zones is not within 1 .. EC_ZONAL_MAX_ZONES; relabel in chunks");
+        std::vector<ec_stats> out(static_cast<size_t>(n_zones));
+        check(ec_zonal_stats_compute(static_cast<ec_dtype>(values.ct_), values.ptr(), mask_or_null, static_cast<ec_dtype>(zones.ct_), zones.ptr(), values.n_,
+                                     n_zones, out.data(), current_stream()));
+        return std::vector<Stats>(out.begin(), out.end());
+    }
     template <typename T> std::vector<T> to_vec() const {  // buffer.rs:175-185
         CellBuffer r = convert(CellEncoding<T>::cell_type());
         if (r.cell_type() != CellEncoding<T>::cell_type())  // danger::cast assert (buffer.rs:444)
@@ -884,6 +898,8 @@ public:
         check(ec_stats_compute(static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), len(), &out, current_stream()));
         return Stats(out);
     }
+    // CellBuffer::zonal_stats over the valid cells: a masked-out cell belongs to no zone, whatever it holds
+    std::vector<Stats> zonal_stats(const CellBuffer& zones, int32_t n_zones) const { return CellBuffer::zonal_stats_of(buf_, mask_.ptr(), zones, n_zones); }
 
     // ---- per-cell order predicates ANDed, in the same launch, with the masks: a cell that is not valid satisfies none (:326-335)
     Mask compare(ec_cmp rel, const MaskedCellBuffer& rhs) const {
@@ -988,6 +1004,15 @@ inline void composite_stack(const std::vector<const B*>& layers) {  // what the 
     }
 }
 }  // namespace detail
+
+inline MaskedCellBuffer CellBuffer::broadcast(const CellBuffer& table) const {
+    if (table.n_ < 1 || table.n_ > size_t(EC_ZONAL_MAX_ZONES)) throw Error(EC_ERR_ARG, "broadcast: the table is not of 1 .. EC_ZONAL_MAX_ZONES cells");
+    CellBuffer out(table.ct_, n_);
+    Mask m(n_);
+    check(ec_zonal_broadcast(static_cast<ec_dtype>(ct_), ptr(), n_, static_cast<int32_t>(table.n_), static_cast<ec_dtype>(table.ct_), table.ptr(), out.ptr(),
+                             m.ptr(), current_stream()));
+    return MaskedCellBuffer(std::move(out), std::move(m));
+}
 
 // no layer is masked: every cell is valid and the result is a CellBuffer
 inline CellBuffer composite(const std::vector<const CellBuffer*>& layers, ec_composite_op op = EC_COMPOSITE_FIRST, CellBuffer* aux = nullptr) {
@@ -1497,6 +1522,20 @@ public:
         if (mask) for (void* q : mask->ptrs_) m.push_back(static_cast<const uint8_t*>(q));
         check(ec_sharded_stats(grp_->raw(), static_cast<ec_dtype>(ct_), p.data(), mask ? m.data() : nullptr, lens_.data(), &out));
         return Stats(out);
+    }
+    // CellBuffer::zonal_stats of the whole raster: every shard's n_zones records, zone by zone folded on the host in shard order
+    // (`zones`: the zone raster cut the same way; `mask` as for stats())
+    std::vector<Stats> zonal_stats(const ShardedCellBuffer& zones, int32_t n_zones, const ShardedCellBuffer* mask = nullptr) const {
+        if (zones.lens_ != lens_) throw Error(EC_ERR_LENGTH, "the zone raster must be sharded identically");
+        if (mask && (mask->ct_ != CellType::UInt8 || mask->lens_ != lens_)) throw Error(EC_ERR_LENGTH, "the mask must be UInt8 and sharded identically");
+        if (n_zones < 1 || n_zones > EC_ZONAL_MAX_ZONES) throw Error(EC_ERR_ARG, "zonal_stats: n_zones is not within 1 .. EC_ZONAL_MAX_ZONES");
+        std::vector<ec_stats> out(static_cast<size_t>(n_zones));
+        std::vector<const void*> p(ptrs_.begin(), ptrs_.end()), z(zones.ptrs_.begin(), zones.ptrs_.end());
+        std::vector<const uint8_t*> m;
+        if (mask) for (void* q : mask->ptrs_) m.push_back(static_cast<const uint8_t*>(q));
+        check(ec_sharded_zonal_stats(grp_->raw(), static_cast<ec_dtype>(ct_), p.data(), mask ? m.data() : nullptr, static_cast<ec_dtype>(zones.ct_), z.data(),
+                                     lens_.data(), n_zones, out.data()));
+        return std::vector<Stats>(out.begin(), out.end());
     }
     template <typename T> std::vector<T> to_vec() const {  // gather; T must be the buffer's own cell type
         if (CellEncoding<T>::cell_type() != ct_) throw NarrowingError(ct_, CellEncoding<T>::cell_type());

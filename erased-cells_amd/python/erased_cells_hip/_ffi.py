@@ -27,6 +27,7 @@ EC_FOCAL_RADIUS_CAP = 7
 EC_FOCAL_WHOLE, EC_FOCAL_NORMALIZE = 1, 2  # flags of ec_focal / ec_focal_convolve
 EC_COMPOSITE_FIRST, EC_COMPOSITE_LAST, EC_COMPOSITE_MIN, EC_COMPOSITE_MAX, EC_COMPOSITE_SUM, EC_COMPOSITE_MEAN = range(6)  # ec_composite_op
 EC_COMPOSITE_MAX_LAYERS, EC_COMPOSITE_NONE = 64, 255
+EC_ZONAL_MAX_ZONES = 256
 
 
 class _Payload(C.Union):
@@ -194,6 +195,11 @@ SIGNATURES = {
     "ec_focal_result_type": (C.c_uint8, [I32, C.c_uint8]),
     "ec_focal": (I32, [I32, C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, VP, U8P, VP]),
     "ec_focal_convolve": (I32, [C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_uint32, VP, U8P, VP]),
+    "ec_zonal_workspace_bytes": (SZ, [I32]),
+    "ec_zonal_stats_device": (I32, [C.c_uint8, VP, U8P, C.c_uint8, VP, SZ, I32, VP, VP, VP]),
+    "ec_zonal_stats_compute": (I32, [C.c_uint8, VP, U8P, C.c_uint8, VP, SZ, I32, VP, VP]),
+    "ec_sharded_zonal_stats": (I32, [VP, C.c_uint8, PVP, PVP, C.c_uint8, PVP, PSZ, I32, VP]),
+    "ec_zonal_broadcast": (I32, [C.c_uint8, VP, SZ, I32, C.c_uint8, VP, VP, U8P, VP]),
     "ec_composite_result_type": (C.c_uint8, [I32, C.c_uint8]),
     "ec_composite": (I32, [I32, C.c_uint8, PVP, PVP, I32, SZ, C.c_uint32, VP, U8P, U8P, VP]),
     "ec_sharded_composite": (I32, [VP, I32, C.c_uint8, C.POINTER(PVP), C.POINTER(PVP), I32, PSZ, C.c_uint32, PVP, PVP, PVP]),

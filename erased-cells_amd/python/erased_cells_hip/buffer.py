@@ -20,7 +20,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_COMPOSITE_MAX_LAYERS, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_RESAMPLE_BILINEAR, EcError, EcStats, EcValue, check, lib
+from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_COMPOSITE_MAX_LAYERS, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_ZONAL_MAX_ZONES, EC_RESAMPLE_BILINEAR, EcError, EcStats, EcValue, check, lib
 
 # CellType (src/ctype.rs:11-20; order of with_ct!, src/lib.rs:89-98)
 UInt8, UInt16, UInt32, UInt64, Int8, Int16, Int32, Int64, Float32, Float64 = range(10)
@@ -689,6 +689,27 @@ class CellBuffer:
         check(lib().ec_stats_compute(self.ct, self.mem.ptr, None, self.n, C.byref(out), _stream))
         return Stats.from_ec(out)
 
+    def zonal_stats(self, zones: "CellBuffer", n_zones: int) -> list:
+        """`stats()` per zone of the zone raster `zones` (UInt8, UInt16 or Int32, one id per cell) in one pass: a list of `n_zones`
+        Stats, entry z over the cells whose id is z.  An id outside 0 .. n_zones - 1 belongs to no zone (ec_zonal_stats_compute;
+        the rule is in include/erased_cells.h).  `mean NDVI per region`: `[s.mean for s in ndvi.zonal_stats(regions, 200)]`."""
+        return _zonal_stats(self, None, zones, n_zones)
+
+    def broadcast(self, table, cell_type: Optional[int] = None) -> "MaskedCellBuffer":
+        """This buffer as a zone raster, each cell replaced by `table[id]`: the way back from per-zone figures into the raster
+        (ec_zonal_broadcast).  `table`: a CellBuffer of n_zones cells, or a sequence / array that `cell_type` (default: its own
+        numpy type) is stored as.  A cell whose id is outside 0 .. len(table) - 1 is zero and not valid in the result."""
+        if not isinstance(table, CellBuffer):
+            a = np.asarray(table)
+            table = CellBuffer.from_vec(a.astype(NP_DTYPES[cell_type]) if cell_type is not None else a)
+        elif cell_type is not None and table.ct != cell_type:
+            raise EcError(EC_ERR_ARG, f"broadcast: the table is {CT_NAMES[table.ct]}, not {CT_NAMES[cell_type]}")
+        if not 1 <= table.n <= EC_ZONAL_MAX_ZONES:
+            raise EcError(EC_ERR_ARG, f"broadcast: a table of {table.n} cells, not within 1 .. EC_ZONAL_MAX_ZONES ({EC_ZONAL_MAX_ZONES})")
+        out, om = CellBuffer.empty(self.n, table.ct), DeviceMem(self.n)
+        check(lib().ec_zonal_broadcast(self.ct, self.mem.ptr, self.n, table.n, table.ct, table.mem.ptr, out.mem.ptr, om.ptr, _stream))
+        return MaskedCellBuffer(out, Mask(self.n, om))
+
     # ---- arithmetic (src/buffer.rs:321-371)
     def _binop(self, op: int, rhs) -> "CellBuffer":
         if isinstance(rhs, CellBuffer):
@@ -1098,6 +1119,10 @@ class MaskedCellBuffer:
         check(lib().ec_stats_compute(self.cell_type(), self._buf.mem.ptr, self._mask.mem.ptr, self.len(), C.byref(out), _stream))
         return Stats.from_ec(out)
 
+    def zonal_stats(self, zones: "CellBuffer", n_zones: int) -> list:
+        """`CellBuffer.zonal_stats` over the valid cells: a masked-out cell belongs to no zone, whatever it holds."""
+        return _zonal_stats(self._buf, self._mask, zones, n_zones)
+
     # ---- arithmetic (src/masked/masked_buffer.rs:323-383)
     def _binop(self, op: int, rhs) -> "MaskedCellBuffer":
         if isinstance(rhs, MaskedCellBuffer):
@@ -1192,6 +1217,20 @@ def select(mask: Mask, a, b):
     check(lib().ec_masked_select(ct, a._buf.mem.ptr, a._mask.mem.ptr, b._buf.mem.ptr, b._mask.mem.ptr, mask.mem.ptr, n,
                                  out.mem.ptr, om.mem.ptr, _stream))
     return MaskedCellBuffer(out, om)
+
+
+def _zonal_stats(buf: "CellBuffer", mask, zones, n_zones: int) -> list:
+    """`n_zones` Stats of `buf` under `mask` (or None) per zone of the CellBuffer `zones` (ec_zonal_stats_compute)."""
+    if isinstance(zones, MaskedCellBuffer) or not isinstance(zones, CellBuffer):
+        raise EcError(EC_ERR_ARG, f"zonal_stats: the zone raster is a {type(zones).__name__}, not a CellBuffer")
+    if isinstance(n_zones, bool) or not isinstance(n_zones, (int, np.integer)) or not 1 <= n_zones <= EC_ZONAL_MAX_ZONES:
+        raise EcError(EC_ERR_ARG, f"zonal_stats: n_zones {n_zones!r} is not within 1 .. EC_ZONAL_MAX_ZONES ({EC_ZONAL_MAX_ZONES}); relabel in chunks")
+    if zones.n != buf.n:
+        raise EcError(EC_ERR_ARG, f"zonal_stats: the zone raster has {zones.n} cells, the values {buf.n}")
+    out = (EcStats * int(n_zones))()
+    check(lib().ec_zonal_stats_compute(buf.ct, buf.mem.ptr, mask.mem.ptr if mask is not None else None, zones.ct, zones.mem.ptr, buf.n,
+                                       int(n_zones), out, _stream))
+    return [Stats.from_ec(s) for s in out]
 
 
 # the spellings of an ec_composite_op

@@ -331,6 +331,19 @@ class ShardGroup:
                                      (C.c_size_t * self.n)(*sb.lens), C.byref(out)))
         return B.Stats.from_ec(out)
 
+    def zonal_stats(self, sb: ShardedBuffer, zones: ShardedBuffer, n_zones: int, mask: ShardedBuffer = None) -> list:
+        """`CellBuffer.zonal_stats` of the whole sharded raster: every shard's `n_zones` records, zone by zone folded on the host in
+        shard order (no collective).  `zones`: the zone raster (UInt8, UInt16 or Int32), sharded like `sb`."""
+        from ._ffi import EC_ERR_ARG, EC_ZONAL_MAX_ZONES, EcError
+        if list(zones.lens) != list(sb.lens) or (mask is not None and list(mask.lens) != list(sb.lens)):
+            raise EcError(EC_ERR_ARG, "zonal_stats: the zone raster or the mask is not sharded like the values")
+        if isinstance(n_zones, bool) or not isinstance(n_zones, int) or not 1 <= n_zones <= EC_ZONAL_MAX_ZONES:
+            raise EcError(EC_ERR_ARG, f"zonal_stats: n_zones {n_zones!r} is not within 1 .. EC_ZONAL_MAX_ZONES ({EC_ZONAL_MAX_ZONES})")
+        out = (EcStats * n_zones)()
+        check(lib().ec_sharded_zonal_stats(self.handle, sb.ct, sb.ptrs, mask.ptrs if mask is not None else None, zones.ct, zones.ptrs,
+                                           (C.c_size_t * self.n)(*sb.lens), n_zones, out))
+        return [B.Stats.from_ec(s) for s in out]
+
     def counts(self, mask: ShardedBuffer) -> tuple[int, int]:
         t, f = C.c_uint64(), C.c_uint64()
         check(lib().ec_sharded_counts(self.handle, mask.ptrs, (C.c_size_t * self.n)(*mask.lens), C.byref(t), C.byref(f)))

@@ -772,3 +772,37 @@ impl Ord for CellBuffer {
     }
 }
 // end api-surface
+
+impl CellBuffer {
+    /// `ec_zonal_stats_compute`: [`CellBuffer::stats`] per zone of the zone raster `zones` (`UInt8`, `UInt16` or `Int32`, one id per
+    /// cell) in one pass.  `mask`: the device bytes of a mask of the same length, or null.
+    pub(crate) fn zonal_stats_raw(&self, mask: *const u8, zones: &CellBuffer, n_zones: usize) -> Result<Vec<Stats>> {
+        assert_eq!(zones.len, self.len, "the zone raster and the values share one length");
+        assert!((1..=EC_ZONAL_MAX_ZONES).contains(&n_zones), "1 .. {EC_ZONAL_MAX_ZONES} zones, not {n_zones}: relabel in chunks");
+        let mut out = vec![Stats::blank(); n_zones];
+        check(unsafe {
+            ec_zonal_stats_compute(self.ct as u8, self.dev_ptr(), mask, zones.ct as u8, zones.dev_ptr(), self.len, n_zones as i32,
+                                   out.as_mut_ptr() as *mut c_void, stream())
+        })?;
+        Ok(out.iter().map(Stats::from_ffi).collect())
+    }
+
+    /// Entry `z` holds the statistics of the cells whose id in `zones` is `z`; an id outside `0 .. n_zones` belongs to no zone.
+    /// The rule is at `ec_zonal_stats_device` in include/erased_cells.h.
+    pub fn zonal_stats(&self, zones: &CellBuffer, n_zones: usize) -> Result<Vec<Stats>> {
+        self.zonal_stats_raw(std::ptr::null(), zones, n_zones)
+    }
+
+    /// This buffer as a zone raster, each cell replaced by `table[id]` (`ec_zonal_broadcast`): the cells and the mask of where an
+    /// id was inside `0 .. table.len()`; every other cell is zero and not valid.  `MaskedCellBuffer::broadcast` pairs them.
+    pub fn broadcast(&self, table: &CellBuffer) -> Result<(CellBuffer, Mask)> {
+        assert!((1..=EC_ZONAL_MAX_ZONES).contains(&table.len), "a table of 1 .. {EC_ZONAL_MAX_ZONES} cells, not {}", table.len);
+        let out = Self::uninit(table.ct, self.len);
+        let mask = Mask::uninit(self.len);
+        check(unsafe {
+            ec_zonal_broadcast(self.ct as u8, self.dev_ptr(), self.len, table.len as i32, table.ct as u8, table.dev_ptr(), out.mem.ptr(),
+                               mask.dev_ptr_mut(), stream())
+        })?;
+        Ok((out, mask))
+    }
+}

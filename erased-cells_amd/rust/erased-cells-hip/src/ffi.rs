@@ -60,6 +60,8 @@ pub const EC_FOCAL_RADIUS_CAP: u32 = 7;
 /// Flags of `ec_focal` / `ec_focal_convolve`: only whole footprints are valid; divide by the weights counted (convolve only).
 pub const EC_FOCAL_WHOLE: u32 = 1;
 pub const EC_FOCAL_NORMALIZE: u32 = 2;
+/// The most zones one `ec_zonal_stats_*` call serves (`EC_ZONAL_MAX_ZONES`).
+pub const EC_ZONAL_MAX_ZONES: usize = 256;
 /// `ec_composite_op`: what `ec_composite` keeps of a cell's stack of layers (it takes it as an `i32`).
 pub const EC_COMPOSITE_FIRST: i32 = 0;
 pub const EC_COMPOSITE_LAST: i32 = 1;
@@ -301,6 +303,16 @@ extern "C" {
                             stream: ec_stream) -> ec_status;
     pub fn ec_sharded_stats(g: *mut ec_shard_group, t: ec_dtype, p: *const *const c_void,
                             masks_or_null: *const *const u8, n: *const usize, stats_out: *mut c_void) -> ec_status;
+    // the band statistics per zone of a zone raster (u8, u16 or i32 ids), and the way back into the raster
+    pub fn ec_zonal_workspace_bytes(n_zones: i32) -> usize;
+    pub fn ec_zonal_stats_device(t: ec_dtype, p: *const c_void, mask_or_null: *const u8, zt: ec_dtype, zones: *const c_void, n: usize,
+                                 n_zones: i32, moments_dev: *mut c_void, workspace_dev: *mut c_void, stream: ec_stream) -> ec_status;
+    pub fn ec_zonal_stats_compute(t: ec_dtype, p: *const c_void, mask_or_null: *const u8, zt: ec_dtype, zones: *const c_void, n: usize,
+                                  n_zones: i32, stats_out: *mut c_void, stream: ec_stream) -> ec_status;
+    pub fn ec_sharded_zonal_stats(g: *mut ec_shard_group, t: ec_dtype, p: *const *const c_void, masks_or_null: *const *const u8,
+                                  zt: ec_dtype, zones: *const *const c_void, n: *const usize, n_zones: i32, stats_out: *mut c_void) -> ec_status;
+    pub fn ec_zonal_broadcast(zt: ec_dtype, zones: *const c_void, n: usize, n_zones: i32, t: ec_dtype, table_dev: *const c_void,
+                              dst: *mut c_void, dst_mask_or_null: *mut u8, stream: ec_stream) -> ec_status;
     pub fn ec_shard_range(n_rows: u64, n_cols: u64, shard: u32, n_shards: u32, cell_offset: *mut u64,
                           cell_len: *mut u64) -> ec_status;
 

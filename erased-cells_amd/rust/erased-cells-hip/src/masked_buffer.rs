@@ -497,3 +497,16 @@ impl Neg for MaskedCellBuffer {
     }
 }
 // end api-surface
+
+impl MaskedCellBuffer {
+    /// [`CellBuffer::zonal_stats`] over the valid cells: a masked-out cell belongs to no zone, whatever it holds.
+    pub fn zonal_stats(&self, zones: &CellBuffer, n_zones: usize) -> Result<Vec<Stats>> {
+        self.0.zonal_stats_raw(self.1.dev_ptr(), zones, n_zones)
+    }
+
+    /// [`CellBuffer::broadcast`] as one value: `table[id]` where the zone raster's id names an entry of `table`, not valid elsewhere.
+    pub fn broadcast(zones: &CellBuffer, table: &CellBuffer) -> Result<Self> {
+        let (cells, mask) = zones.broadcast(table)?;
+        Ok(MaskedCellBuffer(cells, mask))
+    }
+}

@@ -305,6 +305,24 @@ impl ShardedCellBuffer<'_> {
         Ok(Stats::from_ffi(&out))
     }
 
+    /// [`CellBuffer::zonal_stats`] of the whole raster: every shard's `n_zones` records, zone by zone folded on the host in shard order
+    /// (no collective).  `zones`: the zone raster cut the same way; `mask` as for [`Self::stats`].
+    pub fn zonal_stats(&self, zones: &Self, n_zones: usize, mask: Option<&Self>) -> Result<Vec<Stats>> {
+        assert_eq!(zones.lens, self.lens, "the zone raster must be sharded identically");
+        assert!((1..=EC_ZONAL_MAX_ZONES).contains(&n_zones), "1 .. {EC_ZONAL_MAX_ZONES} zones, not {n_zones}");
+        if let Some(m) = mask {
+            assert_eq!(m.ct, CellType::UInt8, "a mask is UInt8 bytes");
+            assert_eq!(m.lens, self.lens, "the mask must be sharded identically");
+        }
+        let masks: Vec<*const u8> = mask.map_or(Vec::new(), |m| m.ptrs.iter().map(|p| *p as *const u8).collect());
+        let mut out = vec![Stats::blank(); n_zones];
+        check(unsafe {
+            ec_sharded_zonal_stats(self.group.g, self.ct as u8, self.const_ptrs().as_ptr(), if mask.is_some() { masks.as_ptr() } else { ptr::null() },
+                                   zones.ct as u8, zones.const_ptrs().as_ptr(), self.lens.as_ptr(), n_zones as i32, out.as_mut_ptr() as *mut c_void)
+        })?;
+        Ok(out.iter().map(Stats::from_ffi).collect())
+    }
+
     /// Gather the shards back into one host `Vec` (the type must be the buffer's own cell type).
     pub fn to_vec<T: CellEncoding + Default>(&self) -> Result<Vec<T>> {
         assert_eq!(self.ct, T::cell_type());

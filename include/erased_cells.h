@@ -777,6 +777,56 @@ ec_status ec_sharded_stats(ec_shard_group *g, ec_dtype t, const void *const *p,
                            const uint8_t *const *masks_or_null, const size_t *n, void *stats_out);
 
 /* ---------------------------------------------------------------- *
+ * Zonal statistics: the band statistics above per zone of a zone raster (land-cover classes, regions, basins) in ONE pass
+ * over the value raster and the zone raster — "mean NDVI per region" — and the way back into the raster.  The reference has
+ * nothing of the kind; the records and the fold are the band statistics' (ec_moments, ec_stats_fold), unchanged.
+ *
+ * The rule.  zt, the zone raster's cell type, is EC_U8, EC_U16 or EC_I32.  Cell i (i < n) belongs to zone z = zones[i] iff
+ * 0 <= z < n_zones and (there is no mask or mask[i] != 0).  A cell with any other id — a negative one, 255 in a u8 class raster
+ * used as "outside" — belongs to no zone and contributes nothing, whatever it holds: a NaN under a cleared mask byte or a
+ * foreign id reaches no sum.  Record z is the ec_moments that ec_stats_device writes for the cells of zone z:
+ *   kind 0  the exact count, sum and sum of squares: independent of launch shape, shard cut and order.
+ *   kind 1  s1 = sum of d, s2 = sum of fma(d, d, .), d = to_f64(x) - pivot, with the pivot of the LAUNCH: to_f64(p[0]) if
+ *           n > 0 and that is finite, else 0.0 — whatever p[0]'s mask byte or zone is; the same in every record of the call.
+ *           No float atomics anywhere: the records are a pure function of the cells, the zones and the launch plan, and the
+ *           same call twice gives the same bytes.
+ * A zone with no cells gets the empty record (count 0, the sentinels' keys, zero sums, the call's pivot); n == 0 writes
+ * n_zones empty records with pivot 0.0.  More than EC_ZONAL_MAX_ZONES zones: relabel in chunks and call again.
+ * ---------------------------------------------------------------- */
+enum { EC_ZONAL_MAX_ZONES = 256 };
+/* Bytes of the workspace ec_zonal_stats_device wants for n_zones zones (a function of n_zones only); 0 for n_zones outside
+ * 1 .. EC_ZONAL_MAX_ZONES.  Host only. */
+size_t ec_zonal_workspace_bytes(int32_t n_zones);
+/* n_zones ec_moments at DEVICE address moments_dev, record z for zone z.  Asynchronous, no allocation, no synchronisation,
+ * capturable (after ec_prepare_stream for a foreign stream); the partials go to the caller's workspace_dev
+ * (ec_zonal_workspace_bytes(n_zones) bytes, 16-byte aligned, contents scrap afterwards).  Refused before any device work, in
+ * this order: n_zones outside 1 .. EC_ZONAL_MAX_ZONES (EC_ERR_ARG); a bad t or zt (EC_ERR_UNSUPPORTED_TYPE); a null pointer
+ * (moments_dev, workspace_dev; p and zones unless n == 0); n above ec_stats_device's bound for t; moments_dev or the workspace
+ * overlapping an input or each other (all EC_ERR_ARG).  A refused call writes nothing. */
+ec_status ec_zonal_stats_device(ec_dtype t, const void *p, const uint8_t *mask_or_null, ec_dtype zt,
+                                const void *zones, size_t n, int32_t n_zones, void *moments_dev,
+                                void *workspace_dev, ec_stream stream);
+/* ec_zonal_stats_device with its workspace from the library's stream-ordered pool, an n_zones x 64-byte download and
+ * ec_stats_fold once per zone: n_zones ec_stats at HOST address stats_out.  The same refusals but the workspace's.
+ * Synchronous result. */
+ec_status ec_zonal_stats_compute(ec_dtype t, const void *p, const uint8_t *mask_or_null, ec_dtype zt,
+                                 const void *zones, size_t n, int32_t n_zones, void *stats_out, ec_stream stream);
+/* The same over a sharded raster: every shard's n_zones records come down and zone z's records are folded in shard order by
+ * ec_stats_fold.  No collective, so kind 0 equals the unsharded figures bit for bit, as ec_sharded_stats promises.
+ * masks_or_null == NULL: unmasked.  Synchronous result. */
+ec_status ec_sharded_zonal_stats(ec_shard_group *g, ec_dtype t, const void *const *p,
+                                 const uint8_t *const *masks_or_null, ec_dtype zt, const void *const *zones,
+                                 const size_t *n, int32_t n_zones, void *stats_out);
+/* The way back: dst[i] = table[zones[i]] (bits copied) with mask byte 1, for a table of n_zones cells of type t at DEVICE
+ * address table_dev — e.g. anomaly = ndvi - the mean of its zone.  A cell whose id belongs to no zone gets all-zero bits and
+ * mask byte 0; dst_mask_or_null may be NULL, the zero bits are written all the same.  Element-wise and asynchronous: any n, any
+ * cell offset, as the other element-wise entry points; n == 0 is legal.  Refused in the order above: n_zones, a bad t or zt,
+ * a null pointer (zones, table_dev, dst), more than 2^31 - 1 tiles, dst or dst_mask overlapping an input or each other.  No
+ * sharded form: run it under ec_shard_group_foreach. */
+ec_status ec_zonal_broadcast(ec_dtype zt, const void *zones, size_t n, int32_t n_zones, ec_dtype t,
+                             const void *table_dev, void *dst, uint8_t *dst_mask_or_null, ec_stream stream);
+
+/* ---------------------------------------------------------------- *
  * Test/bench support (not part of the reference surface).
  * ---------------------------------------------------------------- */
 /* x[i] = lo + splitmix64(seed ^ (base + i)) % (hi - lo + 1), t in {EC_U8, EC_U16, EC_F32}
