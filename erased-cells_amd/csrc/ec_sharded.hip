@@ -43,6 +43,7 @@
 #include "ec_collective.hpp"
 #include "ec_hostpipe.hpp"
 #include "ec_lattice.hpp"
+#include "ec_reclass_plan.hpp"
 #include "ec_runtime.hpp"
 #include "ec_worker.hpp"
 
@@ -153,6 +154,7 @@ ec_status check_group(const ec_shard_group* g, const char* what) {
 //   ec_sharded_mask_from_nodata   p, mask
 //   ec_sharded_compare            l, r, lmask and rmask where given, out_mask
 //   ec_sharded_compare_scalar     l, lmask where given, out_mask
+//   ec_sharded_reclass            src, masks where given, tables_dev, dst, dst_masks where given
 //   ec_sharded_fused              p[k] of every operand with a column, out.  NOT masks[k] and out_mask: they are copied
 //                                 unchecked, a null per-shard mask reaches ec_masked_fused as it is
 //   ec_sharded_expr               p[k] and (masked) masks[k] stream by stream, out, (masked) out_mask
@@ -584,6 +586,32 @@ extern "C" ec_status ec_sharded_cast_scaled(ec_shard_group* g, ec_dtype st_, con
                                n = copy_col(g, n)](int i) -> ec_status {
         if (n[i] == 0) return EC_OK;  // an empty shard may have no mask pointer: not the "mask without nodata" refusal
         return ec_cast_scaled(st_, src[i], m[i], n[i], scale, offset, dt, masked ? &nd : nullptr, dst[i], g->streams[i]);
+    });
+}
+
+extern "C" ec_status ec_sharded_reclass(ec_shard_group* g, ec_dtype t, const void* const* src, const uint8_t* const* masks_or_null, const size_t* n,
+                                        ec_dtype dt, const void* const* tables_dev, void* const* dst, uint8_t* const* dst_masks_or_null) {
+    const char* what = "ec_sharded_reclass";
+    ec_status st = check_group(g, what);
+    if (st != EC_OK) return st;
+    st = ec_reclass(t, nullptr, nullptr, 0, dt, nullptr, nullptr, nullptr, nullptr);  // the dtypes, before any device work
+    if (st != EC_OK) return st;
+    if (!src || !tables_dev || !dst || !n) return set_error(EC_ERR_ARG, "%s: null argument", what);
+    auto sv = take(g, what, "src", src, n, &st);
+    auto mv = take_optional(g, what, "masks", masks_or_null, n, &st);
+    auto tv = take(g, what, "tables_dev", tables_dev, n, &st);
+    auto dv = take(g, what, "dst", dst, n, &st);
+    auto omv = dst_masks_or_null ? take(g, what, "dst_masks", dst_masks_or_null, n, &st) : std::vector<uint8_t*>(g->n, nullptr);
+    if (st != EC_OK) return st;
+    for (int i = 0; i < g->n; ++i) {  // every shard's own refusals of ec_reclass, here: nothing is posted after one
+        bool bad_type = false;
+        if (const char* why = ecr::reclass_refusal(ecl::size_of(t), ecl::size_of(dt), sv[i], mv[i], n[i], tv[i], dv[i], omv[i], &bad_type))
+            return set_error(EC_ERR_ARG, "%s: shard %d: %s", what, i, why);
+    }
+    std::lock_guard<std::mutex> lk(g->call_mu);
+    return post_each_shard(g, [g, t, dt, src = std::move(sv), m = std::move(mv), tab = std::move(tv), dst = std::move(dv), om = std::move(omv),
+                               n = copy_col(g, n)](int i) {
+        return ec_reclass(t, src[i], m[i], n[i], dt, tab[i], dst[i], om[i], g->streams[i]);
     });
 }
 

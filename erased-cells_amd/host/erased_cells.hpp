@@ -521,6 +521,12 @@ public:
     // this buffer as a zone raster, each cell replaced by table[id] (ec_zonal_broadcast): a cell whose id is outside
     // 0 .. table.len() - 1 is zero and not valid in the result.  Defined below MaskedCellBuffer.
     MaskedCellBuffer broadcast(const CellBuffer& table) const;
+    // each cell replaced by the value of its class among the table's breaks, in one pass (ec_reclass; the rule is in
+    // include/erased_cells.h).  The table must have no dropped class and no nodata value (those are MaskedCellBuffer's, below).
+    CellBuffer reclassify(const class ReclassTable& table) const;
+    // a UInt8 class raster with values 0 .. breaks.size(): numpy.digitize under the reference's total order, fit for zonal_stats.
+    // Breaks of any cell type; Defined below ReclassTable.
+    template <typename BT> CellBuffer classify(const std::vector<BT>& breaks, bool right = false) const;
     static std::vector<Stats> zonal_stats_of(const CellBuffer& values, const uint8_t* mask_or_null, const CellBuffer& zones, int32_t n_zones) {
         if (zones.n_ != values.n_) throw Error(EC_ERR_LENGTH, "zonal_stats: the zone raster and the values differ in length");
         if (n_zones < 1 || n_zones > EC_ZONAL_MAX_ZONES) throw Error(EC_ERR_ARG, "zonal_stats: n_zones is not within 1 .. EC_ZONAL_MAX_ZONES; relabel in chunks");
@@ -900,6 +906,9 @@ public:
     }
     // CellBuffer::zonal_stats over the valid cells: a masked-out cell belongs to no zone, whatever it holds
     std::vector<Stats> zonal_stats(const CellBuffer& zones, int32_t n_zones) const { return CellBuffer::zonal_stats_of(buf_, mask_.ptr(), zones, n_zones); }
+    // CellBuffer::reclassify of the valid cells: a cell that is not valid receives the table's nodata value whatever it holds and stays
+    // invalid; a cell of a class the table drops becomes invalid.  The table must have been built with a nodata value.
+    MaskedCellBuffer reclassify(const class ReclassTable& table) const;
 
     // ---- per-cell order predicates ANDed, in the same launch, with the masks: a cell that is not valid satisfies none (:326-335)
     Mask compare(ec_cmp rel, const MaskedCellBuffer& rhs) const {
@@ -1004,6 +1013,61 @@ inline void composite_stack(const std::vector<const B*>& layers) {  // what the 
     }
 }
 }  // namespace detail
+
+// The table of reclassify() for rasters of one cell type: built on the host (ec_reclass_table_build), uploaded once, reusable across
+// calls on this device.  breaks: 1 .. 255 cells of type BT, strictly ascending in the union with the raster's type; values:
+// breaks.size() + 1 cells of the output type DT; valid: empty or one flag per class, a false one drops its class; nodata: given iff the
+// table is for MaskedCellBuffers.
+class ReclassTable {
+    ec_reclass_table host_;
+    std::shared_ptr<DeviceMem> mem_;
+
+public:
+    template <typename BT, typename DT>
+    ReclassTable(CellType cell_type, const std::vector<BT>& breaks, const std::vector<DT>& values, bool right = false,
+                 const std::vector<bool>& valid = {}, const CellValue* nodata = nullptr) {
+        if (values.size() != breaks.size() + 1) throw Error(EC_ERR_ARG, "reclass: breaks.size() + 1 class values are needed");
+        if (!valid.empty() && valid.size() != values.size()) throw Error(EC_ERR_ARG, "reclass: one validity flag per class");
+        std::vector<ec_value> vals;
+        for (const DT& v : values) vals.push_back(CellValue(v).raw());
+        const std::vector<uint8_t> vb(valid.begin(), valid.end());
+        check(ec_reclass_table_build(static_cast<ec_dtype>(cell_type), static_cast<ec_dtype>(CellEncoding<BT>::cell_type()), breaks.data(),
+                                     static_cast<int32_t>(breaks.size() > 256 ? 256 : breaks.size()), right ? 1 : 0,
+                                     static_cast<ec_dtype>(CellEncoding<DT>::cell_type()), vals.data(), vb.empty() ? nullptr : vb.data(),
+                                     nodata ? &nodata->raw() : nullptr, &host_));
+        mem_ = std::make_shared<DeviceMem>(sizeof host_);
+        check(ec_upload(mem_->ptr(), &host_, sizeof host_, current_stream()));
+    }
+    const ec_reclass_table& record() const { return host_; }
+    const void* ptr() const { return mem_->ptr(); }
+    CellType cell_type() const { return static_cast<CellType>(host_.t); }
+    CellType result_type() const { return static_cast<CellType>(host_.dt); }
+    bool has_nodata() const { return (host_.flags & EC_RECLASS_HAS_NODATA) != 0; }
+    bool drops() const { return (host_.flags & EC_RECLASS_DROPS) != 0; }
+};
+
+inline CellBuffer CellBuffer::reclassify(const ReclassTable& table) const {
+    if (table.cell_type() != ct_) throw Error(EC_ERR_ARG, "reclassify: the table is for rasters of another cell type");
+    if (table.has_nodata() || table.drops()) throw Error(EC_ERR_ARG, "reclassify: a table with a nodata value or a dropped class is for MaskedCellBuffers");
+    CellBuffer out(table.result_type(), n_);
+    check(ec_reclass(static_cast<ec_dtype>(ct_), ptr(), nullptr, n_, static_cast<ec_dtype>(table.result_type()), table.ptr(), out.ptr(), nullptr, current_stream()));
+    return out;
+}
+template <typename BT>
+inline CellBuffer CellBuffer::classify(const std::vector<BT>& breaks, bool right) const {
+    std::vector<uint8_t> ids(breaks.size() + 1);
+    for (size_t c = 0; c < ids.size(); ++c) ids[c] = static_cast<uint8_t>(c);
+    return reclassify(ReclassTable(ct_, breaks, ids, right));
+}
+inline MaskedCellBuffer MaskedCellBuffer::reclassify(const ReclassTable& table) const {
+    if (table.cell_type() != cell_type()) throw Error(EC_ERR_ARG, "reclassify: the table is for rasters of another cell type");
+    if (!table.has_nodata()) throw Error(EC_ERR_ARG, "reclassify: a table for MaskedCellBuffers is built with a nodata value");
+    CellBuffer out(table.result_type(), len());
+    Mask m(len());
+    check(ec_reclass(static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), len(), static_cast<ec_dtype>(table.result_type()), table.ptr(), out.ptr(),
+                     m.ptr(), current_stream()));
+    return MaskedCellBuffer(std::move(out), std::move(m));
+}
 
 inline MaskedCellBuffer CellBuffer::broadcast(const CellBuffer& table) const {
     if (table.n_ < 1 || table.n_ > size_t(EC_ZONAL_MAX_ZONES)) throw Error(EC_ERR_ARG, "broadcast: the table is not of 1 .. EC_ZONAL_MAX_ZONES cells");

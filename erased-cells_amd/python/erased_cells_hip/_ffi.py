@@ -28,6 +28,8 @@ EC_FOCAL_WHOLE, EC_FOCAL_NORMALIZE = 1, 2  # flags of ec_focal / ec_focal_convol
 EC_COMPOSITE_FIRST, EC_COMPOSITE_LAST, EC_COMPOSITE_MIN, EC_COMPOSITE_MAX, EC_COMPOSITE_SUM, EC_COMPOSITE_MEAN = range(6)  # ec_composite_op
 EC_COMPOSITE_MAX_LAYERS, EC_COMPOSITE_NONE = 64, 255
 EC_ZONAL_MAX_ZONES = 256
+EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES = 255, 4384
+EC_RECLASS_HAS_NODATA, EC_RECLASS_DROPS = 1, 2  # ec_reclass_table.flags
 
 
 class _Payload(C.Union):
@@ -68,6 +70,13 @@ class EcStats(C.Structure):
     """ec_stats: what ec_stats_fold makes of one or several records."""
     _fields_ = [("count", C.c_uint64), ("min", EcValue), ("max", EcValue), ("sum", C.c_double), ("mean", C.c_double),
                 ("stddev", C.c_double)]
+
+
+class EcReclassTable(C.Structure):
+    """ec_reclass_table: what ec_reclass_table_build writes and ec_reclass reads on the device (include/erased_cells.h)."""
+    _fields_ = [("t", C.c_int32), ("dt", C.c_int32), ("n_breaks", C.c_int32), ("n_reached", C.c_int32), ("flags", C.c_uint32),
+                ("reserved0", C.c_uint32), ("nodata_bits", C.c_uint64), ("reserved1", C.c_uint64), ("thr", C.c_int64 * 255),
+                ("value_bits", C.c_uint64 * 256), ("valid", C.c_uint8 * 256)]
 
 
 VP, SZ, I32, U8P = C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p
@@ -200,6 +209,9 @@ SIGNATURES = {
     "ec_zonal_stats_compute": (I32, [C.c_uint8, VP, U8P, C.c_uint8, VP, SZ, I32, VP, VP]),
     "ec_sharded_zonal_stats": (I32, [VP, C.c_uint8, PVP, PVP, C.c_uint8, PVP, PSZ, I32, VP]),
     "ec_zonal_broadcast": (I32, [C.c_uint8, VP, SZ, I32, C.c_uint8, VP, VP, U8P, VP]),
+    "ec_reclass_table_build": (I32, [C.c_uint8, C.c_uint8, VP, I32, I32, C.c_uint8, PV, U8P, PV, VP]),
+    "ec_reclass": (I32, [C.c_uint8, VP, U8P, SZ, C.c_uint8, VP, VP, U8P, VP]),
+    "ec_sharded_reclass": (I32, [VP, C.c_uint8, PVP, PVP, PSZ, C.c_uint8, PVP, PVP, PVP]),
     "ec_composite_result_type": (C.c_uint8, [I32, C.c_uint8]),
     "ec_composite": (I32, [I32, C.c_uint8, PVP, PVP, I32, SZ, C.c_uint32, VP, U8P, U8P, VP]),
     "ec_sharded_composite": (I32, [VP, I32, C.c_uint8, C.POINTER(PVP), C.POINTER(PVP), I32, PSZ, C.c_uint32, PVP, PVP, PVP]),

@@ -20,7 +20,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_COMPOSITE_MAX_LAYERS, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_ZONAL_MAX_ZONES, EC_RESAMPLE_BILINEAR, EcError, EcStats, EcValue, check, lib
+from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_COMPOSITE_MAX_LAYERS, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_ZONAL_MAX_ZONES, EC_RECLASS_DROPS, EC_RECLASS_HAS_NODATA, EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES, EC_RESAMPLE_BILINEAR, EcError, EcReclassTable, EcStats, EcValue, check, lib
 
 # CellType (src/ctype.rs:11-20; order of with_ct!, src/lib.rs:89-98)
 UInt8, UInt16, UInt32, UInt64, Int8, Int16, Int32, Int64, Float32, Float64 = range(10)
@@ -710,6 +710,20 @@ class CellBuffer:
         check(lib().ec_zonal_broadcast(self.ct, self.mem.ptr, self.n, table.n, table.ct, table.mem.ptr, out.mem.ptr, om.ptr, _stream))
         return MaskedCellBuffer(out, Mask(self.n, om))
 
+    def reclassify(self, table_or_breaks, values=None, right: bool = False, dtype: Optional[int] = None, valid=None, breaks_dtype: Optional[int] = None):
+        """Each cell replaced by the value of its class among the breaks, in one pass (ec_reclass; the rule is in
+        include/erased_cells.h): class c = the number of breaks <= the cell (`right`: < the cell), result `values[c]`.  Pass a
+        ReclassTable to reuse one across calls, or breaks and `len(breaks) + 1` values.  A CellBuffer comes back — or, when `valid`
+        drops a class, a MaskedCellBuffer whose mask is 0 in the dropped classes."""
+        table = _reclass_table(self.ct, table_or_breaks, values, right, dtype, valid, None, breaks_dtype)
+        out, om = _reclass(self, None, table, table.drops)
+        return MaskedCellBuffer(out, om) if om is not None else out
+
+    def classify(self, breaks, right: bool = False, breaks_dtype: Optional[int] = None) -> "CellBuffer":
+        """A UInt8 class raster with values 0 .. len(breaks): numpy.digitize(cells, breaks, right) under the reference's total order,
+        fit for `zonal_stats` — `[s.count for s in x.zonal_stats(x.classify(edges), len(edges) + 1)]` is a histogram."""
+        return self.reclassify(breaks, np.arange(len(breaks) + 1, dtype=np.uint8), right=right, breaks_dtype=breaks_dtype)
+
     # ---- arithmetic (src/buffer.rs:321-371)
     def _binop(self, op: int, rhs) -> "CellBuffer":
         if isinstance(rhs, CellBuffer):
@@ -1123,6 +1137,19 @@ class MaskedCellBuffer:
         """`CellBuffer.zonal_stats` over the valid cells: a masked-out cell belongs to no zone, whatever it holds."""
         return _zonal_stats(self._buf, self._mask, zones, n_zones)
 
+    def reclassify(self, table_or_breaks, values=None, right: bool = False, dtype: Optional[int] = None, valid=None, nodata=None,
+                   breaks_dtype: Optional[int] = None) -> "MaskedCellBuffer":
+        """`CellBuffer.reclassify` of the valid cells: a cell that is not valid receives `nodata` (default: 0) whatever it holds and stays
+        invalid; a cell of a class that `valid` drops becomes invalid.  A ReclassTable must have been built with a nodata value."""
+        table = _reclass_table(self.cell_type(), table_or_breaks, values, right, dtype, valid, 0 if nodata is None else nodata, breaks_dtype)
+        out, om = _reclass(self._buf, self._mask, table, True)
+        return MaskedCellBuffer(out, om)
+
+    def classify(self, breaks, right: bool = False, breaks_dtype: Optional[int] = None) -> "MaskedCellBuffer":
+        """`CellBuffer.classify` of the valid cells; a cell that is not valid holds 255 (0 with 255 breaks) and stays invalid."""
+        return self.reclassify(breaks, np.arange(len(breaks) + 1, dtype=np.uint8), right=right, nodata=255 if len(breaks) < 255 else 0,
+                               breaks_dtype=breaks_dtype)
+
     # ---- arithmetic (src/masked/masked_buffer.rs:323-383)
     def _binop(self, op: int, rhs) -> "MaskedCellBuffer":
         if isinstance(rhs, MaskedCellBuffer):
@@ -1231,6 +1258,99 @@ def _zonal_stats(buf: "CellBuffer", mask, zones, n_zones: int) -> list:
     check(lib().ec_zonal_stats_compute(buf.ct, buf.mem.ptr, mask.mem.ptr if mask is not None else None, zones.ct, zones.mem.ptr, buf.n,
                                        int(n_zones), out, _stream))
     return [Stats.from_ec(s) for s in out]
+
+
+def _typed_array(what: str, xs, ct: Optional[int], default_for_numbers) -> np.ndarray:
+    """`xs` as a 1-D array of a cell type: `ct` when given, else its own numpy type, else `default_for_numbers(list)` for Python numbers"""
+    if ct is None and isinstance(xs, np.ndarray) and xs.dtype in NP_DTYPES:
+        return np.ascontiguousarray(xs).reshape(-1)
+    lst = [x.value if isinstance(x, CellValue) else x for x in (xs.tolist() if isinstance(xs, np.ndarray) else list(xs))]
+    if any(isinstance(x, bool) for x in lst):
+        raise EcError(EC_ERR_ARG, f"reclass: a bool among the {what}")
+    ct = default_for_numbers(lst) if ct is None else ct
+    with np.errstate(all="ignore"):
+        return np.array(lst, dtype=NP_DTYPES[ct])
+
+
+def _fits_exactly(lst, ct: int) -> bool:
+    """every number is integral and a cell of type ct holds it exactly"""
+    try:
+        if not all(float(x).is_integer() for x in lst):
+            return False
+        with np.errstate(all="ignore"):
+            a = np.array(lst, dtype=NP_DTYPES[ct])
+        return all(int(a[i]) == int(x) for i, x in enumerate(lst))
+    except (OverflowError, ValueError, TypeError):
+        return False
+
+
+class ReclassTable:
+    """The table of `CellBuffer.reclassify` for rasters of type `cell_type`: built on the host (ec_reclass_table_build), uploaded
+    once, reusable across calls on this device.  `breaks`: 1 .. 255 numbers, strictly ascending; Python numbers are cells of type
+    `cell_type` when all are integral and fit it, else Float64 (`breaks_dtype` overrides; a numpy array keeps its type).
+    `values`: len(breaks) + 1 cells of the output type `dtype` (default: a numpy array's own type; Python numbers UInt8 when they
+    fit, else Int32, else Float64).  `valid`: len(breaks) + 1 flags, a false one drops its class.  `nodata`: given iff the table
+    is for MaskedCellBuffers — what a cell that is not valid receives."""
+
+    def __init__(self, cell_type: int, breaks, values, right: bool = False, dtype: Optional[int] = None, valid=None, nodata=None,
+                 breaks_dtype: Optional[int] = None):
+        b = _typed_array("breaks", breaks, breaks_dtype, lambda l: cell_type if _fits_exactly(l, cell_type) else Float64)
+        v = _typed_array("values", values, dtype,
+                         lambda l: UInt8 if _fits_exactly(l, UInt8) else Int32 if _fits_exactly(l, Int32) else Float64)
+        bt, dt = cell_type_of(b.dtype), cell_type_of(v.dtype)
+        if not 1 <= b.size <= EC_RECLASS_MAX_BREAKS:
+            raise EcError(EC_ERR_ARG, f"reclass: {b.size} breaks, not within 1 .. EC_RECLASS_MAX_BREAKS ({EC_RECLASS_MAX_BREAKS})")
+        if v.size != b.size + 1:
+            raise EcError(EC_ERR_ARG, f"reclass: {v.size} class values for {b.size} breaks, not {b.size + 1}")
+        if valid is not None and len(valid) != v.size:
+            raise EcError(EC_ERR_ARG, f"reclass: {len(valid)} validity flags for {v.size} classes")
+        if isinstance(right, (bool, np.bool_)):
+            right = int(right)
+        evs = (EcValue * v.size)(*[CellValue(dt, x).to_ec() for x in v])
+        vb = (C.c_uint8 * v.size)(*[1 if x else 0 for x in valid]) if valid is not None else None
+        nd = (nodata if isinstance(nodata, CellValue) else CellValue(dt, nodata)).to_ec() if nodata is not None else None
+        self.host = EcReclassTable()
+        check(lib().ec_reclass_table_build(cell_type, bt, b.ctypes.data_as(C.c_void_p), b.size, right, dt, evs, vb,
+                                           C.byref(nd) if nd is not None else None, C.byref(self.host)))
+        self.ct, self.bt, self.dt, self.n_breaks = cell_type, bt, dt, int(b.size)
+        self.has_nodata = bool(self.host.flags & EC_RECLASS_HAS_NODATA)
+        self.drops = bool(self.host.flags & EC_RECLASS_DROPS)
+        self._mem = None
+
+    def bytes(self) -> bytes:
+        return C.string_at(C.byref(self.host), EC_RECLASS_TABLE_BYTES)
+
+    @property
+    def mem(self) -> DeviceMem:
+        """the device copy (uploaded at first use: building a table needs no device)"""
+        if self._mem is None:
+            self._mem = _upload(np.frombuffer(self.bytes(), dtype=np.uint8))
+        return self._mem
+
+
+def _reclass_table(ct: int, table_or_breaks, values, right, dtype, valid, nodata, breaks_dtype) -> ReclassTable:
+    """the ReclassTable of a reclassify call: the one given (checked against the call) or one built from the breaks"""
+    if not isinstance(table_or_breaks, ReclassTable):
+        if values is None:
+            raise EcError(EC_ERR_ARG, "reclassify: breaks without class values")
+        return ReclassTable(ct, table_or_breaks, values, right, dtype, valid, nodata, breaks_dtype)
+    t = table_or_breaks
+    if values is not None or valid is not None or dtype is not None or breaks_dtype is not None:
+        raise EcError(EC_ERR_ARG, "reclassify: a ReclassTable carries its own values, validity and types")
+    if t.ct != ct:
+        raise EcError(EC_ERR_ARG, f"reclassify: the table is for {CT_NAMES[t.ct]} rasters, this one is {CT_NAMES[ct]}")
+    if t.has_nodata != (nodata is not None):
+        raise EcError(EC_ERR_ARG, "reclassify: a table built with a nodata value is for MaskedCellBuffers, one without for CellBuffers")
+    return t
+
+
+def _reclass(buf: "CellBuffer", mask, table: ReclassTable, want_mask: bool):
+    """ec_reclass of `buf` under `mask` (or None) -> (result buffer, result Mask or None)"""
+    out = CellBuffer.empty(buf.n, table.dt)
+    om = Mask.empty(buf.n) if want_mask else None
+    check(lib().ec_reclass(buf.ct, buf.mem.ptr, mask.mem.ptr if mask is not None else None, buf.n, table.dt, table.mem.ptr, out.mem.ptr,
+                           om.mem.ptr if om is not None else None, _stream))
+    return out, om
 
 
 # the spellings of an ec_composite_op

@@ -111,6 +111,9 @@ class ShardGroup:
 
     def close(self) -> None:
         if self.handle:
+            for tabs in getattr(self, "_owned_tables", []):   # the reclass tables replicated by reclassify()
+                tabs.free()
+            self._owned_tables = []
             check(lib().ec_shard_group_destroy(self.handle))
             self.handle = C.c_void_p()
 
@@ -225,6 +228,42 @@ class ShardGroup:
         check(lib().ec_sharded_cast_scaled(self.handle, src.ct, src.ptrs, mask.ptrs if mask is not None else None, (C.c_size_t * self.n)(*src.lens),
                                            float(scale), float(offset), ct, C.byref(ev) if ev is not None else None, out.ptrs))
         return out
+
+    def reclass_table(self, table: "B.ReclassTable") -> ShardedBuffer:
+        """The table's record on every shard's device (ct = UInt8, EC_RECLASS_TABLE_BYTES each): replicate once, reuse across calls,
+        `free()` it like any sharded buffer once the calls that use it have run."""
+        from ._ffi import EC_RECLASS_TABLE_BYTES
+        out = self.alloc(B.UInt8, [EC_RECLASS_TABLE_BYTES] * self.n)
+        out.host = C.create_string_buffer(table.bytes(), EC_RECLASS_TABLE_BYTES)   # the source of the uploads: kept with the buffer
+        check(lib().ec_sharded_upload(self.handle, out.ptrs, out.host, (C.c_size_t * self.n)(*[0] * self.n), self._sizes(out.lens, 1)))
+        out.table = table
+        return out
+
+    def reclassify(self, src: ShardedBuffer, table_or_breaks, values=None, right: bool = False, dtype: int = None, valid=None,
+                   mask: ShardedBuffer = None, nodata=None, breaks_dtype: int = None):
+        """`reclassify` on every shard, fire-and-forget.  `table_or_breaks`: a replicated table (`reclass_table`), a ReclassTable or
+        breaks with `values`; a table made here is replicated and freed by `close()`.  `mask` (sharded like `src`): the masked
+        form, `nodata` (default 0) stored where it is 0.  Returns the sharded result — `(result, mask)` with a mask or a dropped class."""
+        assert mask is None or mask.lens == src.lens, "the mask must be sharded like its operand"
+        if isinstance(table_or_breaks, ShardedBuffer):
+            tabs = table_or_breaks
+            B._reclass_table(src.ct, tabs.table, values, right, dtype, valid, None if mask is None else 0, breaks_dtype)   # the checks
+        else:
+            nd = None if mask is None else (0 if nodata is None else nodata)
+            tabs = self.reclass_table(B._reclass_table(src.ct, table_or_breaks, values, right, dtype, valid, nd, breaks_dtype))
+            self._owned_tables = getattr(self, "_owned_tables", []) + [tabs]
+        table = tabs.table
+        out = self.alloc(table.dt, src.lens)
+        om = self.alloc(B.UInt8, src.lens) if (mask is not None or table.drops) else None
+        check(lib().ec_sharded_reclass(self.handle, src.ct, src.ptrs, mask.ptrs if mask is not None else None, (C.c_size_t * self.n)(*src.lens),
+                                       table.dt, tabs.ptrs, out.ptrs, om.ptrs if om is not None else None))
+        return (out, om) if om is not None else out
+
+    def classify(self, src: ShardedBuffer, breaks, right: bool = False, mask: ShardedBuffer = None, breaks_dtype: int = None):
+        """`classify` on every shard: a sharded UInt8 class raster with values 0 .. len(breaks), `(classes, mask)` with a mask."""
+        import numpy as np
+        return self.reclassify(src, breaks, np.arange(len(breaks) + 1, dtype=np.uint8), right=right, mask=mask,
+                               nodata=None if mask is None else (255 if len(breaks) < 255 else 0), breaks_dtype=breaks_dtype)
 
     def composite(self, layers, op="first", min_count: int = 1, aux: bool = False, masks=None):
         """`composite` on every shard, fire-and-forget: `layers` up to 64 identically sharded buffers of one cell type, `masks` (optional)

@@ -806,3 +806,78 @@ impl CellBuffer {
         Ok((out, mask))
     }
 }
+
+/// The table of [`CellBuffer::reclassify`] for rasters of one cell type: built on the host (`ec_reclass_table_build`), uploaded once,
+/// reusable across calls on this device.  The rule is at `ec_reclass` in include/erased_cells.h.
+pub struct ReclassTable {
+    pub(crate) host: Box<ec_reclass_table>,
+    pub(crate) mem: DeviceMem,
+}
+
+impl ReclassTable {
+    /// `breaks`: 1 ..= 255 cells of type `B`, strictly ascending in the union with `cell_type`, none NaN; `values`: one cell of the
+    /// output type `D` per class (`breaks.len() + 1`); `valid`: empty, or one flag per class — a false one drops its class;
+    /// `nodata`: given iff the table is for [`MaskedCellBuffer`]s, what a cell that is not valid receives.
+    pub fn new<B: CellEncoding, D: CellEncoding>(
+        cell_type: CellType, breaks: &[B], values: &[D], right: bool, valid: &[bool], nodata: Option<D>,
+    ) -> Result<Self> {
+        assert!((1..=EC_RECLASS_MAX_BREAKS).contains(&breaks.len()), "1 .. {EC_RECLASS_MAX_BREAKS} breaks, not {}", breaks.len());
+        assert_eq!(values.len(), breaks.len() + 1, "one class value more than there are breaks");
+        assert!(valid.is_empty() || valid.len() == values.len(), "one validity flag per class");
+        let vals: Vec<ec_value> = values.iter().map(|v| CellValue::new(*v).to_ffi()).collect();
+        let flags: Vec<u8> = valid.iter().map(|v| *v as u8).collect();
+        let marker = nodata.map(|v| CellValue::new(v).to_ffi());
+        let mut host: Box<ec_reclass_table> = Box::new(unsafe { std::mem::zeroed() });
+        check(unsafe {
+            ec_reclass_table_build(cell_type as u8, B::cell_type() as u8, breaks.as_ptr() as *const c_void, breaks.len() as i32, right as i32,
+                                   D::cell_type() as u8, vals.as_ptr(), if flags.is_empty() { std::ptr::null() } else { flags.as_ptr() },
+                                   marker.as_ref().map_or(std::ptr::null(), |m| m as *const ec_value),
+                                   &mut *host as *mut ec_reclass_table as *mut c_void)
+        })?;
+        let mem = DeviceMem::new(EC_RECLASS_TABLE_BYTES);
+        upload(mem.ptr(), std::slice::from_ref(&*host));
+        Ok(ReclassTable { host, mem })
+    }
+
+    pub fn cell_type(&self) -> CellType {
+        CellType::from_code(self.host.t as u8)
+    }
+    pub fn result_type(&self) -> CellType {
+        CellType::from_code(self.host.dt as u8)
+    }
+    pub fn has_nodata(&self) -> bool {
+        self.host.flags & EC_RECLASS_HAS_NODATA != 0
+    }
+    pub fn drops(&self) -> bool {
+        self.host.flags & EC_RECLASS_DROPS != 0
+    }
+}
+
+impl CellBuffer {
+    /// `ec_reclass` of these cells under `mask` (device bytes, or null) into a new buffer, with the result's mask when asked for.
+    pub(crate) fn reclass_raw(&self, mask: *const u8, table: &ReclassTable, want_mask: bool) -> Result<(CellBuffer, Option<Mask>)> {
+        assert_eq!(table.cell_type(), self.ct, "the table is for rasters of another cell type");
+        assert_eq!(table.has_nodata(), !mask.is_null(), "a table built with a nodata value is for masked rasters, one without for plain ones");
+        assert!(want_mask || !table.drops(), "a table that drops a class needs the result's mask");
+        let out = Self::uninit(table.result_type(), self.len);
+        let om = if want_mask { Some(Mask::uninit(self.len)) } else { None };
+        check(unsafe {
+            ec_reclass(self.ct as u8, self.dev_ptr(), mask, self.len, table.result_type() as u8, table.mem.ptr(), out.mem.ptr(),
+                       om.as_ref().map_or(std::ptr::null_mut(), |m| m.dev_ptr_mut()), stream())
+        })?;
+        Ok((out, om))
+    }
+
+    /// Each cell replaced by the value of its class among the table's breaks, in one pass.  The table drops no class (that form
+    /// is [`MaskedCellBuffer::reclassify`]'s).
+    pub fn reclassify(&self, table: &ReclassTable) -> Result<CellBuffer> {
+        Ok(self.reclass_raw(std::ptr::null(), table, false)?.0)
+    }
+
+    /// A `UInt8` class raster with values `0 ..= breaks.len()`: class `c` = the number of breaks `<=` the cell (`right`: `<`) under
+    /// the reference's total order — fit for [`CellBuffer::zonal_stats`], whose counts are then a histogram.
+    pub fn classify<B: CellEncoding>(&self, breaks: &[B], right: bool) -> Result<CellBuffer> {
+        let ids: Vec<u8> = (0..=breaks.len()).map(|c| c as u8).collect();
+        self.reclassify(&ReclassTable::new::<B, u8>(self.ct, breaks, &ids, right, &[], None)?)
+    }
+}

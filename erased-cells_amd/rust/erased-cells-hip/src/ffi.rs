@@ -62,6 +62,11 @@ pub const EC_FOCAL_WHOLE: u32 = 1;
 pub const EC_FOCAL_NORMALIZE: u32 = 2;
 /// The most zones one `ec_zonal_stats_*` call serves (`EC_ZONAL_MAX_ZONES`).
 pub const EC_ZONAL_MAX_ZONES: usize = 256;
+/// The most breaks one reclass table holds (`EC_RECLASS_MAX_BREAKS`), the size of its record and the flags of the record.
+pub const EC_RECLASS_MAX_BREAKS: usize = 255;
+pub const EC_RECLASS_TABLE_BYTES: usize = 4384;
+pub const EC_RECLASS_HAS_NODATA: u32 = 1;
+pub const EC_RECLASS_DROPS: u32 = 2;
 /// `ec_composite_op`: what `ec_composite` keeps of a cell's stack of layers (it takes it as an `i32`).
 pub const EC_COMPOSITE_FIRST: i32 = 0;
 pub const EC_COMPOSITE_LAST: i32 = 1;
@@ -93,6 +98,23 @@ pub struct ec_moments {
     pub dtype: i32,
     pub moments: [u64; 3],
     pub reserved: u64,
+}
+
+/// Mirrors `ec_reclass_table`: what `ec_reclass_table_build` writes and `ec_reclass` reads on the device, every byte defined.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ec_reclass_table {
+    pub t: i32,
+    pub dt: i32,
+    pub n_breaks: i32,
+    pub n_reached: i32,
+    pub flags: u32,
+    pub reserved0: u32,
+    pub nodata_bits: u64,
+    pub reserved1: u64,
+    pub thr: [i64; 255],
+    pub value_bits: [u64; 256],
+    pub valid: [u8; 256],
 }
 
 /// Mirrors `ec_stats`: what `ec_stats_fold` makes of one or several records.
@@ -313,6 +335,15 @@ extern "C" {
                                   zt: ec_dtype, zones: *const *const c_void, n: *const usize, n_zones: i32, stats_out: *mut c_void) -> ec_status;
     pub fn ec_zonal_broadcast(zt: ec_dtype, zones: *const c_void, n: usize, n_zones: i32, t: ec_dtype, table_dev: *const c_void,
                               dst: *mut c_void, dst_mask_or_null: *mut u8, stream: ec_stream) -> ec_status;
+    // a raster classified by break values: the table built on the host, uploaded by the caller, read by every launch
+    pub fn ec_reclass_table_build(t: ec_dtype, bt: ec_dtype, breaks_host: *const c_void, n_breaks: i32, right: i32, dt: ec_dtype,
+                                  values: *const ec_value, valid_or_null: *const u8, nodata_or_null: *const ec_value,
+                                  table_host_out: *mut c_void) -> ec_status;
+    pub fn ec_reclass(t: ec_dtype, src: *const c_void, mask_or_null: *const u8, n: usize, dt: ec_dtype, table_dev: *const c_void,
+                      dst: *mut c_void, dst_mask_or_null: *mut u8, stream: ec_stream) -> ec_status;
+    pub fn ec_sharded_reclass(g: *mut ec_shard_group, t: ec_dtype, src: *const *const c_void, masks_or_null: *const *const u8,
+                              n: *const usize, dt: ec_dtype, tables_dev: *const *const c_void, dst: *const *mut c_void,
+                              dst_masks_or_null: *const *mut u8) -> ec_status;
     pub fn ec_shard_range(n_rows: u64, n_cols: u64, shard: u32, n_shards: u32, cell_offset: *mut u64,
                           cell_len: *mut u64) -> ec_status;
 

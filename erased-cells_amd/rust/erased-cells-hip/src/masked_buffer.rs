@@ -510,3 +510,19 @@ impl MaskedCellBuffer {
         Ok(MaskedCellBuffer(cells, mask))
     }
 }
+
+impl MaskedCellBuffer {
+    /// [`CellBuffer::reclassify`] of the valid cells: a cell that is not valid receives the table's nodata value whatever it holds
+    /// and stays invalid; a cell of a class the table drops becomes invalid.
+    pub fn reclassify(&self, table: &crate::ReclassTable) -> Result<Self> {
+        let (cells, mask) = self.0.reclass_raw(self.1.dev_ptr(), table, true)?;
+        Ok(MaskedCellBuffer(cells, mask.expect("asked for")))
+    }
+
+    /// [`CellBuffer::classify`] of the valid cells; a cell that is not valid holds 255 (0 with 255 breaks) and stays invalid.
+    pub fn classify<B: CellEncoding>(&self, breaks: &[B], right: bool) -> Result<Self> {
+        let ids: Vec<u8> = (0..=breaks.len()).map(|c| c as u8).collect();
+        let nodata = if breaks.len() < 255 { 255u8 } else { 0u8 };
+        self.reclassify(&crate::ReclassTable::new::<B, u8>(self.cell_type(), breaks, &ids, right, &[], Some(nodata))?)
+    }
+}

@@ -323,6 +323,28 @@ impl ShardedCellBuffer<'_> {
         Ok(out.iter().map(Stats::from_ffi).collect())
     }
 
+    /// [`CellBuffer::reclassify`] on every shard (no communication, fire-and-forget).  `tables`: the table's record on every
+    /// shard's device — a `UInt8` buffer of `EC_RECLASS_TABLE_BYTES` per shard, uploaded by the caller ([`ShardGroup::scatter`] of the
+    /// record's bytes repeated, one row of `EC_RECLASS_TABLE_BYTES` cells per shard) — for rasters of this cell type, results of `result_type`; `mask`: a `UInt8` raster of 0 / 1 bytes cut the
+    /// same way, given iff the table was built with a nodata value.  Returns the result and, when asked for, its mask.
+    pub fn reclassify(&self, tables: &Self, result_type: CellType, mask: Option<&Self>, want_mask: bool) -> Result<(Self, Option<Self>)> {
+        assert!(tables.ct == CellType::UInt8 && tables.lens.iter().all(|l| *l == EC_RECLASS_TABLE_BYTES), "one record per shard");
+        if let Some(m) = mask {
+            assert_eq!(m.ct, CellType::UInt8, "a mask is UInt8 bytes");
+            assert_eq!(m.lens, self.lens, "the mask must be sharded identically");
+        }
+        let out = self.alloc_like(result_type)?;
+        let om = if want_mask { Some(self.alloc_like(CellType::UInt8)?) } else { None };
+        let masks: Vec<*const u8> = mask.map_or(Vec::new(), |m| m.ptrs.iter().map(|p| *p as *const u8).collect());
+        let out_masks: Vec<*mut u8> = om.as_ref().map_or(Vec::new(), |m| m.ptrs.iter().map(|p| *p as *mut u8).collect());
+        check(unsafe {
+            ec_sharded_reclass(self.group.g, self.ct as u8, self.const_ptrs().as_ptr(), if mask.is_some() { masks.as_ptr() } else { ptr::null() },
+                               self.lens.as_ptr(), result_type as u8, tables.const_ptrs().as_ptr(), out.ptrs.as_ptr(),
+                               if want_mask { out_masks.as_ptr() } else { ptr::null() })
+        })?;
+        Ok((out, om))
+    }
+
     /// Gather the shards back into one host `Vec` (the type must be the buffer's own cell type).
     pub fn to_vec<T: CellEncoding + Default>(&self) -> Result<Vec<T>> {
         assert_eq!(self.ct, T::cell_type());

@@ -827,6 +827,84 @@ ec_status ec_zonal_broadcast(ec_dtype zt, const void *zones, size_t n, int32_t n
                              const void *table_dev, void *dst, uint8_t *dst_mask_or_null, ec_stream stream);
 
 /* ---------------------------------------------------------------- *
+ * Reclassification: a raster classified by break values in ONE pass — NDVI into vegetation classes, a DEM into elevation
+ * bands, a 16-bit band into a 256-level stretch — where a chain of ec_compare_scalar and ec_select takes a pass per class
+ * boundary.  A class raster is a zone raster: ec_reclass then ec_zonal_stats_* is "statistics per class", and its counts are
+ * a histogram over any breaks, masked and sharded, in exact integers.  The reference has nothing of the kind; the order is
+ * its own (impl Ord for CellValue, src/value.rs:248-265), exactly as ec_compare_scalar decides >=.
+ *
+ * The rule.  A value raster of cell type t, n_breaks break values b[0 .. n_breaks) of cell type bt (1 <= n_breaks <=
+ * EC_RECLASS_MAX_BREAKS), a flag right, n_breaks + 1 class values of the output type dt, an optional validity byte per
+ * class, and a nodata value of type dt iff the raster has a mask.
+ *   Order    A cell x and a break are compared as ec_compare_scalar compares them: both converted to UT = CellType::union(t, bt)
+ *            (`unify`, src/value.rs:103-107) and compared there, integers naturally, f32 / f64 by total_cmp: -0.0 < +0.0, a
+ *            negative NaN below -inf, a positive NaN above +inf.  A u64 cell 2^53 + 1 against i64 or f64 breaks compares in
+ *            Float64 (it equals a break 2^53); against u64 breaks it compares exactly.
+ *   Breaks   strictly ascending in that order after conversion to UT, none a NaN; the builder refuses both.  NaN CELLS are
+ *            classified by the total order all the same: with breaks {..., +inf} and right = 1 the top class holds exactly the
+ *            positive NaNs; with breaks {-inf, ...} and right = 0 class 0 holds exactly the negative NaNs.
+ *   Class    right = 0: c = #{ j : b[j] <= x }, the intervals [b[j-1], b[j]) — numpy.digitize(x, b, right=False);
+ *            right = 1: c = #{ j : b[j] <  x }, the intervals (b[j-1], b[j]].  In both 0 <= c <= n_breaks.
+ *   Output   no mask or mask[i] != 0: dst[i] = values[c], bits copied, whatever valid[c] says (a class to be dropped gets the
+ *            nodata value as its class value).  mask[i] == 0: dst[i] = nodata, whatever the cell holds — a NaN under a cleared
+ *            mask byte leaves no trace (the ec_cast_scaled convention).
+ *            dst_mask[i] = (mask ? mask[i] != 0 : 1) & (valid ? valid[c] != 0 : 1), written as 0 / 1 iff dst_mask_or_null is
+ *            given; it is required when a validity byte is zero (EC_RECLASS_DROPS in the table's flags says so).
+ * A pure function of the cells: no tolerance anywhere.
+ *
+ * The table.  t -> UT is monotone in t's own order and no break is a NaN, so "UT(x) >= b[j]" (right = 1: ">") over the cells
+ * of type t is "key(x) >= thr[j]" for ONE threshold in t's order keys (the int64 keys of ec_min_max_keys), found on the host by
+ * bisection.  A break no cell of type t reaches (300.0 for a u8 raster) has no threshold; breaks ascend, so these are a suffix:
+ * thr[0 .. n_reached) are the thresholds, non-descending (0.2 and 0.7 against an integer raster give the same one; the class
+ * between them is empty), and c = #{ j < n_reached : thr[j] <= key(x) }.  The kernels therefore know neither bt nor right.
+ * ---------------------------------------------------------------- */
+enum { EC_RECLASS_MAX_BREAKS = 255 };     /* up to 256 classes: a UInt8 class raster, EC_ZONAL_MAX_ZONES zones */
+enum { EC_RECLASS_HAS_NODATA = 1, EC_RECLASS_DROPS = 2 };  /* ec_reclass_table.flags */
+/* What ec_reclass_table_build writes and ec_reclass reads: a fixed-size record with every byte defined (reserved fields, unused
+ * thresholds, slots past n_breaks and the high bytes of a value slot are 0), so the same arguments give the same bytes. */
+typedef struct ec_reclass_table {
+    int32_t t, dt;               /* the raster's and the output's ec_dtype */
+    int32_t n_breaks, n_reached; /* 1 .. 255; 0 .. n_breaks */
+    uint32_t flags;              /* EC_RECLASS_HAS_NODATA: a nodata value was given (the masked form); EC_RECLASS_DROPS: a
+                                    validity byte is zero (a dst_mask is required) */
+    uint32_t reserved0;          /* 0 */
+    uint64_t nodata_bits;        /* the nodata cell's bytes in the low bytes, or 0 */
+    uint64_t reserved1;          /* 0 */
+    int64_t thr[255];            /* thr[0 .. n_reached): order keys of t */
+    uint64_t value_bits[256];    /* class c's cell of type dt in the low bytes, c <= n_breaks */
+    uint8_t valid[256];          /* class c's validity as 0 / 1 (all 1 without validity bytes) */
+} ec_reclass_table;
+enum { EC_RECLASS_TABLE_BYTES = 4384 };   /* sizeof(ec_reclass_table), a multiple of 16 */
+/* Host only, needs no device.  breaks_host: n_breaks cells of type bt; values: n_breaks + 1 ec_value of dtype dt;
+ * valid_or_null: n_breaks + 1 bytes; nodata_or_null: given iff the raster has a mask.  Refused in this order: n_breaks outside
+ * 1 .. EC_RECLASS_MAX_BREAKS; right outside {0, 1} (EC_ERR_ARG); a bad t, bt or dt (EC_ERR_UNSUPPORTED_TYPE); a null
+ * breaks_host, values or table_host_out; a value or the nodata whose dtype is not dt; a NaN break; breaks not strictly
+ * ascending in UT (all EC_ERR_ARG).  A refused build writes nothing to table_host_out. */
+ec_status ec_reclass_table_build(ec_dtype t, ec_dtype bt, const void *breaks_host, int32_t n_breaks, int32_t right,
+                                 ec_dtype dt, const ec_value *values /* n_breaks + 1, each of dtype dt */,
+                                 const uint8_t *valid_or_null /* n_breaks + 1 */, const ec_value *nodata_or_null,
+                                 void *table_host_out /* EC_RECLASS_TABLE_BYTES */);
+/* The rule above over n cells.  table_dev: the built record at a 16-byte-aligned DEVICE address — upload it once (ec_upload)
+ * and reuse it across launches, tiles and shards of that device (the table_dev convention of ec_zonal_broadcast).
+ * Asynchronous, no allocation, no synchronisation, capturable (after ec_prepare_stream for a foreign stream).  Writes exactly
+ * n cells of dst, and n mask bytes when dst_mask_or_null is given, at any cell offset of src, dst and the masks.  n == 0 is
+ * EC_OK and launches nothing.  Refused before any device work and without a device, in this order: a bad t or dt
+ * (EC_ERR_UNSUPPORTED_TYPE); with n > 0 a null src, table_dev or dst; a table_dev that is not 16-byte aligned; more than
+ * 2^31 - 1 tiles; dst or dst_mask overlapping an input, the table or each other (all EC_ERR_ARG; the operation is not in-place).
+ * The host cannot read a device record: that the record's t and dt are the call's, and that it was built with a nodata value
+ * iff mask_or_null is given, is the caller's to keep — the two calls must agree.  Whatever the record holds, the kernel clamps
+ * n_reached to 0 .. 255, reads nothing outside the record's EC_RECLASS_TABLE_BYTES and writes nothing outside dst[0 .. n) and
+ * dst_mask[0 .. n). */
+ec_status ec_reclass(ec_dtype t, const void *src, const uint8_t *mask_or_null, size_t n,
+                     ec_dtype dt, const void *table_dev, void *dst, uint8_t *dst_mask_or_null, ec_stream stream);
+/* ec_reclass on every shard of a group (element-wise: no collective, fire-and-forget).  One pointer per shard, as
+ * ec_sharded_cast; tables_dev[k] is the record on shard k's device.  masks_or_null / dst_masks_or_null == NULL: none on any
+ * shard.  The refusals come back on the calling thread before anything is posted. */
+ec_status ec_sharded_reclass(ec_shard_group *g, ec_dtype t, const void *const *src, const uint8_t *const *masks_or_null,
+                             const size_t *n, ec_dtype dt, const void *const *tables_dev, void *const *dst,
+                             uint8_t *const *dst_masks_or_null);
+
+/* ---------------------------------------------------------------- *
  * Test/bench support (not part of the reference surface).
  * ---------------------------------------------------------------- */
 /* x[i] = lo + splitmix64(seed ^ (base + i)) % (hi - lo + 1), t in {EC_U8, EC_U16, EC_F32}
