@@ -1,0 +1,3 @@
+// ec_composite_rank kernels for the cell types of 4 bytes (see ec_composite_rank_tu.hpp).
+#define EC_RANK_WIDTH 4
+#include "ec_composite_rank_tu.hpp"

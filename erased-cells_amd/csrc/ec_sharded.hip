@@ -661,6 +661,53 @@ extern "C" ec_status ec_sharded_composite(ec_shard_group* g, int32_t op, ec_dtyp
     });
 }
 
+extern "C" ec_status ec_sharded_composite_rank(ec_shard_group* g, ec_dtype t, const void* const* const* layers,
+                                               const uint8_t* const* const* masks_or_null, int32_t n_layers, const size_t* n, uint32_t num,
+                                               uint32_t den, int32_t method, uint32_t min_count, void* const* dst,
+                                               uint8_t* const* dst_mask_or_null, uint8_t* const* aux_or_null) {
+    const char* what = "ec_sharded_composite_rank";
+    ec_status st = check_group(g, what);
+    if (st != EC_OK) return st;
+    // the layer count, q, the method, min_count and the dtype, before any device work (n = 0: no pointer is looked at)
+    st = ec_composite_rank(t, nullptr, nullptr, n_layers, 0, num, den, method, min_count, nullptr, nullptr, nullptr, nullptr);
+    if (st != EC_OK) return st;
+    if (!layers || !dst || !n) return set_error(EC_ERR_ARG, "%s: null argument", what);
+    struct Call {
+        std::vector<const void*> p[64];
+        std::vector<const uint8_t*> m[64];
+        std::vector<void*> dst;
+        std::vector<uint8_t*> dm, aux;
+        std::vector<size_t> n;
+    };
+    auto c = std::make_shared<Call>();
+    bool masked = false;
+    for (int k = 0; k < n_layers; ++k) {
+        if (!layers[k]) return set_error(EC_ERR_ARG, "%s: layer %d is a null column", what, k);
+        masked = masked || (masks_or_null && masks_or_null[k]);
+    }
+    if (masked && !dst_mask_or_null) return set_error(EC_ERR_ARG, "%s: a layer has a mask, so the result needs dst_mask", what);
+    for (int k = 0; k < n_layers; ++k) {
+        c->p[k] = take(g, what, "layers[k]", layers[k], n, &st);
+        c->m[k] = take_optional(g, what, "masks[k]", masks_or_null ? masks_or_null[k] : nullptr, n, &st);
+    }
+    c->dst = take(g, what, "dst", dst, n, &st);
+    if (dst_mask_or_null) c->dm = take(g, what, "dst_mask", dst_mask_or_null, n, &st);
+    if (aux_or_null) c->aux = take(g, what, "aux", aux_or_null, n, &st);
+    if (st != EC_OK) return st;
+    c->n = copy_col(g, n);
+    std::lock_guard<std::mutex> lk(g->call_mu);
+    return post_each_shard(g, [g, c, t, n_layers, num, den, method, min_count](int i) -> ec_status {
+        const void* p[64];
+        const uint8_t* m[64];
+        for (int k = 0; k < n_layers; ++k) {
+            p[k] = c->p[k][i];
+            m[k] = c->m[k][i];
+        }
+        return ec_composite_rank(t, p, m, n_layers, c->n[i], num, den, method, min_count, c->dst[i], c->dm.empty() ? nullptr : c->dm[i],
+                                 c->aux.empty() ? nullptr : c->aux[i], g->streams[i]);
+    });
+}
+
 extern "C" ec_status ec_sharded_fused(ec_shard_group* g, ec_op o1, ec_op o2, ec_op o3, const ec_dtype dt[4], const void* const* const p[4],
                                       const uint8_t* const* const masks_or_null[4], const ec_value* scalars_or_null, const size_t* n,
                                       double* const* out, uint8_t* const* out_mask_or_null) {

@@ -1105,6 +1105,57 @@ inline MaskedCellBuffer composite(const std::vector<const MaskedCellBuffer*>& la
     return MaskedCellBuffer(std::move(out), std::move(om));
 }
 
+// ---------------------------------------------------------------- order statistics of a stack (ec_composite_rank)
+// The valid cells of every stack in the reference's total order, ties by layer index, and the one at position q * (count - 1) kept,
+// rounded down (EC_RANK_LOWER) or up (EC_RANK_UPPER); q = num / den is an exact fraction.  {1, 2} is the median, {0, 1} composite's MIN,
+// {1, 1} its MAX.  The result has the layers' cell type; `aux` as for composite().  The rule is in include/erased_cells.h.
+struct RankFraction {
+    uint32_t num = 1, den = 2;
+};
+namespace detail {
+inline void composite_rank_call(CellType ct, size_t n, const std::vector<const void*>& p, const std::vector<const uint8_t*>* m, RankFraction q,
+                                ec_rank_method method, uint32_t min_count, CellBuffer& out, Mask* om, CellBuffer* aux) {
+    if (q.den < 1 || q.den > EC_RANK_MAX_DEN || q.num > q.den) throw Error(EC_ERR_ARG, "composite_rank: q needs 1 <= den <= EC_RANK_MAX_DEN (65535) and num <= den");
+    if (method != EC_RANK_LOWER && method != EC_RANK_UPPER) throw Error(EC_ERR_ARG, "composite_rank: the method is EC_RANK_LOWER or EC_RANK_UPPER");
+    if (aux) *aux = CellBuffer(CellType::UInt8, n);
+    if (n == 0) return;  // an empty buffer has no memory to point at
+    check(ec_composite_rank(static_cast<ec_dtype>(ct), p.data(), m ? m->data() : nullptr, static_cast<int32_t>(p.size()), n, q.num, q.den, method, min_count,
+                            out.ptr(), om ? om->ptr() : nullptr, aux ? static_cast<uint8_t*>(aux->ptr()) : nullptr, current_stream()));
+}
+}  // namespace detail
+inline CellBuffer composite_rank(const std::vector<const CellBuffer*>& layers, RankFraction q = {}, ec_rank_method method = EC_RANK_LOWER,
+                                 CellBuffer* aux = nullptr) {
+    detail::composite_stack(layers);
+    const CellType ct = layers[0]->cell_type();
+    const size_t n = layers[0]->len();
+    CellBuffer out(ct, n);
+    std::vector<const void*> p;
+    for (const CellBuffer* l : layers) p.push_back(l->ptr());
+    detail::composite_rank_call(ct, n, p, nullptr, q, method, 1, out, nullptr, aux);
+    return out;
+}
+inline MaskedCellBuffer composite_rank(const std::vector<const MaskedCellBuffer*>& layers, RankFraction q = {}, ec_rank_method method = EC_RANK_LOWER,
+                                       uint32_t min_count = 1, CellBuffer* aux = nullptr) {
+    detail::composite_stack(layers);
+    const CellType ct = layers[0]->cell_type();
+    const size_t n = layers[0]->len();
+    CellBuffer out(ct, n);
+    Mask om(n);
+    std::vector<const void*> p;
+    std::vector<const uint8_t*> m;
+    for (const MaskedCellBuffer* l : layers) { p.push_back(l->buffer().ptr()); m.push_back(l->mask().ptr()); }
+    if (min_count < 1 || min_count > layers.size()) throw Error(EC_ERR_ARG, "composite_rank: min_count is not within 1 .. the number of layers");
+    detail::composite_rank_call(ct, n, p, &m, q, method, min_count, out, &om, aux);
+    return MaskedCellBuffer(std::move(out), std::move(om));
+}
+inline CellBuffer composite_median(const std::vector<const CellBuffer*>& layers, ec_rank_method method = EC_RANK_LOWER, CellBuffer* aux = nullptr) {
+    return composite_rank(layers, RankFraction{1, 2}, method, aux);
+}
+inline MaskedCellBuffer composite_median(const std::vector<const MaskedCellBuffer*>& layers, ec_rank_method method = EC_RANK_LOWER, uint32_t min_count = 1,
+                                         CellBuffer* aux = nullptr) {
+    return composite_rank(layers, RankFraction{1, 2}, method, min_count, aux);
+}
+
 // ---------------------------------------------------------------- fused operator chains
 // The reference evaluates `(&nir - &red) / (nir + red)` (src/gdal/rasterband.rs:148) eagerly, one pass and
 // one f64 temporary per operator.  `lazy(buf)` wraps a buffer so that the same operator syntax builds a
@@ -1567,6 +1618,35 @@ public:
         check(ec_sharded_composite(first.grp_->raw(), op, static_cast<ec_dtype>(first.ct_), pc.data(), masks.empty() ? nullptr : mc.data(),
                                    static_cast<int32_t>(layers.size()), first.lens_.data(), min_count, out.ptrs_.data(), out_mask ? om.data() : nullptr,
                                    aux ? ax.data() : nullptr));
+        return out;
+    }
+    // composite_rank of identically sharded layers on every shard (no communication): masks, out_mask and aux as for composite
+    static ShardedCellBuffer composite_rank(const std::vector<const ShardedCellBuffer*>& layers, RankFraction q = {}, ec_rank_method method = EC_RANK_LOWER,
+                                            uint32_t min_count = 1, const std::vector<const ShardedCellBuffer*>& masks = {},
+                                            std::optional<ShardedCellBuffer>* out_mask = nullptr, std::optional<ShardedCellBuffer>* aux = nullptr) {
+        if (layers.empty() || layers.size() > EC_COMPOSITE_MAX_LAYERS) throw Error(EC_ERR_ARG, "composite_rank: the stack holds 1 .. EC_COMPOSITE_MAX_LAYERS (64) layers");
+        if (!masks.empty() && masks.size() != layers.size()) throw Error(EC_ERR_ARG, "composite_rank: one mask entry per layer");
+        const ShardedCellBuffer& first = *layers[0];
+        std::vector<std::vector<const void*>> p(layers.size());
+        std::vector<std::vector<const uint8_t*>> m(layers.size());
+        std::vector<const void* const*> pc;
+        std::vector<const uint8_t* const*> mc;
+        for (size_t k = 0; k < layers.size(); ++k) {
+            if (layers[k]->ct_ != first.ct_ || layers[k]->lens_ != first.lens_) throw Error(EC_ERR_LENGTH, "composite_rank: layers must share a cell type and a sharding");
+            p[k].assign(layers[k]->ptrs_.begin(), layers[k]->ptrs_.end());
+            pc.push_back(p[k].data());
+            const ShardedCellBuffer* mk = masks.empty() ? nullptr : masks[k];
+            if (mk && (mk->ct_ != CellType::UInt8 || mk->lens_ != first.lens_)) throw Error(EC_ERR_LENGTH, "composite_rank: a mask must be UInt8 and sharded like its layer");
+            if (mk) for (void* r : mk->ptrs_) m[k].push_back(static_cast<const uint8_t*>(r));
+            mc.push_back(mk ? m[k].data() : nullptr);
+        }
+        ShardedCellBuffer out(*first.grp_, first.ct_, first.lens_);
+        std::vector<uint8_t*> om, ax;
+        if (out_mask) { out_mask->emplace(ShardedCellBuffer(*first.grp_, CellType::UInt8, first.lens_)); for (void* r : (*out_mask)->ptrs_) om.push_back(static_cast<uint8_t*>(r)); }
+        if (aux) { aux->emplace(ShardedCellBuffer(*first.grp_, CellType::UInt8, first.lens_)); for (void* r : (*aux)->ptrs_) ax.push_back(static_cast<uint8_t*>(r)); }
+        check(ec_sharded_composite_rank(first.grp_->raw(), static_cast<ec_dtype>(first.ct_), pc.data(), masks.empty() ? nullptr : mc.data(),
+                                        static_cast<int32_t>(layers.size()), first.lens_.data(), q.num, q.den, method, min_count, out.ptrs_.data(),
+                                        out_mask ? om.data() : nullptr, aux ? ax.data() : nullptr));
         return out;
     }
     // BufferOps::min_max of the whole raster (buffer.rs:169-173): per-shard keys, one all-reduce(MAX), decode

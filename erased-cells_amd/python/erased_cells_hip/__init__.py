@@ -11,10 +11,10 @@
 """
 from . import _ffi, fused, raster, wire
 from ._ffi import EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES, EC_ZONAL_MAX_ZONES, EcError, NarrowingError, build, lib, tuned
-from .buffer import (ADD, CAST_MODES, CELL_TYPES, COMPOSITE_OPS, CT_NAMES, DIV, FOCAL_OPS, MUL, NP_DTYPES, SUB, CellBuffer, CellValue, DeviceMem,
+from .buffer import (ADD, CAST_MODES, CELL_TYPES, COMPOSITE_OPS, CT_NAMES, DIV, FOCAL_OPS, MUL, NP_DTYPES, RANK_METHODS, SUB, CellBuffer, CellValue, DeviceMem,
                      Float32, Float64, Int8, Int16, Int32, Int64, Mask, MaskedCellBuffer, NoData, ReclassTable, Stats, UInt8,
                      UInt16, UInt32, UInt64, ParseError, can_fit_into, cell_type_from_str, cell_type_of,
-                     cell_type_to_string, composite, init, is_integral, is_signed, mask_from_nodata, max_value, min_value, one,
+                     cell_type_to_string, composite, composite_median, composite_rank, init, is_integral, is_signed, mask_from_nodata, max_value, min_value, one,
                      select, set_stream, size_of, stream, synchronize, union, zero)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -27,6 +27,8 @@ EC_FOCAL_RADIUS_CAP = 7
 EC_FOCAL_WHOLE, EC_FOCAL_NORMALIZE = 1, 2  # flags of ec_focal / ec_focal_convolve
 EC_COMPOSITE_FIRST, EC_COMPOSITE_LAST, EC_COMPOSITE_MIN, EC_COMPOSITE_MAX, EC_COMPOSITE_SUM, EC_COMPOSITE_MEAN = range(6)  # ec_composite_op
 EC_COMPOSITE_MAX_LAYERS, EC_COMPOSITE_NONE = 64, 255
+EC_RANK_LOWER, EC_RANK_UPPER = range(2)  # ec_rank_method
+EC_RANK_MAX_DEN = 65535
 EC_ZONAL_MAX_ZONES = 256
 EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES = 255, 4384
 EC_RECLASS_HAS_NODATA, EC_RECLASS_DROPS = 1, 2  # ec_reclass_table.flags
@@ -215,6 +217,8 @@ SIGNATURES = {
     "ec_composite_result_type": (C.c_uint8, [I32, C.c_uint8]),
     "ec_composite": (I32, [I32, C.c_uint8, PVP, PVP, I32, SZ, C.c_uint32, VP, U8P, U8P, VP]),
     "ec_sharded_composite": (I32, [VP, I32, C.c_uint8, C.POINTER(PVP), C.POINTER(PVP), I32, PSZ, C.c_uint32, PVP, PVP, PVP]),
+    "ec_composite_rank": (I32, [C.c_uint8, PVP, PVP, I32, SZ, C.c_uint32, C.c_uint32, I32, C.c_uint32, VP, U8P, U8P, VP]),
+    "ec_sharded_composite_rank": (I32, [VP, C.c_uint8, C.POINTER(PVP), C.POINTER(PVP), I32, PSZ, C.c_uint32, C.c_uint32, I32, C.c_uint32, PVP, PVP, PVP]),
     "ec_synth_fill": (I32, [C.c_uint8, VP, SZ, C.c_uint64, C.c_uint64, C.c_double, C.c_double, VP]),
     "ec_synth_mask": (I32, [U8P, SZ, C.c_uint64, C.c_uint64, C.c_uint32, VP]),
     "ec_tune_set": (I32, [C.c_char_p, C.c_int64]),

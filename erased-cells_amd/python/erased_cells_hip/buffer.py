@@ -20,7 +20,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_COMPOSITE_MAX_LAYERS, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_ZONAL_MAX_ZONES, EC_RECLASS_DROPS, EC_RECLASS_HAS_NODATA, EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES, EC_RESAMPLE_BILINEAR, EcError, EcReclassTable, EcStats, EcValue, check, lib
+from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_COMPOSITE_MAX_LAYERS, EC_RANK_LOWER, EC_RANK_MAX_DEN, EC_RANK_UPPER, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_ZONAL_MAX_ZONES, EC_RECLASS_DROPS, EC_RECLASS_HAS_NODATA, EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES, EC_RESAMPLE_BILINEAR, EcError, EcReclassTable, EcStats, EcValue, check, lib
 
 # CellType (src/ctype.rs:11-20; order of with_ct!, src/lib.rs:89-98)
 UInt8, UInt16, UInt32, UInt64, Int8, Int16, Int32, Int64, Float32, Float64 = range(10)
@@ -1410,3 +1410,51 @@ def composite(layers, op="first", min_count: int = 1, aux: bool = False):
                                  ax.mem.ptr if aux else None, _stream))
     res = MaskedCellBuffer(out, om) if masked else out
     return (res, ax) if aux else res
+
+
+# the spellings of an ec_rank_method
+RANK_METHODS = {"lower": EC_RANK_LOWER, "upper": EC_RANK_UPPER}
+
+
+def _rank_args(q, method):
+    """(num, den, ec_rank_method) of `q`, a pair of integers (num, den) with 0 <= num <= den and 1 <= den <= EC_RANK_MAX_DEN, or 0 or 1,
+    and of "lower" / "upper" or an ec_rank_method value; anything else is refused.  A float is no exact rational: it is refused."""
+    if isinstance(q, (int, np.integer)) and not isinstance(q, bool) and int(q) in (0, 1):
+        q = (int(q), 1)
+    ok = isinstance(q, (tuple, list)) and len(q) == 2 and all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in q)
+    if not ok or not (1 <= int(q[1]) <= EC_RANK_MAX_DEN and 0 <= int(q[0]) <= int(q[1])):
+        raise EcError(EC_ERR_ARG, f"composite_rank: q {q!r} is not a pair of integers (num, den) with 0 <= num <= den and "
+                                  f"1 <= den <= EC_RANK_MAX_DEN ({EC_RANK_MAX_DEN})")
+    m = RANK_METHODS.get(method, method) if isinstance(method, str) else method
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) not in (EC_RANK_LOWER, EC_RANK_UPPER):
+        raise EcError(EC_ERR_ARG, f"composite_rank: method {method!r} is not one of {sorted(RANK_METHODS)} or an ec_rank_method value 0..1")
+    return int(q[0]), int(q[1]), int(m)
+
+
+def composite_rank(layers, q=(1, 2), method="lower", min_count: int = 1, aux: bool = False):
+    """The per-cell order statistic of a stack of co-registered `layers` (the same kinds as `composite` takes) in one pass
+    (ec_composite_rank; the rule is in include/erased_cells.h): the valid cells of each stack in the reference's total order, ties by
+    layer index, and the one at position q * (count - 1) kept — rounded down ("lower") or up ("upper"), q = (num, den) an exact
+    fraction.  (1, 2) is the median, (0, 1) the minimum, (1, 1) the maximum.  The result has the layers' cell type; a cell is valid
+    when at least `min_count` layers are.  A CellBuffer when no layer is masked, otherwise a MaskedCellBuffer; with `aux` a pair
+    (result, UInt8 CellBuffer): the layer each cell came from (255: none)."""
+    num, den, m = _rank_args(q, method)
+    pairs, ct, n = _composite_stack(layers, min_count)
+    masked = any(mk is not None for _, mk in pairs)
+    out = CellBuffer.empty(n, ct)
+    om = Mask.empty(n) if masked else None
+    ax = CellBuffer.empty(n, UInt8) if aux else None
+    if n:  # an empty buffer has no memory to point at
+        k = len(pairs)
+        lp = (C.c_void_p * k)(*[b.mem.ptr for b, _ in pairs])
+        mp = (C.c_void_p * k)(*[mk.mem.ptr if mk is not None else None for _, mk in pairs])
+        check(lib().ec_composite_rank(ct, lp, mp if masked else None, k, n, num, den, m, int(min_count), out.mem.ptr,
+                                      om.mem.ptr if masked else None, ax.mem.ptr if aux else None, _stream))
+    res = MaskedCellBuffer(out, om) if masked else out
+    return (res, ax) if aux else res
+
+
+def composite_median(layers, method="lower", min_count: int = 1, aux: bool = False):
+    """`composite_rank` at q = 1/2: the lower ("lower") or upper ("upper") median of the valid cells of each stack; they agree where the
+    count is odd."""
+    return composite_rank(layers, (1, 2), method, min_count, aux)

@@ -297,6 +297,38 @@ class ShardGroup:
         res = res + (ax,) if aux else res
         return res[0] if len(res) == 1 else res
 
+    def composite_rank(self, layers, q=(1, 2), method="lower", min_count: int = 1, aux: bool = False, masks=None):
+        """`composite_rank` on every shard, fire-and-forget: the per-cell order statistic (q = (num, den); (1, 2) the median) of up to 64
+        identically sharded buffers of one cell type, `masks` (optional) one sharded mask or None per layer.  Returns what `composite`
+        returns: the sharded result, `(result, mask)` when a layer has a mask, and with `aux` the sharded UInt8 aux buffer last."""
+        from ._ffi import EC_COMPOSITE_MAX_LAYERS, EC_ERR_ARG, EcError, PVP
+        (num, den, mth), layers = B._rank_args(q, method), list(layers)
+        k = len(layers)
+        if not 1 <= k <= EC_COMPOSITE_MAX_LAYERS:
+            raise EcError(EC_ERR_ARG, f"composite_rank: {k} layers, not within 1 .. EC_COMPOSITE_MAX_LAYERS ({EC_COMPOSITE_MAX_LAYERS})")
+        masks = list(masks) if masks is not None else [None] * k
+        if len(masks) != k:
+            raise EcError(EC_ERR_ARG, f"composite_rank: {len(masks)} masks for {k} layers")
+        ct, lens = layers[0].ct, layers[0].lens
+        for i, b in enumerate(layers):
+            if b.ct != ct:
+                raise EcError(EC_ERR_ARG, f"composite_rank: layer {i} is {B.CT_NAMES[b.ct]}, layer 0 {B.CT_NAMES[ct]}: cast the stack to one cell type first")
+            if b.lens != lens or (masks[i] is not None and masks[i].lens != lens):
+                raise EcError(EC_ERR_ARG, f"composite_rank: layer {i} or its mask is not sharded like layer 0")
+        if isinstance(min_count, bool) or not isinstance(min_count, int) or not 1 <= min_count <= k:
+            raise EcError(EC_ERR_ARG, f"composite_rank: min_count {min_count!r} is not within 1 .. {k}, the number of layers")
+        masked = any(m is not None for m in masks)
+        out = self.alloc(ct, lens)
+        om = self.alloc(B.UInt8, lens) if masked else None
+        ax = self.alloc(B.UInt8, lens) if aux else None
+        p = (PVP * k)(*[C.cast(b.ptrs, PVP) for b in layers])
+        m = (PVP * k)(*[C.cast(b.ptrs, PVP) if b is not None else PVP() for b in masks]) if masked else None
+        check(lib().ec_sharded_composite_rank(self.handle, ct, p, m, k, (C.c_size_t * self.n)(*lens), num, den, mth, min_count, out.ptrs,
+                                              om.ptrs if masked else None, ax.ptrs if aux else None))
+        res = (out, om) if masked else (out,)
+        res = res + (ax,) if aux else res
+        return res[0] if len(res) == 1 else res
+
     def program(self, streams, scalars, steps, masks=None):
         """An expression program (`fused.program`: steps `(op, a, b, dst)`) on every shard, fire-and-forget: `streams` up to four
         identically sharded buffers, `masks` (optional) one sharded mask per stream.  Returns the f64 result, or

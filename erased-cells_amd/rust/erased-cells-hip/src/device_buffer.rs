@@ -692,6 +692,72 @@ impl CellBuffer {
     }
 }
 
+/// Which neighbour [`CellBuffer::composite_rank`] keeps when `q * (count - 1)` is no whole position (`ec_rank_method`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum RankMethod {
+    /// The position rounded down: `numpy.quantile`'s "lower".
+    Lower = EC_RANK_LOWER,
+    /// The position rounded up: "higher".
+    Upper = EC_RANK_UPPER,
+}
+
+/// The exact fraction `num / den` of [`CellBuffer::composite_rank`]: `(1, 2)` the median, `(0, 1)` the minimum, `(1, 1)` the maximum.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct RankFraction {
+    pub num: u32,
+    pub den: u32,
+}
+
+impl RankFraction {
+    pub const MEDIAN: RankFraction = RankFraction { num: 1, den: 2 };
+}
+
+impl CellBuffer {
+    /// `ec_composite_rank` over `layers` with their mask pointers, as [`CellBuffer::composite_raw`] takes them.
+    pub(crate) fn composite_rank_raw(layers: &[&CellBuffer], masks: &[*const u8], q: RankFraction, method: RankMethod, min_count: u32, out_mask: *mut u8,
+                                     aux: bool) -> Result<(Self, Option<Self>)> {
+        assert!(!layers.is_empty() && layers.len() <= EC_COMPOSITE_MAX_LAYERS, "a stack holds 1 .. {EC_COMPOSITE_MAX_LAYERS} layers, not {}", layers.len());
+        assert!(masks.is_empty() || masks.len() == layers.len(), "one mask entry per layer");
+        assert!(q.den >= 1 && q.den <= EC_RANK_MAX_DEN && q.num <= q.den, "q = {} / {} needs 1 <= den <= {EC_RANK_MAX_DEN} and num <= den", q.num, q.den);
+        let (ct, len) = (layers[0].ct, layers[0].len);
+        for l in layers {
+            assert_eq!(l.ct, ct, "the layers of a stack share one cell type: cast first");
+            assert_eq!(l.len, len, "the layers of a stack share one length");
+        }
+        let out = Self::uninit(ct, len);
+        let source = if aux { Some(Self::uninit(CellType::UInt8, len)) } else { None };
+        if len != 0 {
+            let cells: Vec<*const c_void> = layers.iter().map(|l| l.dev_ptr()).collect();
+            let masks_ptr = if masks.is_empty() { std::ptr::null() } else { masks.as_ptr() };
+            let aux_ptr = source.as_ref().map_or(std::ptr::null_mut(), |a| a.mem.ptr() as *mut u8);
+            check(unsafe {
+                ec_composite_rank(ct as u8, cells.as_ptr(), masks_ptr, layers.len() as i32, len, q.num, q.den, method as i32, min_count, out.mem.ptr(),
+                                  out_mask, aux_ptr, stream())
+            })?;
+        }
+        Ok((out, source))
+    }
+
+    /// The per-cell order statistic of a stack of co-registered layers of one cell type and length, in one pass: the cells of each
+    /// stack in the total order of `min_max`, ties by layer index, and the one at position `q * (layers - 1)` kept; the rule is at
+    /// `ec_composite_rank` in include/erased_cells.h.  Every cell is valid here: see `MaskedCellBuffer::composite_rank` for clouds.
+    pub fn composite_rank(layers: &[&CellBuffer], q: RankFraction, method: RankMethod) -> Result<Self> {
+        Ok(Self::composite_rank_raw(layers, &[], q, method, 1, std::ptr::null_mut(), false)?.0)
+    }
+
+    /// [`CellBuffer::composite_rank`] at one half: the lower or the upper median.
+    pub fn composite_median(layers: &[&CellBuffer], method: RankMethod) -> Result<Self> {
+        Self::composite_rank(layers, RankFraction::MEDIAN, method)
+    }
+
+    /// [`CellBuffer::composite_rank`] and, as `UInt8` cells, the index of the layer each cell came from.
+    pub fn composite_rank_with_source(layers: &[&CellBuffer], q: RankFraction, method: RankMethod) -> Result<(Self, Self)> {
+        let (out, source) = Self::composite_rank_raw(layers, &[], q, method, 1, std::ptr::null_mut(), true)?;
+        Ok((out, source.expect("asked for")))
+    }
+}
+
 // api-surface(src/buffer.rs:318-436): the sixteen binary-operator impl headers, the two `Neg` impls and the ordering /
 // equality impl headers of CellBuffer (`&a op &b`, `a op b`, `a op &b`, `a op scalar`; no `scalar op a` in the reference either)
 macro_rules! buffer_operator {

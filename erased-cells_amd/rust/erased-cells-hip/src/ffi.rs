@@ -77,6 +77,10 @@ pub const EC_COMPOSITE_MEAN: i32 = 5;
 /// The tallest stack of one call, and the aux byte of a cell that no layer gave.
 pub const EC_COMPOSITE_MAX_LAYERS: usize = 64;
 pub const EC_COMPOSITE_NONE: u8 = 255;
+/// `ec_rank_method`: which neighbour `ec_composite_rank` keeps (it takes it as an `i32`).
+pub const EC_RANK_LOWER: i32 = 0;
+pub const EC_RANK_UPPER: i32 = 1;
+pub const EC_RANK_MAX_DEN: u32 = 65535;
 
 /// Mirrors `ec_value`: tag + 8-byte payload, 16 bytes.
 #[repr(C)]
@@ -367,6 +371,13 @@ extern "C" {
     pub fn ec_sharded_composite(g: *mut ec_shard_group, op: i32, t: ec_dtype, layers: *const *const *const c_void,
                                 masks_or_null: *const *const *const u8, n_layers: i32, n: *const usize, min_count: u32,
                                 dst: *const *mut c_void, dst_mask_or_null: *const *mut u8, aux_or_null: *const *mut u8) -> ec_status;
+    pub fn ec_composite_rank(t: ec_dtype, layers: *const *const c_void, masks_or_null: *const *const u8, n_layers: i32, n: usize,
+                             num: u32, den: u32, method: i32, min_count: u32, dst: *mut c_void, dst_mask_or_null: *mut u8,
+                             aux_or_null: *mut u8, s: ec_stream) -> ec_status;
+    pub fn ec_sharded_composite_rank(g: *mut ec_shard_group, t: ec_dtype, layers: *const *const *const c_void,
+                                     masks_or_null: *const *const *const u8, n_layers: i32, n: *const usize, num: u32, den: u32,
+                                     method: i32, min_count: u32, dst: *const *mut c_void, dst_mask_or_null: *const *mut u8,
+                                     aux_or_null: *const *mut u8) -> ec_status;
     pub fn ec_window_put(t: ec_dtype, tile: *const c_void, tile_mask_or_null: *const u8, win_cols: u64, win_rows: u64,
                          dst: *mut c_void, dst_mask_or_null: *mut u8, dst_cols: u64, dst_rows: u64, x0: u64, y0: u64,
                          s: ec_stream) -> ec_status;

@@ -11,7 +11,7 @@
 use crate::device::stream;
 use crate::error::{check, must, Result};
 use crate::ffi::*;
-use crate::{BufferOps, CastMode, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Cmp, CompositeOp, FocalOp, Mask, NoData, ResampleAlg, Stats};
+use crate::{BufferOps, CastMode, CellBuffer, CellBufferIterator, CellEncoding, CellType, CellValue, Cmp, CompositeOp, FocalOp, Mask, NoData, RankFraction, RankMethod, ResampleAlg, Stats};
 use std::fmt::{Debug, Formatter};
 use std::ops::{Add, Div, Mul, Neg, Sub};
 
@@ -440,6 +440,23 @@ impl MaskedCellBuffer {
         let masks: Vec<*const u8> = layers.iter().map(|l| l.1.dev_ptr()).collect();
         let mask = Mask::uninit(cells.first().map_or(0, |c| c.len()));
         let (out, source) = CellBuffer::composite_raw(&cells, &masks, op, min_count, mask.dev_ptr_mut(), true)?;
+        Ok((MaskedCellBuffer(out, mask), source.expect("asked for")))
+    }
+
+    /// [`CellBuffer::composite_rank`] over the cells whose mask byte is set: the median (or another quantile) of the clear
+    /// observations.  A cell of the result is valid when at least `min_count` layers are valid there; an invalid one is zero.
+    pub fn composite_rank(layers: &[&MaskedCellBuffer], q: RankFraction, method: RankMethod, min_count: u32) -> Result<Self> {
+        Ok(Self::composite_rank_with_source(layers, q, method, min_count)?.0)
+    }
+
+    /// [`MaskedCellBuffer::composite_rank`] and, as `UInt8` cells, the index of the layer each cell came from — `EC_COMPOSITE_NONE`
+    /// for an invalid cell.
+    pub fn composite_rank_with_source(layers: &[&MaskedCellBuffer], q: RankFraction, method: RankMethod, min_count: u32) -> Result<(Self, CellBuffer)> {
+        assert!(min_count >= 1 && min_count as usize <= layers.len(), "min_count {min_count} is not within 1 .. {}", layers.len());
+        let cells: Vec<&CellBuffer> = layers.iter().map(|l| &l.0).collect();
+        let masks: Vec<*const u8> = layers.iter().map(|l| l.1.dev_ptr()).collect();
+        let mask = Mask::uninit(cells.first().map_or(0, |c| c.len()));
+        let (out, source) = CellBuffer::composite_rank_raw(&cells, &masks, q, method, min_count, mask.dev_ptr_mut(), true)?;
         Ok((MaskedCellBuffer(out, mask), source.expect("asked for")))
     }
 }

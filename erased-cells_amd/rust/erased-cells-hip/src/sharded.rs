@@ -13,7 +13,7 @@
 use crate::device::stream;
 use crate::error::{check, must, Result};
 use crate::ffi::*;
-use crate::{BufferOps, CastMode, CellBuffer, CellEncoding, CellType, CellValue, Cmp, CompositeOp, Stats};
+use crate::{BufferOps, CastMode, CellBuffer, CellEncoding, CellType, CellValue, Cmp, CompositeOp, RankFraction, RankMethod, Stats};
 #[cfg(feature = "masked")]
 use crate::Mask;
 use std::os::raw::c_void;
@@ -276,6 +276,33 @@ impl ShardedCellBuffer<'_> {
             ec_sharded_composite(first.group.g, op as i32, first.ct as u8, cells.as_ptr(), if masked { mask_ptrs.as_ptr() } else { ptr::null() },
                                  layers.len() as i32, first.lens.as_ptr(), min_count, out.ptrs.as_ptr(),
                                  mask_out.as_ref().map_or(ptr::null(), |v| v.as_ptr()), source_out.as_ptr())
+        })?;
+        Ok((out, out_mask, source))
+    }
+
+    /// [`CellBuffer::composite_rank`] of identically sharded layers on every shard (no communication); `masks` and the three results as
+    /// for [`ShardedCellBuffer::composite`].
+    pub fn composite_rank(layers: &[&Self], masks: &[Option<&Self>], q: RankFraction, method: RankMethod, min_count: u32) -> Result<(Self, Option<Self>, Self)> {
+        assert!(!layers.is_empty() && layers.len() <= EC_COMPOSITE_MAX_LAYERS, "a stack holds 1 .. {EC_COMPOSITE_MAX_LAYERS} layers, not {}", layers.len());
+        assert!(masks.is_empty() || masks.len() == layers.len(), "one mask entry per layer");
+        let first = layers[0];
+        for l in layers {
+            assert!(l.ct == first.ct && l.lens == first.lens, "the layers of a stack share a cell type and a sharding");
+        }
+        let cell_cols: Vec<Vec<*const c_void>> = layers.iter().map(|l| l.const_ptrs()).collect();
+        let cells: Vec<*const *const c_void> = cell_cols.iter().map(|c| c.as_ptr()).collect();
+        let mask_cols: Vec<Option<Vec<*const u8>>> = masks.iter().map(|m| m.map(|b| b.ptrs.iter().map(|p| *p as *const u8).collect())).collect();
+        let mask_ptrs: Vec<*const *const u8> = mask_cols.iter().map(|c| c.as_ref().map_or(ptr::null(), |v| v.as_ptr())).collect();
+        let masked = masks.iter().any(|m| m.is_some());
+        let out = first.alloc_like(first.ct)?;
+        let out_mask = if masked { Some(first.alloc_like(CellType::UInt8)?) } else { None };
+        let source = first.alloc_like(CellType::UInt8)?;
+        let bytes = |b: &Self| -> Vec<*mut u8> { b.ptrs.iter().map(|p| *p as *mut u8).collect() };
+        let (mask_out, source_out) = (out_mask.as_ref().map(bytes), bytes(&source));
+        check(unsafe {
+            ec_sharded_composite_rank(first.group.g, first.ct as u8, cells.as_ptr(), if masked { mask_ptrs.as_ptr() } else { ptr::null() },
+                                      layers.len() as i32, first.lens.as_ptr(), q.num, q.den, method as i32, min_count, out.ptrs.as_ptr(),
+                                      mask_out.as_ref().map_or(ptr::null(), |v| v.as_ptr()), source_out.as_ptr())
         })?;
         Ok((out, out_mask, source))
     }

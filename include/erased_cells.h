@@ -709,6 +709,44 @@ ec_status ec_sharded_composite(ec_shard_group *g, int32_t op /* an ec_composite_
                                int32_t n_layers, const size_t *n, uint32_t min_count, void *const *dst,
                                uint8_t *const *dst_mask_or_null, uint8_t *const *aux_or_null);
 
+/* Order statistics of a stack: the median composite and the other quantiles.  ec_composite's MIN and MAX are the two ends of a
+ * cell's stack; this is any position between them — the per-cell middle observation of the clear dates survives one unmasked
+ * cloud or shadow, where MAX keeps the cloud and MEAN smears it.  The reference has no counterpart (see above).
+ * ec_rank_method crosses the ABI as an int32_t, like ec_composite_op. */
+typedef enum { EC_RANK_LOWER = 0, EC_RANK_UPPER = 1 } ec_rank_method;
+enum { EC_RANK_MAX_DEN = 65535 };
+/* layers, masks_or_null, VALID, count, min_count, dst_mask_or_null, aux_or_null and EC_COMPOSITE_NONE mean exactly what they
+ * mean for ec_composite; so do n == 0, no allocation, asynchronous, capturable after ec_prepare_stream.  dst holds n cells of
+ * type t.  At most EC_COMPOSITE_MAX_LAYERS layers.
+ * The rule, so every cell has one right answer.  At cell i let c be the number of valid layers.  Order the valid layers
+ * ascending by the pair (order_key(cell), k): the reference's total order (src/value.rs:248-265, as ec_min_max uses it), and
+ * among cells of equal key the lesser layer index first.  The pairs are distinct, so the order is total.  The position kept
+ * for q = num / den, 0 <= num <= den, 1 <= den <= EC_RANK_MAX_DEN, counting from 0, is
+ *   EC_RANK_LOWER   r = (num * (c - 1)) / den
+ *   EC_RANK_UPPER   r = (num * (c - 1) + den - 1) / den
+ * in integer arithmetic (everything fits 32 bits): numpy.quantile's "lower" / "higher" with an exact rational q.
+ * The cell stores the bits of the layer at position r, mask byte 1 and aux = that layer's k iff c >= min_count; otherwise
+ * all-zero bits, mask byte 0 and aux = EC_COMPOSITE_NONE.  A layer that is not valid contributes nothing, whatever its cell
+ * holds.
+ *   1/2 LOWER is the lower median, 1/2 UPPER the upper one; they agree when c is odd.
+ *   num = 0 gives the bits and the aux of ec_composite MIN.
+ *   num = den gives the bits of ec_composite MAX; its aux is the GREATEST k among cells of equal key, where MAX reports the
+ *   least.
+ * A mean of the two middles is not built: (lower + upper) / 2 through the operators is the composition.
+ * Refusals, before any device work and in this order: n_layers outside 1 .. EC_COMPOSITE_MAX_LAYERS; den outside
+ * 1 .. EC_RANK_MAX_DEN or num > den; a method that is none; min_count outside 1 .. n_layers (all EC_ERR_ARG); a bad dtype
+ * (EC_ERR_UNSUPPORTED_TYPE); then, for n > 0, ec_composite's pointer, tile-count and aliasing refusals in its order.  A
+ * refused call writes nothing. */
+ec_status ec_composite_rank(ec_dtype t, const void *const *layers, const uint8_t *const *masks_or_null, int32_t n_layers,
+                            size_t n, uint32_t num, uint32_t den, int32_t method /* an ec_rank_method */, uint32_t min_count,
+                            void *dst, uint8_t *dst_mask_or_null, uint8_t *aux_or_null, ec_stream stream);
+/* ec_composite_rank on every shard of a group, columns as for ec_sharded_composite.  The whole-call refusals of
+ * ec_composite_rank come first and post nothing. */
+ec_status ec_sharded_composite_rank(ec_shard_group *g, ec_dtype t, const void *const *const *layers,
+                                    const uint8_t *const *const *masks_or_null, int32_t n_layers, const size_t *n,
+                                    uint32_t num, uint32_t den, int32_t method, uint32_t min_count, void *const *dst,
+                                    uint8_t *const *dst_mask_or_null, uint8_t *const *aux_or_null);
+
 /* ---------------------------------------------------------------- *
  * Band statistics: count, min, max, sum, mean and population standard deviation in one pass over a resident buffer.
  * The reference has BufferOps::min_max only (src/buffer.rs:169-173; masked: src/masked/masked_buffer.rs:208-217); its own
