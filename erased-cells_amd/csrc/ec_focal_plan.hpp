@@ -1,6 +1,7 @@
 // ec_focal_plan.hpp — the arithmetic that the host side and the kernels of ec_focal / ec_focal_convolve (include/erased_cells.h) share:
 // the refusals, the tile grid, the part of the raster a workgroup stages (its output tile and the halo, clipped at the raster's edges)
-// and the LDS layout of that stage.
+// and the LDS layout of that stage — and, for ec_focal_rank / ec_focal_majority, which stage the same way, their refusals (rank_refusal) and their
+// layout (rank_layout_of) at the end of the file.
 //
 // Self-contained: no HIP include; under a plain C++ compiler the function attributes are defined away (as ec_order_key.hpp does), so
 // host/test_focal_plan.cpp runs these very functions under the address and undefined-behaviour sanitizers.
@@ -105,6 +106,54 @@ inline const char* refusal(bool convolve, int32_t op, const void* src, const voi
     if (g->tiles_y > kMaxTiles / g->tiles_x) return "more than 2^31 - 1 tiles";  // tiles_x >= 1; no overflow: the product is never formed
     g->tiles = g->tiles_x * g->tiles_y;
     return nullptr;
+}
+
+// ---- ec_focal_rank / ec_focal_majority: the order statistics of a footprint (ec_focal_rank_kernels.hpp)
+constexpr uint32_t kRankMaxTaps = 64;   // EC_FOCAL_RANK_MAX_TAPS
+constexpr uint32_t kRankMaxDen = 65535; // EC_RANK_MAX_DEN
+
+// Why a call of ec_focal_rank (`rank`) or ec_focal_majority is refused, or null: refusal's checks in refusal's order, the tap count
+// directly behind the radius cap, and for ec_focal_rank the fraction and the method at the end.  EC_FOCAL_WHOLE is the only flag.
+inline const char* rank_refusal(bool rank, const void* src, const void* dst, const void* src_mask, const void* dst_mask, uint64_t cols,
+                                uint64_t rows, uint32_t rx, uint32_t ry, uint32_t num, uint32_t den, int32_t method, uint32_t flags,
+                                uint32_t tw, uint32_t th, Grid* g) {
+    g->tiles_x = g->tiles_y = g->tiles = 0;
+    if (!src || !dst) return "null pointer";
+    if (flags & ~kFlagWhole) return "unknown flag bits";
+    if (rx > kRadiusCap || ry > kRadiusCap) return "a radius above EC_FOCAL_RADIUS_CAP (7)";
+    if ((2 * rx + 1) * (2 * ry + 1) > kRankMaxTaps) return "more than EC_FOCAL_RANK_MAX_TAPS (64) taps in the footprint";
+    if (!dst_mask && (src_mask || (flags & kFlagWhole))) return "dst_mask is NULL where cells can be invalid (a source mask, or EC_FOCAL_WHOLE)";
+    if (cols != 0 && rows > UINT64_MAX / cols) return "cols * rows overflows 64 bits";
+    if (dst == src) return "dst == src: the operation is not in-place";
+    if (dst_mask && dst_mask == src_mask) return "dst_mask == src_mask: the operation is not in-place";
+    if (cols != 0 && rows != 0) {
+        g->tiles_x = ceil_div(cols, tw);
+        g->tiles_y = ceil_div(rows, th);
+        if (g->tiles_y > kMaxTiles / g->tiles_x) return "more than 2^31 - 1 tiles";
+        g->tiles = g->tiles_x * g->tiles_y;
+    }
+    if (rank) {
+        if (den < 1 || den > kRankMaxDen || num > den) {
+            g->tiles = 0;
+            return "q = num / den needs 1 <= den <= EC_RANK_MAX_DEN (65535) and num <= den";
+        }
+        if (method != 0 && method != 1) {
+            g->tiles = 0;
+            return "the method is not an ec_rank_method (0 .. 1)";
+        }
+    }
+    return nullptr;
+}
+
+// The stage of layout_of(kConvolve) — cells and mask bytes, no row results — and behind it the tile's results on their way from the
+// lane that sorted a cell to the lane that stores its 16-byte slot: th rows of tw results of `cell` bytes (off_racc) and th rows
+// of tw validity bytes (off_rcnt).
+EC_FOCAL_HD Layout rank_layout_of(uint32_t cell, bool masked, uint32_t rx, uint32_t ry, uint32_t tw, uint32_t th) {
+    Layout l = layout_of(cell, masked, kConvolve, rx, ry, tw, th);
+    l.off_racc = l.bytes;
+    l.off_rcnt = l.off_racc + th * tw * cell;
+    l.bytes = l.off_rcnt + round16(th * tw);
+    return l;
 }
 
 }  // namespace ecf

@@ -1,0 +1,3 @@
+// ec_focal_rank / ec_focal_majority kernels for the cell types of 4 bytes (see ec_focal_rank_tu.hpp).
+#define EC_FOCAL_RANK_WIDTH 4
+#include "ec_focal_rank_tu.hpp"

@@ -338,6 +338,18 @@ struct Stats {
 class Mask;
 class MaskedCellBuffer;
 
+namespace detail {
+// ec_focal_rank, or ec_focal_majority when `q` is null, on raw pointers: what the focal_rank / focal_median / focal_majority methods share
+inline void focal_rank_call(ec_dtype t, const void* src, const uint8_t* src_mask, size_t n, size_t cols, std::pair<uint32_t, uint32_t> radius,
+                            const std::pair<uint32_t, uint32_t>* q, ec_rank_method method, bool whole, void* dst, uint8_t* dst_mask) {
+    if (cols ? n % cols != 0 : n != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
+    if (!n) return;
+    const uint32_t flags = whole ? EC_FOCAL_WHOLE : 0;
+    if (q) check(ec_focal_rank(t, src, src_mask, cols, n / cols, radius.first, radius.second, q->first, q->second, method, flags, dst, dst_mask, current_stream()));
+    else check(ec_focal_majority(t, src, src_mask, cols, n / cols, radius.first, radius.second, flags, dst, dst_mask, current_stream()));
+}
+}  // namespace detail
+
 class CellBuffer {
     CellType ct_ = CellType::UInt8;
     size_t n_ = 0;
@@ -593,6 +605,30 @@ public:
     MaskedCellBuffer focal_whole(size_t cols, ec_focal_op op, std::pair<uint32_t, uint32_t> radius = {1, 1}) const;
     MaskedCellBuffer convolve_whole(size_t cols, const std::vector<double>& weights, std::pair<uint32_t, uint32_t> radius, bool normalize = false) const;
 
+    // Order statistics of a moving window (ec_focal_rank / ec_focal_majority; the rule is in include/erased_cells.h): the taps of every
+    // footprint in the reference's total order and the one at position q * (count - 1) kept, q = {num, den} an exact fraction, rounded
+    // down (EC_RANK_LOWER) or up (EC_RANK_UPPER) — {1, 2} the median, {0, 1} focal MIN, {1, 1} focal MAX — or the most frequent value
+    // of the footprint, the least of those that tie.  At most 64 cells in the footprint.  The result has this buffer's type; the _whole
+    // forms count only cells whose whole footprint exists, and a MaskedCellBuffer says which.
+    CellBuffer focal_rank(size_t cols, std::pair<uint32_t, uint32_t> q = {1, 2}, ec_rank_method method = EC_RANK_LOWER,
+                          std::pair<uint32_t, uint32_t> radius = {1, 1}) const {
+        CellBuffer out(ct_, n_);
+        detail::focal_rank_call(static_cast<ec_dtype>(ct_), ptr(), nullptr, n_, cols, radius, &q, method, false, out.ptr(), nullptr);
+        return out;
+    }
+    CellBuffer focal_median(size_t cols, std::pair<uint32_t, uint32_t> radius = {1, 1}, ec_rank_method method = EC_RANK_LOWER) const {
+        return focal_rank(cols, {1, 2}, method, radius);
+    }
+    CellBuffer focal_majority(size_t cols, std::pair<uint32_t, uint32_t> radius = {1, 1}) const {
+        CellBuffer out(ct_, n_);
+        detail::focal_rank_call(static_cast<ec_dtype>(ct_), ptr(), nullptr, n_, cols, radius, nullptr, EC_RANK_LOWER, false, out.ptr(), nullptr);
+        return out;
+    }
+    MaskedCellBuffer focal_rank_whole(size_t cols, std::pair<uint32_t, uint32_t> q = {1, 2}, ec_rank_method method = EC_RANK_LOWER,
+                                      std::pair<uint32_t, uint32_t> radius = {1, 1}) const;
+    MaskedCellBuffer focal_median_whole(size_t cols, std::pair<uint32_t, uint32_t> radius = {1, 1}, ec_rank_method method = EC_RANK_LOWER) const;
+    MaskedCellBuffer focal_majority_whole(size_t cols, std::pair<uint32_t, uint32_t> radius = {1, 1}) const;
+
     // ---- Ord/Eq (buffer.rs:373-436): cell type first, then lexicographic total order, then length
     int cmp(const CellBuffer& o) const {  // decided on the device: first differing cell, no download
         int32_t res = 0;
@@ -840,6 +876,23 @@ public:
                                            radius.second, (whole ? EC_FOCAL_WHOLE : 0) | (normalize ? EC_FOCAL_NORMALIZE : 0), b.ptr(), m.ptr(), current_stream()));
         return MaskedCellBuffer(std::move(b), std::move(m));
     }
+    // CellBuffer::focal_rank / focal_median / focal_majority over the cells whose mask byte is set: the position follows their count
+    MaskedCellBuffer focal_rank(size_t cols, std::pair<uint32_t, uint32_t> q = {1, 2}, ec_rank_method method = EC_RANK_LOWER,
+                                std::pair<uint32_t, uint32_t> radius = {1, 1}, bool whole = false) const {
+        CellBuffer b(cell_type(), len());
+        Mask m(len());
+        detail::focal_rank_call(static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), len(), cols, radius, &q, method, whole, b.ptr(), m.ptr());
+        return MaskedCellBuffer(std::move(b), std::move(m));
+    }
+    MaskedCellBuffer focal_median(size_t cols, std::pair<uint32_t, uint32_t> radius = {1, 1}, ec_rank_method method = EC_RANK_LOWER, bool whole = false) const {
+        return focal_rank(cols, {1, 2}, method, radius, whole);
+    }
+    MaskedCellBuffer focal_majority(size_t cols, std::pair<uint32_t, uint32_t> radius = {1, 1}, bool whole = false) const {
+        CellBuffer b(cell_type(), len());
+        Mask m(len());
+        detail::focal_rank_call(static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), len(), cols, radius, nullptr, EC_RANK_LOWER, whole, b.ptr(), m.ptr());
+        return MaskedCellBuffer(std::move(b), std::move(m));
+    }
     void put_window(size_t cols, std::pair<size_t, size_t> window, std::pair<size_t, size_t> window_size, const MaskedCellBuffer& tile) {
         if (cols ? len() % cols != 0 : len() != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
         if (tile.cell_type() != cell_type() || tile.len() != window_size.first * window_size.second)
@@ -978,6 +1031,22 @@ inline MaskedCellBuffer CellBuffer::convolve_whole(size_t cols, const std::vecto
     Mask m(n_);
     if (n_) check(ec_focal_convolve(static_cast<ec_dtype>(ct_), ptr(), nullptr, cols, n_ / cols, weights.data(), radius.first, radius.second,
                                     EC_FOCAL_WHOLE | (normalize ? EC_FOCAL_NORMALIZE : 0), b.ptr(), m.ptr(), current_stream()));
+    return MaskedCellBuffer(std::move(b), std::move(m));
+}
+
+inline MaskedCellBuffer CellBuffer::focal_rank_whole(size_t cols, std::pair<uint32_t, uint32_t> q, ec_rank_method method, std::pair<uint32_t, uint32_t> radius) const {
+    CellBuffer b(ct_, n_);
+    Mask m(n_);
+    detail::focal_rank_call(static_cast<ec_dtype>(ct_), ptr(), nullptr, n_, cols, radius, &q, method, true, b.ptr(), m.ptr());
+    return MaskedCellBuffer(std::move(b), std::move(m));
+}
+inline MaskedCellBuffer CellBuffer::focal_median_whole(size_t cols, std::pair<uint32_t, uint32_t> radius, ec_rank_method method) const {
+    return focal_rank_whole(cols, {1, 2}, method, radius);
+}
+inline MaskedCellBuffer CellBuffer::focal_majority_whole(size_t cols, std::pair<uint32_t, uint32_t> radius) const {
+    CellBuffer b(ct_, n_);
+    Mask m(n_);
+    detail::focal_rank_call(static_cast<ec_dtype>(ct_), ptr(), nullptr, n_, cols, radius, nullptr, EC_RANK_LOWER, true, b.ptr(), m.ptr());
     return MaskedCellBuffer(std::move(b), std::move(m));
 }
 

@@ -25,6 +25,7 @@ EC_CAST_AS, EC_CAST_ROUND = 0, 1  # ec_cast_mode: Rust's `as` / the storing rule
 EC_FOCAL_SUM, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_MAX = range(4)  # ec_focal_op
 EC_FOCAL_RADIUS_CAP = 7
 EC_FOCAL_WHOLE, EC_FOCAL_NORMALIZE = 1, 2  # flags of ec_focal / ec_focal_convolve
+EC_FOCAL_RANK_MAX_TAPS = 64  # the footprint of ec_focal_rank / ec_focal_majority
 EC_COMPOSITE_FIRST, EC_COMPOSITE_LAST, EC_COMPOSITE_MIN, EC_COMPOSITE_MAX, EC_COMPOSITE_SUM, EC_COMPOSITE_MEAN = range(6)  # ec_composite_op
 EC_COMPOSITE_MAX_LAYERS, EC_COMPOSITE_NONE = 64, 255
 EC_RANK_LOWER, EC_RANK_UPPER = range(2)  # ec_rank_method
@@ -206,6 +207,8 @@ SIGNATURES = {
     "ec_focal_result_type": (C.c_uint8, [I32, C.c_uint8]),
     "ec_focal": (I32, [I32, C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, VP, U8P, VP]),
     "ec_focal_convolve": (I32, [C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_uint32, VP, U8P, VP]),
+    "ec_focal_rank": (I32, [C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, I32, C.c_uint32, VP, U8P, VP]),
+    "ec_focal_majority": (I32, [C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, VP, U8P, VP]),
     "ec_zonal_workspace_bytes": (SZ, [I32]),
     "ec_zonal_stats_device": (I32, [C.c_uint8, VP, U8P, C.c_uint8, VP, SZ, I32, VP, VP, VP]),
     "ec_zonal_stats_compute": (I32, [C.c_uint8, VP, U8P, C.c_uint8, VP, SZ, I32, VP, VP]),

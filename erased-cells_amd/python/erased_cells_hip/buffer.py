@@ -477,6 +477,23 @@ def _convolve(buf: "CellBuffer", mask, cols: int, weights, normalize: bool, whol
     return out, om
 
 
+def _focal_rank(buf: "CellBuffer", mask, cols: int, q, method, radius, whole: bool):
+    """ec_focal_rank, or ec_focal_majority when `q` is None, of `buf` (under `mask`, or None) read as rows of `cols` cells ->
+    (result buffer of the same cell type, result Mask or None), as `_focal` gives them for "min"."""
+    num, den, m = _rank_args(q, method, "focal_rank") if q is not None else (0, 1, 0)
+    (rx, ry), rows = _radius(radius), _raster_rows(buf.n, cols)
+    out = CellBuffer.empty(buf.n, buf.ct)
+    om = Mask.empty(buf.n) if (mask is not None or whole) else None
+    flags = EC_FOCAL_WHOLE if whole else 0
+    if buf.n:  # an empty buffer has no memory to point at
+        sm, dm = (mask.mem.ptr if mask is not None else None), (om.mem.ptr if om is not None else None)
+        if q is not None:
+            check(lib().ec_focal_rank(buf.ct, buf.mem.ptr, sm, cols, rows, rx, ry, num, den, m, flags, out.mem.ptr, dm, _stream))
+        else:
+            check(lib().ec_focal_majority(buf.ct, buf.mem.ptr, sm, cols, rows, rx, ry, flags, out.mem.ptr, dm, _stream))
+    return out, om
+
+
 # --------------------------------------------------------------------------- CellBuffer
 @dataclasses.dataclass(frozen=True)
 class Stats:
@@ -587,6 +604,24 @@ class CellBuffer:
         """The weighted moving-window sum (a correlation) with the 2-D `weights` of odd shape (2 ry + 1, 2 rx + 1), as Float64 cells;
         `normalize` divides by the sum of the weights counted.  A MaskedCellBuffer with `whole`, as `focal`."""
         out, om = _convolve(self, None, cols, weights, normalize, whole)
+        return out if om is None else MaskedCellBuffer(out, om)
+
+    def focal_rank(self, cols: int, q=(1, 2), method="lower", radius=(1, 1), whole: bool = False):
+        """The moving-window order statistic (ec_focal_rank; the rule is in include/erased_cells.h): the taps of every cell's footprint
+        in the reference's total order and the one at position q * (count - 1) kept — rounded down ("lower") or up ("upper"),
+        q = (num, den) an exact fraction as `composite_rank` takes it, `radius` = (rx, ry) as `focal` takes it, at most 64 cells in the
+        footprint.  (0, 1) is `focal(cols, "min")`, (1, 1) `focal(cols, "max")`.  Returns what `focal(cols, "min", ...)` returns."""
+        out, om = _focal_rank(self, None, cols, q, method, radius, whole)
+        return out if om is None else MaskedCellBuffer(out, om)
+
+    def focal_median(self, cols: int, radius=(1, 1), method="lower", whole: bool = False):
+        """`focal_rank` at q = 1/2: the median filter.  The lower and the upper median agree where the tap count is odd."""
+        return self.focal_rank(cols, (1, 2), method, radius, whole)
+
+    def focal_majority(self, cols: int, radius=(1, 1), whole: bool = False):
+        """The majority (mode) filter (ec_focal_majority): every cell takes the value most cells of its footprint hold, the least of
+        those that tie under the total order; "equal" is equal bits.  Returns what `focal(cols, "min", ...)` returns."""
+        out, om = _focal_rank(self, None, cols, None, None, radius, whole)
         return out if om is None else MaskedCellBuffer(out, om)
 
     def put_window(self, cols: int, window, tile: "CellBuffer", window_size) -> None:
@@ -1056,6 +1091,18 @@ class MaskedCellBuffer:
         """`CellBuffer.convolve` over the cells whose mask byte is set."""
         return MaskedCellBuffer(*_convolve(self._buf, self._mask, cols, weights, normalize, whole))
 
+    def focal_rank(self, cols: int, q=(1, 2), method="lower", radius=(1, 1), whole: bool = False) -> "MaskedCellBuffer":
+        """`CellBuffer.focal_rank` over the cells whose mask byte is set: the position follows the count of those."""
+        return MaskedCellBuffer(*_focal_rank(self._buf, self._mask, cols, q, method, radius, whole))
+
+    def focal_median(self, cols: int, radius=(1, 1), method="lower", whole: bool = False) -> "MaskedCellBuffer":
+        """`focal_rank` at q = 1/2 over the cells whose mask byte is set."""
+        return self.focal_rank(cols, (1, 2), method, radius, whole)
+
+    def focal_majority(self, cols: int, radius=(1, 1), whole: bool = False) -> "MaskedCellBuffer":
+        """`CellBuffer.focal_majority` over the cells whose mask byte is set."""
+        return MaskedCellBuffer(*_focal_rank(self._buf, self._mask, cols, None, None, radius, whole))
+
     def put_window(self, cols: int, window, tile: "MaskedCellBuffer", window_size) -> None:
         """CellBuffer.put_window for values and mask in one launch."""
         if tile.cell_type() != self.cell_type():
@@ -1416,18 +1463,18 @@ def composite(layers, op="first", min_count: int = 1, aux: bool = False):
 RANK_METHODS = {"lower": EC_RANK_LOWER, "upper": EC_RANK_UPPER}
 
 
-def _rank_args(q, method):
+def _rank_args(q, method, what="composite_rank"):
     """(num, den, ec_rank_method) of `q`, a pair of integers (num, den) with 0 <= num <= den and 1 <= den <= EC_RANK_MAX_DEN, or 0 or 1,
     and of "lower" / "upper" or an ec_rank_method value; anything else is refused.  A float is no exact rational: it is refused."""
     if isinstance(q, (int, np.integer)) and not isinstance(q, bool) and int(q) in (0, 1):
         q = (int(q), 1)
     ok = isinstance(q, (tuple, list)) and len(q) == 2 and all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in q)
     if not ok or not (1 <= int(q[1]) <= EC_RANK_MAX_DEN and 0 <= int(q[0]) <= int(q[1])):
-        raise EcError(EC_ERR_ARG, f"composite_rank: q {q!r} is not a pair of integers (num, den) with 0 <= num <= den and "
+        raise EcError(EC_ERR_ARG, f"{what}: q {q!r} is not a pair of integers (num, den) with 0 <= num <= den and "
                                   f"1 <= den <= EC_RANK_MAX_DEN ({EC_RANK_MAX_DEN})")
     m = RANK_METHODS.get(method, method) if isinstance(method, str) else method
     if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) not in (EC_RANK_LOWER, EC_RANK_UPPER):
-        raise EcError(EC_ERR_ARG, f"composite_rank: method {method!r} is not one of {sorted(RANK_METHODS)} or an ec_rank_method value 0..1")
+        raise EcError(EC_ERR_ARG, f"{what}: method {method!r} is not one of {sorted(RANK_METHODS)} or an ec_rank_method value 0..1")
     return int(q[0]), int(q[1]), int(m)
 
 

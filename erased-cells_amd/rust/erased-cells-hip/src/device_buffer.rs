@@ -350,6 +350,58 @@ impl CellBuffer {
         Ok((out, mask))
     }
 
+    /// `ec_focal_rank`, or `ec_focal_majority` when `q` is `None`, with a mask pair (both, or null pointers) and the flags given.
+    pub(crate) fn focal_rank_raw(&self, cols: usize, q: Option<(RankFraction, RankMethod)>, radius: (u32, u32), flags: u32, mask: *const u8,
+                                 out_mask: *mut u8) -> Result<Self> {
+        assert!(if cols == 0 { self.len == 0 } else { self.len % cols == 0 }, "{} cells are not rows of {cols} cells", self.len);
+        let rows = if cols == 0 { 0 } else { self.len / cols };
+        let out = Self::uninit(self.ct, self.len);
+        if self.len != 0 {
+            check(unsafe {
+                match q {
+                    Some((q, method)) => ec_focal_rank(
+                        self.ct as u8, self.dev_ptr(), mask, cols as u64, rows as u64, radius.0, radius.1, q.num, q.den, method as i32, flags,
+                        out.mem.ptr(), out_mask, stream(),
+                    ),
+                    None => ec_focal_majority(self.ct as u8, self.dev_ptr(), mask, cols as u64, rows as u64, radius.0, radius.1, flags, out.mem.ptr(), out_mask, stream()),
+                }
+            })?;
+        }
+        Ok(out)
+    }
+
+    /// The moving-window order statistic: the cells of every footprint (at most `EC_FOCAL_RANK_MAX_TAPS`) in the reference's total
+    /// order and the one at position `q * (count - 1)` kept, rounded down or up by `method`; `RankFraction::MEDIAN` is the median
+    /// filter, `(0, 1)` [`CellBuffer::focal`] MIN, `(1, 1)` its MAX.  The rule is at `ec_focal_rank` in include/erased_cells.h.  One launch.
+    pub fn focal_rank(&self, cols: usize, q: RankFraction, method: RankMethod, radius: (u32, u32)) -> Result<Self> {
+        self.focal_rank_raw(cols, Some((q, method)), radius, 0, std::ptr::null(), std::ptr::null_mut())
+    }
+
+    /// [`CellBuffer::focal_rank`] at one half: the median filter.  The lower and the upper median agree where the count is odd.
+    pub fn focal_median(&self, cols: usize, radius: (u32, u32), method: RankMethod) -> Result<Self> {
+        self.focal_rank(cols, RankFraction::MEDIAN, method, radius)
+    }
+
+    /// The majority (mode) filter: every cell takes the value most cells of its footprint hold, the least of those that tie under the
+    /// total order; "equal" is equal bits.  The rule is at `ec_focal_majority` in include/erased_cells.h.  One launch.
+    pub fn focal_majority(&self, cols: usize, radius: (u32, u32)) -> Result<Self> {
+        self.focal_rank_raw(cols, None, radius, 0, std::ptr::null(), std::ptr::null_mut())
+    }
+
+    /// [`CellBuffer::focal_rank`] where only a cell whose whole footprint lies inside the raster is valid: the cells and the mask that says which.
+    pub fn focal_rank_whole(&self, cols: usize, q: RankFraction, method: RankMethod, radius: (u32, u32)) -> Result<(Self, Mask)> {
+        let mask = Mask::uninit(self.len);
+        let out = self.focal_rank_raw(cols, Some((q, method)), radius, EC_FOCAL_WHOLE, std::ptr::null(), mask.dev_ptr_mut())?;
+        Ok((out, mask))
+    }
+
+    /// [`CellBuffer::focal_majority`] where only a cell whose whole footprint lies inside the raster is valid.
+    pub fn focal_majority_whole(&self, cols: usize, radius: (u32, u32)) -> Result<(Self, Mask)> {
+        let mask = Mask::uninit(self.len);
+        let out = self.focal_rank_raw(cols, None, radius, EC_FOCAL_WHOLE, std::ptr::null(), mask.dev_ptr_mut())?;
+        Ok((out, mask))
+    }
+
     /// The weighted moving-window sum (a correlation: weight `[dy][dx]` meets cell `(i - ry + dy, j - rx + dx)`) as `Float64` cells;
     /// `normalize` divides by the sum of the weights counted.  One launch; the weights travel in the kernel's arguments.
     pub fn convolve(&self, cols: usize, weights: &[f64], radius: (u32, u32), normalize: bool) -> Result<Self> {

@@ -60,6 +60,8 @@ pub const EC_FOCAL_RADIUS_CAP: u32 = 7;
 /// Flags of `ec_focal` / `ec_focal_convolve`: only whole footprints are valid; divide by the weights counted (convolve only).
 pub const EC_FOCAL_WHOLE: u32 = 1;
 pub const EC_FOCAL_NORMALIZE: u32 = 2;
+/// The most cells the footprint of `ec_focal_rank` / `ec_focal_majority` holds: one sorting network (`EC_FOCAL_RANK_MAX_TAPS`).
+pub const EC_FOCAL_RANK_MAX_TAPS: u32 = 64;
 /// The most zones one `ec_zonal_stats_*` call serves (`EC_ZONAL_MAX_ZONES`).
 pub const EC_ZONAL_MAX_ZONES: usize = 256;
 /// The most breaks one reclass table holds (`EC_RECLASS_MAX_BREAKS`), the size of its record and the flags of the record.
@@ -365,6 +367,11 @@ extern "C" {
     pub fn ec_focal_convolve(t: ec_dtype, src: *const c_void, src_mask_or_null: *const u8, cols: u64, rows: u64,
                              weights_host: *const f64, rx: u32, ry: u32, flags: u32, dst: *mut c_void, dst_mask_or_null: *mut u8,
                              s: ec_stream) -> ec_status;
+    pub fn ec_focal_rank(t: ec_dtype, src: *const c_void, src_mask_or_null: *const u8, cols: u64, rows: u64, rx: u32, ry: u32,
+                         num: u32, den: u32, method: i32, flags: u32, dst: *mut c_void, dst_mask_or_null: *mut u8,
+                         s: ec_stream) -> ec_status;
+    pub fn ec_focal_majority(t: ec_dtype, src: *const c_void, src_mask_or_null: *const u8, cols: u64, rows: u64, rx: u32, ry: u32,
+                             flags: u32, dst: *mut c_void, dst_mask_or_null: *mut u8, s: ec_stream) -> ec_status;
     pub fn ec_composite_result_type(op: i32, t: ec_dtype) -> ec_dtype;
     pub fn ec_composite(op: i32, t: ec_dtype, layers: *const *const c_void, masks_or_null: *const *const u8, n_layers: i32, n: usize,
                         min_count: u32, dst: *mut c_void, dst_mask_or_null: *mut u8, aux_or_null: *mut u8, s: ec_stream) -> ec_status;

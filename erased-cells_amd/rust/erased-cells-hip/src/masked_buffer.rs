@@ -148,6 +148,28 @@ impl MaskedCellBuffer {
         Ok(MaskedCellBuffer(cells, mask))
     }
 
+    /// [`CellBuffer::focal_rank`] over the cells whose mask byte is set: the position follows the count of those.  With `whole` only a
+    /// cell whose whole footprint exists and is unmasked is valid.  One launch.
+    pub fn focal_rank(&self, cols: usize, q: RankFraction, method: RankMethod, radius: (u32, u32), whole: bool) -> Result<Self> {
+        let mask = Mask::uninit(self.0.len());
+        let flags = if whole { EC_FOCAL_WHOLE } else { 0 };
+        let cells = self.0.focal_rank_raw(cols, Some((q, method)), radius, flags, self.1.dev_ptr(), mask.dev_ptr_mut())?;
+        Ok(MaskedCellBuffer(cells, mask))
+    }
+
+    /// [`MaskedCellBuffer::focal_rank`] at one half: the median filter over the cells whose mask byte is set.
+    pub fn focal_median(&self, cols: usize, radius: (u32, u32), method: RankMethod, whole: bool) -> Result<Self> {
+        self.focal_rank(cols, RankFraction::MEDIAN, method, radius, whole)
+    }
+
+    /// [`CellBuffer::focal_majority`] over the cells whose mask byte is set.
+    pub fn focal_majority(&self, cols: usize, radius: (u32, u32), whole: bool) -> Result<Self> {
+        let mask = Mask::uninit(self.0.len());
+        let flags = if whole { EC_FOCAL_WHOLE } else { 0 };
+        let cells = self.0.focal_rank_raw(cols, None, radius, flags, self.1.dev_ptr(), mask.dev_ptr_mut())?;
+        Ok(MaskedCellBuffer(cells, mask))
+    }
+
     /// [`CellBuffer::convolve`] over the cells whose mask byte is set.
     pub fn convolve(&self, cols: usize, weights: &[f64], radius: (u32, u32), normalize: bool, whole: bool) -> Result<Self> {
         let mask = Mask::uninit(self.0.len());

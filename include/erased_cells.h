@@ -652,6 +652,43 @@ ec_status ec_focal_convolve(ec_dtype t, const void *src, const uint8_t *src_mask
                             uint64_t cols, uint64_t rows, const double *weights_host, uint32_t rx, uint32_t ry,
                             uint32_t flags, void *dst /* f64 cells */, uint8_t *dst_mask_or_null, ec_stream stream);
 
+/* Order statistics of a moving window: the median filter, the other window quantiles and the majority (mode) filter.
+ * ec_focal's MIN and MAX are the two ends of a footprint's order; ec_focal_rank is any position between them — the median
+ * removes a speckle or salt-and-pepper outlier where MEAN smears it and MIN / MAX keep it — and ec_focal_majority is the
+ * clean-up step after a classification: every cell takes the class most of its neighbours have.
+ * Footprint, TAPS, clipping at the raster's edges (no wrap into the neighbouring row), VALID (count > 0, or
+ * count == (2 rx + 1) * (2 ry + 1) under EC_FOCAL_WHOLE), dst_mask_or_null and rx == ry == 0 mean exactly what they mean for
+ * ec_focal: a cell that is no tap contributes nothing, whatever it holds; the centre cell's mask byte has no special role; a
+ * valid cell stores its result and mask byte 1, an invalid one all-zero bits and mask byte 0.  dst holds cols * rows cells of
+ * type t.  No allocation, asynchronous, capturable after ec_prepare_stream, no sharded form.  The only flag is EC_FOCAL_WHOLE.
+ * A footprint has at most EC_FOCAL_RANK_MAX_TAPS cells, (2 rx + 1) * (2 ry + 1) <= 64 with rx, ry <= EC_FOCAL_RADIUS_CAP:
+ * 3 x 3, 5 x 5, 7 x 7, 7 x 9, 3 x 15, 1 x 15 and so on; 9 x 9 and 15 x 5 are refused.
+ * ec_focal_rank, the rule: let c be the number of taps of the cell.  Order the taps ascending by order_key(cell), the
+ * reference's total order (src/value.rs:248-265, as ec_min_max and ec_composite_rank use it).  The key is a bijection on
+ * bits, so taps of equal key have equal bits and how ties are ordered cannot reach the result.  The position kept is
+ * ec_composite_rank's, for q = num / den, 0 <= num <= den, 1 <= den <= EC_RANK_MAX_DEN, counting from 0:
+ *   EC_RANK_LOWER   r = (num * (c - 1)) / den
+ *   EC_RANK_UPPER   r = (num * (c - 1) + den - 1) / den
+ * and the cell stores the bits of the tap at position r.
+ *   num = 0 gives the bits and the mask of ec_focal MIN, num = den those of ec_focal MAX.
+ *   1/2 LOWER is the lower median, 1/2 UPPER the upper one; they agree where c is odd.
+ *   At clipped edges and next to holes r follows the clipped count c, not the footprint's size.
+ * ec_focal_majority, the rule: among the taps keep the key that occurs most often; among keys of equal greatest frequency the
+ * least under the total order; the cell stores its bits.  "Equal" means equal bits: -0.0 and 0.0 are different keys, and so
+ * are NaNs of different payloads.  There is no frequency output and no "strict majority only" flag.
+ * Refusals (EC_ERR_ARG, before any device work; a refused call writes nothing), in this order: ec_focal's — a null src or dst,
+ * unknown flag bits (every bit but EC_FOCAL_WHOLE), rx or ry above EC_FOCAL_RADIUS_CAP — then more than
+ * EC_FOCAL_RANK_MAX_TAPS taps, then ec_focal's again: dst_mask NULL where it is required, cols * rows beyond 64 bits,
+ * dst == src or dst_mask == src_mask, more than 2^31 - 1 tiles; for ec_focal_rank then den outside 1 .. EC_RANK_MAX_DEN or
+ * num > den, then a method that is none.  A bad dtype is EC_ERR_UNSUPPORTED_TYPE.  cols * rows == 0 is EC_OK and launches
+ * nothing. */
+enum { EC_FOCAL_RANK_MAX_TAPS = 64 };
+ec_status ec_focal_rank(ec_dtype t, const void *src, const uint8_t *src_mask_or_null, uint64_t cols, uint64_t rows,
+                        uint32_t rx, uint32_t ry, uint32_t num, uint32_t den, int32_t method /* an ec_rank_method */,
+                        uint32_t flags, void *dst, uint8_t *dst_mask_or_null, ec_stream stream);
+ec_status ec_focal_majority(ec_dtype t, const void *src, const uint8_t *src_mask_or_null, uint64_t cols, uint64_t rows,
+                            uint32_t rx, uint32_t ry, uint32_t flags, void *dst, uint8_t *dst_mask_or_null, ec_stream stream);
+
 /* ---------------------------------------------------------------- *
  * Composites: one raster from a stack of K co-registered layers (dates, tiles, sensors), every output cell from the K cells
  * at its index — the first cloud-free observation, the greatest-value composite, the mean over the clear observations, how
