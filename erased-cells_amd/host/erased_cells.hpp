@@ -750,6 +750,30 @@ public:
     Mask dilate(size_t cols, std::pair<uint32_t, uint32_t> radius = {1, 1}) const { return morph(cols, EC_FOCAL_MAX, radius); }
     Mask erode(size_t cols, std::pair<uint32_t, uint32_t> radius = {1, 1}) const { return morph(cols, EC_FOCAL_MIN, radius); }
 
+    // ec_distance's max_sq of a greatest distance: floor(max_distance^2), exactly — the sign of fma(d, d, -k) is that of d^2 - k.
+    // Infinity and everything from 2^16 cells on, beyond any raster's diagonal, is EC_DISTANCE_UNLIMITED.
+    static uint32_t max_sq_of(double max_distance) {
+        if (!(max_distance >= 0)) throw Error(EC_ERR_ARG, "distance: the greatest distance is not a number >= 0");
+        if (max_distance >= 65536.0) return EC_DISTANCE_UNLIMITED;
+        double k = std::floor(max_distance * max_distance);
+        if (std::fma(max_distance, max_distance, -k) < 0) k -= 1;
+        else if (std::fma(max_distance, max_distance, -(k + 1)) >= 0) k += 1;
+        return static_cast<uint32_t>(k);
+    }
+    // The exact Euclidean distance, in cells, of every cell of the mask read as rows of `cols` bytes to the nearest SET byte
+    // (ec_distance; the rule is in include/erased_cells.h): Float64 distances, or with `squared` the UInt32 squared distances.  A cell
+    // is valid iff the mask has a set byte and its distance is at most max_distance; an invalid cell holds zero bits.
+    MaskedCellBuffer distance(size_t cols, double max_distance = std::numeric_limits<double>::infinity(), bool squared = false) const;
+    // A byte of the result is set iff a set byte of the mask lies within `distance` cells of it, Euclidean: the round buffer (dilate is
+    // the rectangle).  ec_distance's mask-only form: no distance is ever written.
+    Mask within(size_t cols, double distance) const {
+        if (cols ? n_ % cols != 0 : n_ != 0) throw std::logic_error("the mask is not rows of " + std::to_string(cols) + " bytes");
+        const uint32_t max_sq = max_sq_of(distance);
+        Mask m(n_);
+        if (n_) check(ec_distance(ptr(), cols, n_ / cols, max_sq, EC_U32, nullptr, m.ptr(), nullptr, current_stream()));
+        return m;
+    }
+
     Mask operator!() const& {  // Not for &Mask (mask.rs:111-116)
         Mask m(n_);
         check(ec_mask_not(ptr(), n_, m.ptr(), current_stream()));
@@ -1031,6 +1055,15 @@ inline MaskedCellBuffer CellBuffer::convolve_whole(size_t cols, const std::vecto
     Mask m(n_);
     if (n_) check(ec_focal_convolve(static_cast<ec_dtype>(ct_), ptr(), nullptr, cols, n_ / cols, weights.data(), radius.first, radius.second,
                                     EC_FOCAL_WHOLE | (normalize ? EC_FOCAL_NORMALIZE : 0), b.ptr(), m.ptr(), current_stream()));
+    return MaskedCellBuffer(std::move(b), std::move(m));
+}
+
+inline MaskedCellBuffer Mask::distance(size_t cols, double max_distance, bool squared) const {
+    if (cols ? n_ % cols != 0 : n_ != 0) throw std::logic_error("the mask is not rows of " + std::to_string(cols) + " bytes");
+    const uint32_t max_sq = max_sq_of(max_distance);
+    CellBuffer b(squared ? CellType::UInt32 : CellType::Float64, n_);
+    Mask m(n_);
+    if (n_) check(ec_distance(ptr(), cols, n_ / cols, max_sq, squared ? EC_U32 : EC_F64, b.ptr(), m.ptr(), nullptr, current_stream()));
     return MaskedCellBuffer(std::move(b), std::move(m));
 }
 

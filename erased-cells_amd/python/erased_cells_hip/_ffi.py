@@ -33,6 +33,7 @@ EC_RANK_MAX_DEN = 65535
 EC_ZONAL_MAX_ZONES = 256
 EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES = 255, 4384
 EC_RECLASS_HAS_NODATA, EC_RECLASS_DROPS = 1, 2  # ec_reclass_table.flags
+EC_DISTANCE_MAX_SIDE, EC_DISTANCE_UNLIMITED = 32768, 0xFFFFFFFF  # ec_distance: the longest side, max_sq of "no limit"
 
 
 class _Payload(C.Union):
@@ -217,6 +218,8 @@ SIGNATURES = {
     "ec_reclass_table_build": (I32, [C.c_uint8, C.c_uint8, VP, I32, I32, C.c_uint8, PV, U8P, PV, VP]),
     "ec_reclass": (I32, [C.c_uint8, VP, U8P, SZ, C.c_uint8, VP, VP, U8P, VP]),
     "ec_sharded_reclass": (I32, [VP, C.c_uint8, PVP, PVP, PSZ, C.c_uint8, PVP, PVP, PVP]),
+    "ec_distance_workspace_bytes": (SZ, [C.c_uint64, C.c_uint64]),
+    "ec_distance": (I32, [U8P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint8, VP, U8P, VP, VP]),
     "ec_composite_result_type": (C.c_uint8, [I32, C.c_uint8]),
     "ec_composite": (I32, [I32, C.c_uint8, PVP, PVP, I32, SZ, C.c_uint32, VP, U8P, U8P, VP]),
     "ec_sharded_composite": (I32, [VP, I32, C.c_uint8, C.POINTER(PVP), C.POINTER(PVP), I32, PSZ, C.c_uint32, PVP, PVP, PVP]),

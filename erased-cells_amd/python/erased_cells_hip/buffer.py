@@ -16,11 +16,12 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import fractions
 from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_COMPOSITE_MAX_LAYERS, EC_RANK_LOWER, EC_RANK_MAX_DEN, EC_RANK_UPPER, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_ZONAL_MAX_ZONES, EC_RECLASS_DROPS, EC_RECLASS_HAS_NODATA, EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES, EC_RESAMPLE_BILINEAR, EcError, EcReclassTable, EcStats, EcValue, check, lib
+from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_COMPOSITE_MAX_LAYERS, EC_DISTANCE_UNLIMITED, EC_RANK_LOWER, EC_RANK_MAX_DEN, EC_RANK_UPPER, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_ZONAL_MAX_ZONES, EC_RECLASS_DROPS, EC_RECLASS_HAS_NODATA, EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES, EC_RESAMPLE_BILINEAR, EcError, EcReclassTable, EcStats, EcValue, check, lib
 
 # CellType (src/ctype.rs:11-20; order of with_ct!, src/lib.rs:89-98)
 UInt8, UInt16, UInt32, UInt64, Int8, Int16, Int32, Int64, Float32, Float64 = range(10)
@@ -439,6 +440,17 @@ def _raster_rows(n: int, cols: int) -> int:
     if cols < 0 or (cols == 0 and n != 0) or (cols and n % cols):
         raise AssertionError(f"a buffer of {n} cells is not a raster of rows of {cols} cells")
     return n // cols if cols else 0
+
+
+def _max_sq(max_distance) -> int:
+    """ec_distance's max_sq of a greatest distance: floor(max_distance^2), exact through Fraction (an int, a float or a Fraction);
+    None, infinity and everything from 2^16 cells on — beyond any raster's diagonal — is EC_DISTANCE_UNLIMITED"""
+    if max_distance is None or max_distance == float("inf"):
+        return EC_DISTANCE_UNLIMITED
+    if isinstance(max_distance, bool) or max_distance != max_distance or max_distance < 0:
+        raise EcError(EC_ERR_ARG, f"distance: the greatest distance {max_distance!r} is not a number >= 0")
+    sq = fractions.Fraction(max_distance) ** 2
+    return min(sq.numerator // sq.denominator, EC_DISTANCE_UNLIMITED)
 
 
 def _radius(radius):
@@ -947,6 +959,29 @@ class Mask:
     def erode(self, cols: int, radius=(1, 1)) -> "Mask":
         """A byte of the result is set iff ALL bytes of its clipped footprint are (ec_focal MIN)."""
         return self._morph(cols, EC_FOCAL_MIN, radius)
+
+    def _distance(self, cols: int, max_sq: int, ct, want_mask: bool = True):
+        """ec_distance of the mask read as rows of `cols` bytes, with the workspace from the library's pool -> (CellBuffer of type
+        `ct` or None for the mask-only form, Mask or None)."""
+        rows = _raster_rows(self.n, cols)
+        out = CellBuffer.empty(self.n, ct) if ct is not None else None
+        om = Mask.empty(self.n) if want_mask else None
+        if self.n:  # an empty mask has no memory to point at
+            check(lib().ec_distance(self.mem.ptr, cols, rows, max_sq, ct if ct is not None else UInt32, out.mem.ptr if out is not None else None,
+                                    om.mem.ptr if om is not None else None, None, _stream))
+        return out, om
+
+    def distance(self, cols: int, max_distance=None, squared: bool = False) -> "MaskedCellBuffer":
+        """The exact Euclidean distance, in cells, of every cell of the mask read as rows of `cols` bytes to the nearest SET byte
+        (ec_distance; the rule is in include/erased_cells.h): Float64 distances, or with `squared` the UInt32 squared distances.  A
+        cell is valid iff the mask has a set byte and its distance is at most `max_distance` (None: no limit; an int, a float or a
+        Fraction, compared exactly); an invalid cell holds zero bits."""
+        return MaskedCellBuffer(*self._distance(cols, _max_sq(max_distance), UInt32 if squared else Float64))
+
+    def within(self, cols: int, distance) -> "Mask":
+        """A byte of the result is set iff a set byte of the mask lies within `distance` cells of it, Euclidean: the round buffer
+        (`dilate` is the rectangle).  ec_distance's mask-only form: no distance is ever written."""
+        return self._distance(cols, _max_sq(distance), None)[1]
 
     def counts(self) -> tuple[int, int]:
         """(data, nodata) — mask.rs:72-80."""

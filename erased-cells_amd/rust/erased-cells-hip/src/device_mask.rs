@@ -163,6 +163,60 @@ impl Mask {
     pub fn erode(&self, cols: usize, radius: (u32, u32)) -> Result<Mask> {
         self.morph(cols, EC_FOCAL_MIN, radius)
     }
+
+    /// `ec_distance`'s `max_sq` of a greatest distance: floor(max_distance^2), exactly — the sign of `mul_add(d, d, -k)` is that of
+    /// d^2 - k.  `None`, infinity and everything from 2^16 cells on, beyond any raster's diagonal, is `EC_DISTANCE_UNLIMITED`.
+    pub fn max_sq_of(max_distance: Option<f64>) -> u32 {
+        let d = match max_distance {
+            None => return EC_DISTANCE_UNLIMITED,
+            Some(d) => d,
+        };
+        assert!(d >= 0.0, "the greatest distance {d} is not a number >= 0");
+        if d >= 65536.0 {
+            return EC_DISTANCE_UNLIMITED;
+        }
+        let mut k = (d * d).floor();
+        if d.mul_add(d, -k) < 0.0 {
+            k -= 1.0;
+        } else if d.mul_add(d, -(k + 1.0)) >= 0.0 {
+            k += 1.0;
+        }
+        k as u32
+    }
+
+    // ec_distance with the workspace from the library's pool: the values (or none: the mask-only form) and the validity bytes
+    fn distance_raw(&self, cols: usize, max_sq: u32, out: Option<&crate::CellBuffer>, out_mask: &Mask) -> Result<()> {
+        assert!(if cols == 0 { self.len == 0 } else { self.len % cols == 0 }, "{} bytes are not rows of {cols} bytes", self.len);
+        if self.len == 0 {
+            return Ok(());
+        }
+        let (t, dst) = match out {
+            Some(b) => (b.ct as u8, b.dev_ptr() as *mut c_void),
+            None => (crate::CellType::UInt32 as u8, std::ptr::null_mut()),
+        };
+        check(unsafe {
+            ec_distance(self.dev_ptr(), cols as u64, (self.len / cols) as u64, max_sq, t, dst, out_mask.dev_ptr_mut(), std::ptr::null_mut(), stream())
+        })
+    }
+
+    /// The exact Euclidean distance, in cells, of every cell of the mask read as rows of `cols` bytes to the nearest SET byte
+    /// (`ec_distance`; the rule is in include/erased_cells.h): Float64 distances, or with `squared` the UInt32 squared distances.
+    /// A cell is valid iff the mask has a set byte and its distance is at most `max_distance` (`None`: no limit); an invalid
+    /// cell holds zero bits.
+    pub fn distance(&self, cols: usize, max_distance: Option<f64>, squared: bool) -> Result<crate::MaskedCellBuffer> {
+        let ct = if squared { crate::CellType::UInt32 } else { crate::CellType::Float64 };
+        let (out, om) = (crate::CellBuffer::uninit(ct, self.len), Mask::uninit(self.len));
+        self.distance_raw(cols, Self::max_sq_of(max_distance), Some(&out), &om)?;
+        Ok(crate::MaskedCellBuffer::new(out, om))
+    }
+
+    /// A byte of the result is set iff a set byte of the mask lies within `distance` cells of it, Euclidean: the round buffer
+    /// (`dilate` is the rectangle).  `ec_distance`'s mask-only form: no distance is ever written.
+    pub fn within(&self, cols: usize, distance: f64) -> Result<Mask> {
+        let om = Mask::uninit(self.len);
+        self.distance_raw(cols, Self::max_sq_of(Some(distance)), None, &om)?;
+        Ok(om)
+    }
 }
 
 impl Default for Mask {

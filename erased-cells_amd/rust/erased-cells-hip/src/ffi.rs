@@ -62,6 +62,9 @@ pub const EC_FOCAL_WHOLE: u32 = 1;
 pub const EC_FOCAL_NORMALIZE: u32 = 2;
 /// The most cells the footprint of `ec_focal_rank` / `ec_focal_majority` holds: one sorting network (`EC_FOCAL_RANK_MAX_TAPS`).
 pub const EC_FOCAL_RANK_MAX_TAPS: u32 = 64;
+/// The longest side of a raster `ec_distance` takes (`EC_DISTANCE_MAX_SIDE`) and its `max_sq` of "no limit" (`EC_DISTANCE_UNLIMITED`).
+pub const EC_DISTANCE_MAX_SIDE: u64 = 32768;
+pub const EC_DISTANCE_UNLIMITED: u32 = 0xFFFF_FFFF;
 /// The most zones one `ec_zonal_stats_*` call serves (`EC_ZONAL_MAX_ZONES`).
 pub const EC_ZONAL_MAX_ZONES: usize = 256;
 /// The most breaks one reclass table holds (`EC_RECLASS_MAX_BREAKS`), the size of its record and the flags of the record.
@@ -372,6 +375,10 @@ extern "C" {
                          s: ec_stream) -> ec_status;
     pub fn ec_focal_majority(t: ec_dtype, src: *const c_void, src_mask_or_null: *const u8, cols: u64, rows: u64, rx: u32, ry: u32,
                              flags: u32, dst: *mut c_void, dst_mask_or_null: *mut u8, s: ec_stream) -> ec_status;
+    // the exact Euclidean distance transform of a mask: squared distances (u32) or distances (f64), or only "within max_sq"
+    pub fn ec_distance_workspace_bytes(cols: u64, rows: u64) -> usize;
+    pub fn ec_distance(mask: *const u8, cols: u64, rows: u64, max_sq: u32, out_type: ec_dtype, dst_or_null: *mut c_void,
+                       dst_mask_or_null: *mut u8, workspace_dev_or_null: *mut c_void, stream: ec_stream) -> ec_status;
     pub fn ec_composite_result_type(op: i32, t: ec_dtype) -> ec_dtype;
     pub fn ec_composite(op: i32, t: ec_dtype, layers: *const *const c_void, masks_or_null: *const *const u8, n_layers: i32, n: usize,
                         min_count: u32, dst: *mut c_void, dst_mask_or_null: *mut u8, aux_or_null: *mut u8, s: ec_stream) -> ec_status;

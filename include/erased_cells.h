@@ -980,6 +980,50 @@ ec_status ec_sharded_reclass(ec_shard_group *g, ec_dtype t, const void *const *s
                              uint8_t *const *dst_masks_or_null);
 
 /* ---------------------------------------------------------------- *
+ * Distance: the exact Euclidean distance transform of a mask — "how far is every cell from the nearest cloud / water / road /
+ * valid cell" (GDAL's gdal_proximity, scipy.ndimage.distance_transform_edt).  Mask::dilate is a rectangle of at most 15 x 15; this
+ * is global, and within(d) is the round buffer.  The reference has nothing of the kind.
+ *
+ * The rule.  mask is a row-major raster of cols x rows bytes.  Cell (y, x) is a TARGET iff mask[y * cols + x] != 0.  For every
+ * cell (i, j):
+ *       d2(i, j) = min over targets (y, x) of (i - y)^2 + (j - x)^2          exact integers; 0 on a target
+ * The raster does not wrap: distances are between cell indices.  1 <= cols, rows <= EC_DISTANCE_MAX_SIDE, so
+ * d2 <= 2 * 32767^2 < 2^31.  A cell is VALID iff at least one target exists and d2 <= max_sq (GDAL's MAXDIST, stated on the
+ * squared distance so that it is exact; EC_DISTANCE_UNLIMITED: every cell of a raster with a target).  A valid cell stores, with
+ * mask byte 1,
+ *       out_type == EC_U32:  d2 as a u32
+ *       out_type == EC_F64:  sqrt((double)d2), one correctly rounded IEEE operation
+ * and an invalid cell all-zero bits and mask byte 0; the zero bits are written even where dst_mask_or_null is NULL, as
+ * ec_zonal_broadcast does.  A pure function of the mask: every cell has one right answer whatever the launch shape.
+ *
+ * The algorithm is Meijster, Roerdink and Hesselink's (2000), in integers: a sweep down and up every column, then the lower
+ * envelope of parabolas along every row.  The workspace holds the column distances (u16) and the row scans' stacks.
+ * ---------------------------------------------------------------- */
+enum { EC_DISTANCE_MAX_SIDE = 32768 };
+#define EC_DISTANCE_UNLIMITED 0xFFFFFFFFu
+/* Bytes of the workspace ec_distance wants for a raster of cols x rows cells; 0 for a shape it refuses.  Host only. */
+size_t ec_distance_workspace_bytes(uint64_t cols, uint64_t rows);
+/* The rule above.  Asynchronous, no synchronisation.  With a workspace of the caller's (ec_distance_workspace_bytes(cols, rows)
+ * bytes at a 16-byte-aligned DEVICE address, contents scrap afterwards) there is no allocation and the call is capturable (after
+ * ec_prepare_stream for a foreign stream); with workspace_dev_or_null == NULL the workspace comes from the library's
+ * stream-ordered pool and goes back to it on the same stream, the way ec_zonal_stats_compute gets its own — still asynchronous.
+ * dst_or_null may be NULL when dst_mask_or_null is not: the "within distance" form, in which only the validity bytes are wanted
+ * and no value is ever written.  mask and dst_mask may sit at any byte address, dst is aligned to its cell type.  Writes exactly
+ * cols * rows cells of dst and cols * rows bytes of dst_mask, each where given.
+ * Refused before any device work and without a device, writing nothing, in this order (EC_ERR_ARG unless said otherwise):
+ *   1. cols or rows is 0 or above EC_DISTANCE_MAX_SIDE;
+ *   2. out_type is neither EC_U32 nor EC_F64: EC_ERR_UNSUPPORTED_TYPE for a value that is no cell type at all, EC_ERR_ARG for a
+ *      cell type this entry point does not produce;
+ *   3. mask is NULL;
+ *   4. dst_or_null and dst_mask_or_null are both NULL;
+ *   5. dst is misaligned for out_type;
+ *   6. dst, dst_mask or the workspace overlaps mask or each other.
+ * There is no sharded form: a row-block shard would need every other shard's columns.  Not here either: anisotropic cells (scale
+ * the f64 result), the index of the nearest target, city-block or chessboard metrics, sides above EC_DISTANCE_MAX_SIDE. */
+ec_status ec_distance(const uint8_t *mask, uint64_t cols, uint64_t rows, uint32_t max_sq, ec_dtype out_type,
+                      void *dst_or_null, uint8_t *dst_mask_or_null, void *workspace_dev_or_null, ec_stream stream);
+
+/* ---------------------------------------------------------------- *
  * Test/bench support (not part of the reference surface).
  * ---------------------------------------------------------------- */
 /* x[i] = lo + splitmix64(seed ^ (base + i)) % (hi - lo + 1), t in {EC_U8, EC_U16, EC_F32}
