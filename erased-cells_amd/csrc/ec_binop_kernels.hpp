@@ -48,6 +48,10 @@ __device__ __forceinline__ size_t two_front_tile() {
     const size_t b = blockIdx.x;
     return (b & 1) ? size_t(gridDim.x) - 1 - (b >> 1) : (b >> 1);
 }
+// The same map inside one launch of a job cut into several (split_launch, ec_runtime.hpp): this launch covers the tiles
+// [first, first + gridDim.x).  `first_group(first)` names the workgroup that does a job's once-only work (ragged tails).
+__device__ __forceinline__ size_t two_front_tile(size_t first) { return first + two_front_tile(); }
+__device__ __forceinline__ bool first_group(size_t first) { return first == 0 && blockIdx.x == 0; }
 
 // ---------------------------------------------------------------------------
 // DIRECT variant: one block tile of kBlock*U pairs (2 cells each).  Pointers may sit

@@ -46,6 +46,7 @@ static ec_status launch_binop_pair(const void* l, const void* r, size_t n, doubl
         constexpr unsigned kStatic = kWavesPerBlock * unsigned(Staged<L>::kSlabBytes + Staged<R>::kSlabBytes);
         const int knob = tu.binop_lds_kb.load();
         const unsigned lds = knob >= 0 ? unsigned(knob) << 10 : by_rule ? 32000u - kStatic : 0u;
+        if (const ec_status st = check_groups("binop(lds)", tiles)) return st;
         k_binop_lds<L, R, OP><<<grid_for(tiles), kBlock, lds, s>>>(lp, rp, out, n);
         if (by_rule) lds_rule_launches().fetch_add(1, std::memory_order_relaxed);
         return check_launch(by_rule ? "binop(lds, by rule)" : "binop(lds)");
@@ -53,6 +54,7 @@ static ec_status launch_binop_pair(const void* l, const void* r, size_t n, doubl
     const LoadedStream st[2] = {{l, sizeof(L)}, {r, sizeof(R)}};
     const unsigned head = peel_head(st, 2, n);
     const size_t tiles = (((n - head) >> 1) + size_t(kBlock) * U - 1) / (size_t(kBlock) * U);
+    if (const ec_status st = check_groups("binop", tiles)) return st;
     k_binop_direct<L, R, OP, U><<<grid_for(tiles), kBlock, lds_cap(tuning().binop_lds_kb.load(), sizeof(L) == 8 && sizeof(R) == 8 ? 48 : 0), s>>>(lp, rp, out, n, head | (policy << 8));
     return check_launch("binop(direct)");
 }
@@ -71,6 +73,7 @@ static ec_status launch_masked_pair(const void* l, const uint8_t* lm, const void
     constexpr bool kCanStage = Staged<L>::value || Staged<R>::value;
     if (kCanStage && tu.binop_variant == 1) {
         const size_t tiles = (n / kLdsWaveCells + kWavesPerBlock - 1) / kWavesPerBlock;
+        if (const ec_status st = check_groups("masked_binop(lds)", tiles)) return st;
         k_masked_binop<L, R, OP, U, true><<<grid_for(tiles), kBlock, lds_cap(tu.binop_lds_kb.load(), 0), s>>>(lp, lm, rp, rm, out, om, n, 0u);
         return check_launch("masked_binop(lds)");
     }
@@ -81,6 +84,7 @@ static ec_status launch_masked_pair(const void* l, const uint8_t* lm, const void
     unsigned policy = cache_plan(stream_bytes, 4, n * sizeof(double));
     if (l == r && (policy & 1u)) policy |= 2u;
     if (lm == rm && (policy & 4u)) policy |= 8u;
+    if (const ec_status st = check_groups("masked_binop", tiles)) return st;
     k_masked_binop<L, R, OP, U, false><<<grid_for(tiles), kBlock, 0, s>>>(lp, lm, rp, rm, out, om, n, head | (policy << 8));
     return check_launch("masked_binop(direct)");
 }
@@ -97,6 +101,7 @@ static ec_status launch_scalar(const void* l, double rhs, size_t n, double* out,
     const LoadedStream st[1] = {{l, sizeof(L)}};
     const unsigned head = peel_head(st, 1, n);
     const size_t tiles = (((n - head) >> 1) + size_t(kBlock) * U - 1) / (size_t(kBlock) * U);
+    if (const ec_status st = check_groups("binop_scalar", tiles)) return st;
     const size_t stream_bytes[1] = {n * sizeof(L)};
     const unsigned policy = cache_plan(stream_bytes, 1, n * sizeof(double));
     const unsigned lds = lds_cap(tuning().scalar_lds_kb.load(), sizeof(L) == 8 ? 32 : 0);

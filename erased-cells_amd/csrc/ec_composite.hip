@@ -27,10 +27,9 @@ static ec_status launch_composite(const CompositeArgs& a, hipStream_t s) {
     for (int k = 0; k < a.layers; ++k) aligned = aligned && aligned_to(a.p[k], CPL * sizeof(T)) && (!a.m[k] || aligned_to(a.m[k], CPL));
     if (aligned) {
         const size_t groups = a.n / CPL, tile = size_t(kBlock) * S::U;
-        k_composite<T, OP><<<grid_for((groups + tile - 1) / tile), kBlock, 0, s>>>(a);
-    } else {
-        k_composite_cellwise<T, OP><<<grid_capped((a.n + kBlock - 1) / kBlock, 8), kBlock, 0, s>>>(a);
+        return split_launch((groups + tile - 1) / tile, "composite", [&](size_t first, unsigned grid) { k_composite<T, OP><<<grid, kBlock, 0, s>>>(a, first); });
     }
+    k_composite_cellwise<T, OP><<<grid_capped((a.n + kBlock - 1) / kBlock, 8), kBlock, 0, s>>>(a);
     return check_launch("composite");
 }
 

@@ -127,12 +127,12 @@ __device__ __forceinline__ void composite_cell(const CompositeArgs& a, size_t i)
 }
 
 template <typename T, int OP>
-__global__ __launch_bounds__(kBlock) void k_composite(const CompositeArgs a) {
+__global__ __launch_bounds__(kBlock) void k_composite(const CompositeArgs a, const size_t first_tile) {
     constexpr int U = CompositeShape<T, OP>::U;
     constexpr size_t CPL = CompositeShape<T, OP>::CPL;
     constexpr size_t TILE = size_t(kBlock) * U;
     const size_t ngroups = a.n / CPL;
-    const size_t tile = two_front_tile();  // one workgroup per tile, straight-line
+    const size_t tile = two_front_tile(first_tile);  // one workgroup per tile, straight-line
     const size_t base = tile * TILE + threadIdx.x;
     if (tile * TILE + TILE <= ngroups) {
         composite_groups<T, OP, U>(a, base);
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(kBlock) void k_composite(const CompositeArgs a) {
             if (g < ngroups) composite_groups<T, OP, 1>(a, g);
         }
     }
-    if (blockIdx.x == 0)
+    if (first_group(first_tile))
         for (size_t i = ngroups * CPL + threadIdx.x; i < a.n; i += kBlock) composite_cell<T, OP>(a, i);
 }
 

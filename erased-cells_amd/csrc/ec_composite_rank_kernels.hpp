@@ -203,9 +203,9 @@ __device__ __forceinline__ void rank_group_run(const CompositeRankArgs& a, size_
 }
 
 template <typename T, int KB>
-__global__ __launch_bounds__(kBlock) void k_composite_rank(const CompositeRankArgs a) {
+__global__ __launch_bounds__(kBlock) void k_composite_rank(const CompositeRankArgs a, const size_t first_tile) {
     constexpr size_t G = rank_group(sizeof(T), KB);
-    const size_t first = (two_front_tile() * kBlock + threadIdx.x) * G;  // one workgroup per tile, straight-line
+    const size_t first = (two_front_tile(first_tile) * kBlock + threadIdx.x) * G;  // one workgroup per tile, straight-line
     if (first < a.n) rank_group_run<T, KB, int(G)>(a, first);
 }
 

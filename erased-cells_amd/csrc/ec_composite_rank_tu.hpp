@@ -28,8 +28,7 @@ static ec_status launch_composite_rank(const CompositeRankArgs& a, hipStream_t s
         }
     }
     const size_t groups = (a.n + G - 1) / G;  // the last one may be partial: it is guarded in the kernel
-    k_composite_rank<T, KB><<<grid_for((groups + kBlock - 1) / kBlock), kBlock, 0, s>>>(a);
-    return check_launch("composite_rank");
+    return split_launch((groups + kBlock - 1) / kBlock, "composite_rank", [&](size_t first, unsigned grid) { k_composite_rank<T, KB><<<grid, kBlock, 0, s>>>(a, first); });
 }
 
 // composite_rank_c1 / _c2 / _c4 / _c8 (declared in ec_composite_rank.hip): the launch for a cell type of this width

@@ -155,7 +155,7 @@ static ec_status launch_expr(const ec_dtype* dt, const void* const* p, int32_t n
         default: kern = expr_kernel<8>(cls[1], cls[2], cls[3]); break;
     }
     if (!kern) return set_error(EC_ERR_ARG, "%s: no kernel for stream classes %d %d %d %d", what, cls[0], cls[1], cls[2], cls[3]);
-    launch_stream_tile<kExprU>(kern, ea.head, n, s, ea, out, out_mask, n);
+    if (const ec_status st = launch_stream_tile<kExprU>(what, kern, ea.head, n, s, ea, out, out_mask, n)) return st;
     return check_launch("expr");
 }
 

@@ -156,7 +156,7 @@ ec_status expr_fixed_launch(const ExprArgs& ea, size_t n, double* out, uint8_t* 
         case kFixAffine: kern = fixed_kernel_of<kFixAffine>(c); break;
     }
     if (!kern) return EC_OK;
-    launch_stream_tile<kFixedU>(kern, ea.head, n, s, ea, fm, out, out_mask, n);
+    if (const ec_status st = launch_stream_tile<kFixedU>("expr(built-in)", kern, ea.head, n, s, ea, fm, out, out_mask, n)) return st;
     g_fixed_launches.fetch_add(1, std::memory_order_relaxed);
     *launched = true;
     return EC_OK;

@@ -602,6 +602,7 @@ ec_status expr_jit_launch(const ExprArgs& ea, size_t n, double* out, uint8_t* ou
     } else {
         void* params[] = {&p[0], &p[1], &p[2], &p[3], &c[0], &c[1], &c[2], &c[3], &c[4], &c[5], &c[6], &c[7], &out, &nn, &head,
                           &m[0], &m[1], &m[2], &m[3], &out_mask};
+        if (const ec_status refused = check_groups("expr(compiled)", (npairs + 511) / 512)) return refused;
         const unsigned grid = grid_for((npairs + 511) / 512);
         st = check_hip(hipModuleLaunchKernel(fn, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr), "hipModuleLaunchKernel(ec_expr_jit)");
     }

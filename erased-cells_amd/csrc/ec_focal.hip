@@ -34,17 +34,21 @@ static ec_status focal_args(const char* what, ec_dtype t, const void* src, const
 }
 
 template <typename T, int KIND>
-static ec_status launch_focal(const FocalArgs& a, uint64_t tiles, hipStream_t s) {
-    if (a.src_mask) k_focal<T, true, KIND><<<grid_for(tiles), kBlock, a.lds.bytes, s>>>(a);
-    else k_focal<T, false, KIND><<<grid_for(tiles), kBlock, a.lds.bytes, s>>>(a);
-    return check_launch(KIND == ecf::kSeparableSum ? "focal(sum)" : "focal(min_max)");
+static ec_status launch_focal(FocalArgs a, uint64_t tiles, hipStream_t s) {
+    return split_launch(tiles, KIND == ecf::kSeparableSum ? "focal(sum)" : "focal(min_max)", [&](size_t first, unsigned grid) {
+        a.first_tile = uint32_t(first);  // tiles <= 2^31 - 1 (ecf::refusal)
+        if (a.src_mask) k_focal<T, true, KIND><<<grid, kBlock, a.lds.bytes, s>>>(a);
+        else k_focal<T, false, KIND><<<grid, kBlock, a.lds.bytes, s>>>(a);
+    });
 }
 
 template <typename T>
-static ec_status launch_convolve(const FocalArgs& a, const FocalWeights& w, uint64_t tiles, hipStream_t s) {
-    if (a.src_mask) k_focal_convolve<T, true><<<grid_for(tiles), kBlock, a.lds.bytes, s>>>(a, w);
-    else k_focal_convolve<T, false><<<grid_for(tiles), kBlock, a.lds.bytes, s>>>(a, w);
-    return check_launch("focal(convolve)");
+static ec_status launch_convolve(FocalArgs a, const FocalWeights& w, uint64_t tiles, hipStream_t s) {
+    return split_launch(tiles, "focal(convolve)", [&](size_t first, unsigned grid) {
+        a.first_tile = uint32_t(first);
+        if (a.src_mask) k_focal_convolve<T, true><<<grid, kBlock, a.lds.bytes, s>>>(a, w);
+        else k_focal_convolve<T, false><<<grid, kBlock, a.lds.bytes, s>>>(a, w);
+    });
 }
 
 }  // namespace ecd

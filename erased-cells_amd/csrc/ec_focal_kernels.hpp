@@ -55,6 +55,7 @@ struct FocalArgs {
     uint32_t cacheable;
     uint32_t cellwise_stores;  // "unaligned_vector" is off and a slot of the output can start off a 16-byte boundary
     ecf::Layout lds;
+    uint32_t first_tile = 0;  // this launch covers the tiles [first_tile, first_tile + gridDim.x) of the raster (split_launch, ec_runtime.hpp)
 };
 struct FocalWeights {
     double w[(2 * EC_FOCAL_RADIUS_CAP + 1) * (2 * EC_FOCAL_RADIUS_CAP + 1)];
@@ -109,7 +110,7 @@ __device__ __forceinline__ void focal_stage(const FocalArgs& a, const ecf::Tile&
 }
 
 __device__ __forceinline__ ecf::Tile focal_this_tile(const FocalArgs& a) {
-    const uint32_t tile = uint32_t(two_front_tile()), ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+    const uint32_t tile = uint32_t(two_front_tile(a.first_tile)), ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
     return ecf::tile_at(a.cols, a.rows, a.rx, a.ry, tx, ty, TW, TH);
 }
 

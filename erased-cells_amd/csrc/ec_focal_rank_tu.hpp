@@ -16,9 +16,11 @@
 namespace ecd {
 
 template <typename T, int KB>
-static ec_status launch_focal_rank(const FocalArgs& a, const RankTable& r, uint64_t tiles, hipStream_t s) {
-    k_focal_rank<T, KB><<<grid_for(tiles), kBlock, a.lds.bytes, s>>>(a, r);
-    return check_launch(a.op == kFocalRankPick ? "focal_rank" : "focal_majority");
+static ec_status launch_focal_rank(FocalArgs a, const RankTable& r, uint64_t tiles, hipStream_t s) {
+    return split_launch(tiles, a.op == kFocalRankPick ? "focal_rank" : "focal_majority", [&](size_t first, unsigned grid) {
+        a.first_tile = uint32_t(first);  // tiles <= 2^31 - 1 (ecf::rank_refusal)
+        k_focal_rank<T, KB><<<grid, kBlock, a.lds.bytes, s>>>(a, r);
+    });
 }
 
 // focal_rank_c1 / _c2 / _c4 / _c8 (declared in ec_focal_rank.hip): the launch for a cell type of this width

@@ -31,7 +31,7 @@ static ec_status launch_fused_any(FusedArgs& fa, int nops, size_t n, double* out
         default: kern = fused_any_kernel<8>(cls[1], cls[2], cls[3]); break;
     }
     if (!kern) return set_error(EC_ERR_ARG, "ec_fused: no kernel for load classes %d %d %d %d", cls[0], cls[1], cls[2], cls[3]);
-    launch_stream_tile<kFusedU>(kern, fa.head, n, s, fa, out, out_mask, n);
+    if (const ec_status st = launch_stream_tile<kFusedU>("ec_fused", kern, fa.head, n, s, fa, out, out_mask, n)) return st;
     return check_launch("fused(any)");
 }
 

@@ -22,16 +22,18 @@ static ec_status launch_reclass(const void* src, const uint8_t* mask, size_t n, 
     const bool aligned = aligned_to(src, CPL * sizeof(T)) && aligned_to(dst, CPL * sizeof(W)) && (!mask || aligned_to(mask, CPL)) &&
                          (!dst_mask || aligned_to(dst_mask, CPL));
     const size_t stream_bytes[1] = {n * sizeof(T)};  // the value operand; mask bytes load nt
-    auto launch = [&](auto masked) {
+    auto launch = [&](auto masked) -> ec_status {
         constexpr bool MASKED = decltype(masked)::value;
-        if (aligned)
-            k_reclass<T, W, MASKED, ecr::kU><<<grid_for(ecr::tiles(n, CPL)), kBlock, 0, s>>>(sp, mask, tab, out, dst_mask, n, cache_plan(stream_bytes, 1));
-        else
-            k_reclass_cellwise<T, W, MASKED><<<grid_capped((n + kBlock - 1) / kBlock, 8), kBlock, 0, s>>>(sp, mask, tab, out, dst_mask, n);
+        if (aligned) {
+            const unsigned policy = cache_plan(stream_bytes, 1);
+            return split_launch(ecr::tiles(n, CPL), "reclass", [&](size_t first, unsigned groups) {
+                k_reclass<T, W, MASKED, ecr::kU><<<groups, kBlock, 0, s>>>(sp, mask, tab, out, dst_mask, n, policy, first);
+            });
+        }
+        k_reclass_cellwise<T, W, MASKED><<<grid_capped((n + kBlock - 1) / kBlock, 8), kBlock, 0, s>>>(sp, mask, tab, out, dst_mask, n);
+        return check_launch("reclass");
     };
-    if (mask) launch(std::true_type{});
-    else launch(std::false_type{});
-    return check_launch("reclass");
+    return mask ? launch(std::true_type{}) : launch(std::false_type{});
 }
 
 }  // namespace ecd

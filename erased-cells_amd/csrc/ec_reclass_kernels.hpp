@@ -151,7 +151,7 @@ struct Reclass {
 template <typename T, typename W, bool MASKED, int U>
 __global__ __launch_bounds__(kBlock) void k_reclass(const T* __restrict__ src, const uint8_t* __restrict__ mask,
                                                     const ec_reclass_table* __restrict__ tab, W* __restrict__ dst, uint8_t* __restrict__ dst_mask,
-                                                    size_t n, unsigned cacheable) {
+                                                    size_t n, unsigned cacheable, size_t first_tile) {
     __shared__ ReclassLds<T, W> lds;
     const Reclass<T, W, MASKED> rc(lds, tab, dst_mask != nullptr);
     constexpr int CPL = 16 / max_of<sizeof(T), sizeof(W)>::value;
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(kBlock) void k_reclass(const T* __restrict__ src, c
     using MV = vec<uint8_t, CPL>;
     const size_t ngroups = n / CPL;
     constexpr size_t TILE = size_t(kBlock) * U;
-    const size_t tile = two_front_tile();
+    const size_t tile = two_front_tile(first_tile);
     const size_t base = tile * TILE + threadIdx.x;
     auto store = [&](size_t g, const cells<T, CPL>& x, const cells<uint8_t, CPL>& m) {
         W o[CPL];
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(kBlock) void k_reclass(const T* __restrict__ src, c
             store(g, x, m);
         }
     }
-    if (blockIdx.x == 0)
+    if (first_group(first_tile))
         for (size_t i = ngroups * CPL + threadIdx.x; i < n; i += kBlock) rc.cell(src, mask, dst, dst_mask, i);
 }
 

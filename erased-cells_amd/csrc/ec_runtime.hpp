@@ -11,6 +11,7 @@
 #include <mutex>
 #include <string>
 
+#include "ec_launch_split.hpp"  // kMaxGroups, part
 #include "ec_reduce_plan.hpp"  // kReduceU, kMaxReduceBlocks
 #include "erased_cells.h"
 
@@ -197,10 +198,33 @@ inline ec_status add_mask(const uint8_t* m, int k, const char* what, const uint8
     return EC_OK;
 }
 
-// Element-wise kernels: one workgroup per tile.
+// Element-wise kernels: one workgroup per tile.  A job of more than ecs::kMaxGroups tiles does not fit one launch
+// (ec_launch_split.hpp): its caller has refused it (check_groups) or cut it (split_launch) before it comes here.  The answer for
+// one that comes all the same is 0, a grid the runtime refuses (check_launch then reports it) — never a smaller grid that would
+// run and leave tiles unwritten.
 inline unsigned grid_for(size_t tiles) {
     if (tiles < 1) tiles = 1;
-    return static_cast<unsigned>(tiles < size_t(0x7fffffff) ? tiles : size_t(0x7fffffff));
+    return tiles <= size_t(ecs::kMaxGroups) ? static_cast<unsigned>(tiles) : 0u;
+}
+// The refusal of the streaming families (binops, maps, one-pass trees), before any device work: EC_ERR_ARG and nothing written
+// for a call whose tiles do not fit one launch.
+inline ec_status check_groups(const char* what, size_t tiles) {
+    if (tiles <= size_t(ecs::kMaxGroups)) return EC_OK;
+    return set_error(EC_ERR_ARG, "%s: %zu tiles of %d lanes do not fit one launch (at most %llu workgroups: a grid's work-items are a 32-bit count); "
+                     "run it over shards of the buffer", what, tiles, int(ecs::kLanes), static_cast<unsigned long long>(ecs::kMaxGroups));
+}
+// The launches of a one-workgroup-per-tile job of any size up to the families' 2^31 - 1 tiles: launch(first tile, workgroups) once
+// per part of ecs::part, in order, on the caller's stream.  No allocation, no synchronisation; capturable.
+template <typename F>
+inline ec_status split_launch(size_t tiles, const char* what, F&& launch) {
+    if (tiles < 1) tiles = 1;
+    for (uint64_t k = 0, parts = ecs::launches(tiles); k < parts; ++k) {
+        const ecs::Part p = ecs::part(tiles, k);
+        launch(static_cast<size_t>(p.first), static_cast<unsigned>(p.count));
+        const ec_status st = check_launch(what);
+        if (st != EC_OK) return st;
+    }
+    return EC_OK;
 }
 // Grid-stride kernels (cell-wise fallbacks, reductions): at most bpc workgroups per CU.
 inline unsigned grid_capped(size_t blocks, int bpc) {

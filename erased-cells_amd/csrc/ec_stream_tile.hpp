@@ -150,12 +150,14 @@ __device__ __forceinline__ void stream_tile(const A& a, const void* const (&p)[4
 }
 
 // Launch of a one-pass kernel of U pairs per lane per tile: one workgroup per tile behind the `head` peeled cells, and the LDS the
-// fused_lds_kb knob reserves per workgroup (an occupancy cap: profiles/r04/fused_caps.md).
+// fused_lds_kb knob reserves per workgroup (an occupancy cap: profiles/r04/fused_caps.md).  A job whose tiles do not fit one launch
+// is refused before anything is launched (check_groups); EC_OK means "launched": the caller reads the launch's own status.
 template <int U, typename... KArgs, typename... Args>
-void launch_stream_tile(void (*kern)(KArgs...), unsigned head, size_t n, hipStream_t s, const Args&... args) {
-    const size_t per_tile = size_t(kBlock) * U;
-    const unsigned grid = grid_for((((n - head) >> 1) + per_tile - 1) / per_tile);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), static_cast<unsigned>(tuning().fused_lds_kb.load()) << 10, s, args...);
+ec_status launch_stream_tile(const char* what, void (*kern)(KArgs...), unsigned head, size_t n, hipStream_t s, const Args&... args) {
+    const size_t per_tile = size_t(kBlock) * U, tiles = (((n - head) >> 1) + per_tile - 1) / per_tile;
+    if (const ec_status st = check_groups(what, tiles)) return st;
+    hipLaunchKernelGGL(kern, dim3(grid_for(tiles)), dim3(kBlock), static_cast<unsigned>(tuning().fused_lds_kb.load()) << 10, s, args...);
+    return EC_OK;
 }
 
 }  // namespace ecd

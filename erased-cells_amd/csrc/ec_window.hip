@@ -43,8 +43,8 @@ static ec_status launch_window(int kind, const WindowArgs& args, const WindowAxi
         return check_launch("window(cell-wise)");
     }
     const uint64_t slots = (a.g.n + (16 / W) - 1) / (16 / W), per_tile = uint64_t(kBlock) * kWindowU;
+    if (const ec_status st = check_groups("window", (slots + per_tile - 1) / per_tile)) return st;  // a window of 256 GiB
     const unsigned grid = grid_for((slots + per_tile - 1) / per_tile);
-    if (uint64_t(grid) * per_tile < slots) return set_error(EC_ERR_ARG, "window: more than 2^31 tiles");
     if (ax) k_window_nearest<W, MASKED><<<grid, kBlock, 0, s>>>(a, *ax, *ay);
     else if (kind == kWinPut) k_window_put<W, MASKED><<<grid, kBlock, 0, s>>>(a);
     else k_window_copy<W, MASKED><<<grid, kBlock, 0, s>>>(a);

@@ -50,8 +50,10 @@ static ec_status launch_resample(const ResampleArgs& args, uint64_t win_cells, h
     ResampleArgs a = args;
     const size_t bytes[2] = {win_cells * W, MASKED ? win_cells : 0};  // the streams that are loaded: the window's cells and mask bytes
     a.w.cacheable = cache_plan(bytes, 2);
-    k_window_resample<T, MASKED><<<grid_for(resample_tiles(a.w.g.n, W)), kBlock, 0, s>>>(a);  // at most 2^31 - 1 tiles: checked by the caller
-    return check_launch("window(resample)");
+    return split_launch(resample_tiles(a.w.g.n, W), "window(resample)", [&](size_t first, unsigned grid) {  // at most 2^31 - 1 tiles: checked by the caller
+        a.first_tile = first;
+        k_window_resample<T, MASKED><<<grid, kBlock, 0, s>>>(a);
+    });
 }
 
 static ec_status dispatch_resample(ec_dtype t, const ResampleArgs& a, uint64_t win_cells, hipStream_t s) {

@@ -123,6 +123,7 @@ struct ResampleArgs {
     WindowArgs w;
     ResampleAxis ax, ay;
     unsigned cellwise_stores;
+    uint64_t first_tile;  // this launch covers the tiles [first_tile, first_tile + gridDim.x) of the output (split_launch, ec_runtime.hpp)
 };
 
 template <typename T, bool MASKED>
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void k_window_resample(ResampleArgs a) {
     using C = typename width_cell<W>::type;
     using M = typename byte_words<CPL>::type;  // the mask bytes of one value slot
     const WindowGeom& g = a.w.g;
-    const uint64_t first = uint64_t(two_front_tile()) * SPAN;
+    const uint64_t first = uint64_t(two_front_tile(a.first_tile)) * SPAN;
     if (first >= g.n) return;
     const uint64_t row0 = first / g.w, col0 = first - row0 * g.w;  // wave-uniform, once per workgroup
     const T* __restrict__ win = static_cast<const T*>(a.w.in) + g.origin;

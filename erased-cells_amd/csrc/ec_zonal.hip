@@ -112,14 +112,16 @@ static ec_status launch_broadcast(const void* zones, const void* table, size_t n
     const W* tab = static_cast<const W*>(table);
     W* out = static_cast<W*>(dst);
     const bool aligned = aligned_to(zones, CPL * sizeof(ZT)) && aligned_to(dst, CPL * sizeof(W)) && (!dst_mask || aligned_to(dst_mask, CPL));
-    auto launch = [&](auto maskout) {
+    auto launch = [&](auto maskout) -> ec_status {
         constexpr bool MASKOUT = decltype(maskout)::value;
-        if (aligned) k_zonal_broadcast<W, ZT, MASKOUT, ecz::kBroadcastU><<<grid_for(ecz::broadcast_tiles(n, CPL)), kBlock, 0, s>>>(zp, tab, n_zones, out, dst_mask, n);
-        else k_zonal_broadcast_cellwise<W, ZT, MASKOUT><<<grid_capped((n + kBlock - 1) / kBlock, 8), kBlock, 0, s>>>(zp, tab, n_zones, out, dst_mask, n);
+        if (aligned)
+            return split_launch(ecz::broadcast_tiles(n, CPL), "zonal_broadcast", [&](size_t first, unsigned grid) {
+                k_zonal_broadcast<W, ZT, MASKOUT, ecz::kBroadcastU><<<grid, kBlock, 0, s>>>(zp, tab, n_zones, out, dst_mask, n, first);
+            });
+        k_zonal_broadcast_cellwise<W, ZT, MASKOUT><<<grid_capped((n + kBlock - 1) / kBlock, 8), kBlock, 0, s>>>(zp, tab, n_zones, out, dst_mask, n);
+        return check_launch("zonal_broadcast");
     };
-    if (dst_mask) launch(std::true_type{});
-    else launch(std::false_type{});
-    return check_launch("zonal_broadcast");
+    return dst_mask ? launch(std::true_type{}) : launch(std::false_type{});
 }
 
 }  // namespace ecd

@@ -353,7 +353,7 @@ __global__ __launch_bounds__(kStatsFinalizeBlock) void k_zonal_finalize(const Mo
 // loaded nt like every other access: the L2 serves the workgroups' re-reads all the same).
 template <typename W, typename ZT, bool MASKOUT, int U>
 __global__ __launch_bounds__(kBlock) void k_zonal_broadcast(const ZT* __restrict__ zones, const W* __restrict__ table, int32_t n_zones,
-                                                            W* __restrict__ dst, uint8_t* __restrict__ dst_mask, size_t n) {
+                                                            W* __restrict__ dst, uint8_t* __restrict__ dst_mask, size_t n, size_t first_tile) {
     __shared__ W tab[ecz::kMaxZones];
     for (int z = threadIdx.x; z < n_zones; z += kBlock) tab[z] = ld_cell(table + z);
     __syncthreads();
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void k_zonal_broadcast(const ZT* __restrict
     using MV = vec<uint8_t, CPL>;
     const size_t ngroups = n / CPL;
     constexpr size_t TILE = size_t(kBlock) * U;
-    const size_t base = two_front_tile() * TILE + threadIdx.x;
+    const size_t base = two_front_tile(first_tile) * TILE + threadIdx.x;
     cells<ZT, CPL> z[U] = {};
 #pragma unroll
     for (int j = 0; j < U; ++j) {
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(kBlock) void k_zonal_broadcast(const ZT* __restrict
         nt_store(o, reinterpret_cast<DV*>(dst) + g);
         if constexpr (MASKOUT) mask_store(m, reinterpret_cast<MV*>(dst_mask) + g);
     }
-    if (blockIdx.x == 0)
+    if (first_group(first_tile))
         for (size_t i = ngroups * CPL + threadIdx.x; i < n; i += kBlock) {
             const int32_t zk = zone_id(ld_cell(zones + i));
             const bool ok = zone_in_range(zk, n_zones);

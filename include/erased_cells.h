@@ -153,6 +153,14 @@ ec_status ec_stream_sync(ec_stream s);
  * truncation of src/buffer.rs:327.  n == 0 is a no-op.  Every element-wise entry point of this header writes exactly
  * `n` cells of each of its outputs and no byte in front of or behind them, wherever the output sits (any cell offset:
  * an f64 output at 8 mod 16, a mask at any byte); operands are not written (tests/test_gpu_output_bounds.py).
+ * The size one call may cover: the streaming entry points — ec_binop, ec_binop_scalar, ec_masked_binop, ec_neg, ec_convert,
+ * ec_fill, ec_fused / ec_masked_fused, ec_expr / ec_masked_expr, the ec_mask_* maps, ec_compare / ec_select, ec_cast /
+ * ec_cast_scaled and ec_window's copies — run one workgroup of 256 lanes per tile in ONE launch, and a launch holds at most
+ * 2^24 - 1 = 16 777 215 workgroups (a grid's work-items are a 32-bit count).  A call that needs more — 64 GiB or more of one
+ * stream: 2^34 cells for a binop or a one-pass tree, 2^37 bytes of a map's widest stream — is refused before any device work:
+ * EC_ERR_ARG, nothing written, the message names the limit.  Run it over shards of the buffer.  (The families documented with
+ * "more than 2^31 - 1 tiles" — focal, focal_rank, composite, composite_rank, reclass, zonal broadcast, resample — cut a larger job
+ * into several launches themselves and keep that limit.)
  * ---------------------------------------------------------------- */
 /* impl {Add,Sub,Mul,Div} for &CellBuffer — src/buffer.rs:324-329 */
 ec_status ec_binop(ec_op op, ec_dtype lt, const void *l, ec_dtype rt, const void *r,
