@@ -1,11 +1,9 @@
 // ec_composite.hip — ec_composite (include/erased_cells.h): one raster from a stack of K co-registered layers, per cell the first
-// or last valid layer, the least or greatest valid cell, or the sum or mean of the valid cells.  The refusals (before any device
-// work and before the library asks for a device) and the launches of k_composite / k_composite_cellwise
+// or last valid layer, the least or greatest valid cell, or the sum or mean of the valid cells.  The refusals (the stack's are ecs::*_refusal,
+// ec_stack_plan.hpp; all before any device work and before the library asks for a device) and the launches of k_composite / k_composite_cellwise
 // (ec_composite_kernels.hpp).  A translation unit of its own, as the moving windows have: its kernels (FIRST and LAST by cell
 // width, MIN, MAX and SUM by cell type, each as a tile kernel and a cell-wise one) compile beside the others.
 #include <hip/hip_runtime.h>
-
-#include <cstring>
 
 #include "ec_composite_kernels.hpp"
 #include "ec_dispatch.hpp"
@@ -23,9 +21,7 @@ template <typename T, int OP>
 static ec_status launch_composite(const CompositeArgs& a, hipStream_t s) {
     using S = CompositeShape<T, OP>;
     constexpr size_t CPL = S::CPL;
-    bool aligned = aligned_to(a.dst, CPL * sizeof(typename S::R)) && (!a.dst_mask || aligned_to(a.dst_mask, CPL)) && (!a.aux || aligned_to(a.aux, CPL));
-    for (int k = 0; k < a.layers; ++k) aligned = aligned && aligned_to(a.p[k], CPL * sizeof(T)) && (!a.m[k] || aligned_to(a.m[k], CPL));
-    if (aligned) {
+    if (tuning().unaligned_vector || ecs::stack_aligned(a, CPL, sizeof(T), sizeof(typename S::R))) {
         const size_t groups = a.n / CPL, tile = size_t(kBlock) * S::U;
         return split_launch((groups + tile - 1) / tile, "composite", [&](size_t first, unsigned grid) { k_composite<T, OP><<<grid, kBlock, 0, s>>>(a, first); });
     }
@@ -60,45 +56,20 @@ extern "C" ec_dtype ec_composite_result_type(int32_t op, ec_dtype t) {
 extern "C" ec_status ec_composite(int32_t op, ec_dtype t, const void* const* layers, const uint8_t* const* masks_or_null, int32_t n_layers, size_t n,
                                   uint32_t min_count, void* dst, uint8_t* dst_mask_or_null, uint8_t* aux_or_null, ec_stream stream) {
     if (!valid_composite_op(op)) return set_error(EC_ERR_ARG, "ec_composite: operation %d is not an ec_composite_op (0..5)", int(op));
-    if (n_layers < 1 || n_layers > kCompositeMaxLayers)
-        return set_error(EC_ERR_ARG, "ec_composite: %d layers, not within 1 .. EC_COMPOSITE_MAX_LAYERS (%d)", int(n_layers), kCompositeMaxLayers);
-    if (min_count < 1 || min_count > uint32_t(n_layers))
-        return set_error(EC_ERR_ARG, "ec_composite: min_count %u is not within 1 .. %d, the number of layers", min_count, int(n_layers));
+    ecs::Message why;
+    if (ecs::count_refusal(why, "ec_composite", n_layers) || ecs::min_count_refusal(why, "ec_composite", min_count, n_layers))
+        return set_error(EC_ERR_ARG, "%s", why);
     if (!ecl::valid(t)) return set_error(EC_ERR_UNSUPPORTED_TYPE, "ec_composite: bad dtype %d", int(t));
     if (n == 0) return EC_OK;
-    if (!layers || !dst) return set_error(EC_ERR_ARG, "ec_composite: null pointer");
-    bool masked = false;
-    for (int k = 0; k < n_layers; ++k) {
-        if (!layers[k]) return set_error(EC_ERR_ARG, "ec_composite: layer %d is a null pointer", k);
-        masked = masked || (masks_or_null && masks_or_null[k]);
-    }
-    if (masked && !dst_mask_or_null) return set_error(EC_ERR_ARG, "ec_composite: a layer has a mask, so the result needs dst_mask");
     size_t cpl, u;
     composite_tile_shape(op, ecl::size_of(t), &cpl, &u);
-    if ((n / cpl + size_t(kBlock) * u - 1) / (size_t(kBlock) * u) > size_t(0x7fffffff))
-        return set_error(EC_ERR_ARG, "ec_composite: %zu cells are more than 2^31 - 1 tiles", n);
-    for (int k = 0; k < n_layers; ++k)
-        if (layers[k] == dst) return set_error(EC_ERR_ARG, "ec_composite: dst is layer %d (the operation is not in-place)", k);
-    for (int k = 0; k < n_layers; ++k) {
-        const uint8_t* m = masks_or_null ? masks_or_null[k] : nullptr;
-        if (m && (m == dst_mask_or_null || m == aux_or_null)) return set_error(EC_ERR_ARG, "ec_composite: dst_mask or aux is the mask of layer %d", k);
-    }
-    if (dst_mask_or_null && dst_mask_or_null == dst) return set_error(EC_ERR_ARG, "ec_composite: dst_mask is dst");
-    if (aux_or_null && (aux_or_null == dst || aux_or_null == dst_mask_or_null)) return set_error(EC_ERR_ARG, "ec_composite: aux is dst or dst_mask");
+    const size_t tiles = (n / cpl + size_t(kBlock) * u - 1) / (size_t(kBlock) * u);
+    if (ecs::pointer_refusal(why, "ec_composite", layers, masks_or_null, n_layers, n, tiles, dst, dst_mask_or_null, aux_or_null))
+        return set_error(EC_ERR_ARG, "%s", why);
     const ec_status st = ensure_ready();
     if (st != EC_OK) return st;
     CompositeArgs a;
-    memset(&a, 0, sizeof a);
-    for (int k = 0; k < n_layers; ++k) {  // read now: the caller's arrays may go when the call returns
-        a.p[k] = layers[k];
-        a.m[k] = masks_or_null ? masks_or_null[k] : nullptr;
-    }
-    a.dst = dst;
-    a.dst_mask = dst_mask_or_null;
-    a.aux = aux_or_null;
-    a.n = n;
-    a.layers = n_layers;
-    a.min_count = min_count;
+    ecs::fill(&a, layers, masks_or_null, n_layers, n, min_count, dst, dst_mask_or_null, aux_or_null);
     a.mean = op == kCompositeMean;
     return dispatch_composite(op, t, a, S(stream));
 }

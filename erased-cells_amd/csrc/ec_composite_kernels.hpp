@@ -17,22 +17,17 @@
 
 #include "ec_composite_cell.hpp"
 #include "ec_map_kernels.hpp"
+#include "ec_stack_plan.hpp"
 
 namespace ecd {
 
 constexpr int kCompositeBatch = 4;  // layers whose loads are in flight together
 
-struct CompositeArgs {
-    const void* p[kCompositeMaxLayers];
-    const uint8_t* m[kCompositeMaxLayers];  // null: every cell of the layer is valid
-    void* dst;
-    uint8_t* dst_mask;  // may be null
-    uint8_t* aux;       // may be null
-    size_t n;
-    int32_t layers;
-    uint32_t min_count;
+struct CompositeArgs : ecs::StackArgs {  // the stack (ec_stack_plan.hpp), then this family's own
     uint32_t mean;
 };
+static_assert(ecs::kMaxLayers == kCompositeMaxLayers && sizeof(CompositeArgs) == 1072 && offsetof(CompositeArgs, mean) == sizeof(ecs::StackArgs),
+              "the kernels read the block at constant offsets: its layout is part of them");
 
 // groups per lane per tile: the host's tile count and the kernels agree through this
 constexpr int composite_u(bool sums, size_t cell_bytes) { return sums ? 2 : cell_bytes == 1 ? 1 : 2; }

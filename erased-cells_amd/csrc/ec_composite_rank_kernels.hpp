@@ -16,20 +16,15 @@
 
 #include "ec_composite_rank_cell.hpp"
 #include "ec_map_kernels.hpp"
+#include "ec_stack_plan.hpp"
 
 namespace ecd {
 
-struct CompositeRankArgs {
-    const void* p[kCompositeMaxLayers];
-    const uint8_t* m[kCompositeMaxLayers];  // null: every cell of the layer is valid
-    void* dst;
-    uint8_t* dst_mask;  // may be null
-    uint8_t* aux;       // may be null
-    size_t n;
-    int32_t layers;
-    uint32_t min_count;
+struct CompositeRankArgs : ecs::StackArgs {  // the stack (ec_stack_plan.hpp), then this family's own
     RankTable rank;  // r(c), c = 1 .. 64
 };
+static_assert(ecs::kMaxLayers == kCompositeMaxLayers && sizeof(CompositeRankArgs) == 1328 && offsetof(CompositeRankArgs, rank) == sizeof(ecs::StackArgs),
+              "the kernels read the block at constant offsets: its layout is part of them");
 
 // registers one word takes
 constexpr int rank_word_regs(size_t cell_bytes) { return cell_bytes <= 2 ? 1 : cell_bytes == 4 ? 2 : 3; }

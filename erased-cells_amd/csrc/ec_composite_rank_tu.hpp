@@ -19,10 +19,8 @@ namespace ecd {
 template <typename T, int KB>
 static ec_status launch_composite_rank(const CompositeRankArgs& a, hipStream_t s) {
     constexpr size_t G = rank_group(sizeof(T), KB);
-    bool aligned = aligned_to(a.dst, G * sizeof(T)) && (!a.dst_mask || aligned_to(a.dst_mask, G)) && (!a.aux || aligned_to(a.aux, G));
-    for (int k = 0; k < a.layers; ++k) aligned = aligned && aligned_to(a.p[k], G * sizeof(T)) && (!a.m[k] || aligned_to(a.m[k], G));
     if constexpr (G > 1) {  // a group of one cell is aligned wherever a cell is: those buckets have no cell-wise kernel
-        if (!aligned) {
+        if (!(tuning().unaligned_vector || ecs::stack_aligned(a, G, sizeof(T), sizeof(T)))) {
             k_composite_rank_cellwise<T, KB><<<grid_capped((a.n + kBlock - 1) / kBlock, 8), kBlock, 0, s>>>(a);
             return check_launch("composite_rank");
         }

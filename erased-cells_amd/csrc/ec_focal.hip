@@ -1,7 +1,8 @@
 // ec_focal.hip — ec_focal and ec_focal_convolve (include/erased_cells.h): moving-window sum, mean, minimum, maximum and weighted sum
 // of a resident raster.  The refusals (ecf::refusal, ec_focal_plan.hpp: before any device work and before the library asks for a
-// device) and the launches of k_focal / k_focal_convolve (ec_focal_kernels.hpp).  A translation unit of its own, as the windows have:
-// its sixty kernels (ten cell types x masked or not x sum-mean, min-max, convolve) compile beside the others.
+// device), the launch arguments of every moving window (focal_args: ec_focal_rank.hip calls it too) and the launches of k_focal /
+// k_focal_convolve (ec_focal_kernels.hpp).  A translation unit of its own, as the windows have: its sixty kernels (ten cell types x
+// masked or not x sum-mean, min-max, convolve) compile beside the others.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -12,19 +13,18 @@
 
 namespace ecd {
 
-// what both entry points do after their refusals: the launch arguments but for `op`, or a status that ends the call (*done)
-static ec_status focal_args(const char* what, ec_dtype t, const void* src, const uint8_t* src_mask, uint64_t cols, uint64_t rows, uint32_t rx,
-                            uint32_t ry, uint32_t flags, void* dst, uint8_t* dst_mask, int kind, const ecf::Grid& g,
-                            FocalArgs* a, bool* done) {
+// declared in ec_focal_kernels.hpp.  `lds` is the stage for cells of ecl::size_of(t) bytes — of no bytes for a bad dtype, which is
+// refused here before anything reads it.
+ec_status focal_args(const char* what, ec_dtype t, const void* src, const uint8_t* src_mask, uint64_t cols, uint64_t rows, uint32_t rx, uint32_t ry,
+                     uint32_t op, uint32_t flags, void* dst, uint8_t* dst_mask, const ecf::Layout& lds, const ecf::Grid& g, FocalArgs* a, bool* done) {
     *done = true;
-    const size_t W = ecl::with_cell_type(t, [](auto c) { return sizeof(ecl::cell_t<decltype(c)>); }, size_t(0));
-    if (W == 0) return set_error(EC_ERR_UNSUPPORTED_TYPE, "%s: bad dtype %d", what, int(t));
+    if (!ecl::valid(t)) return set_error(EC_ERR_UNSUPPORTED_TYPE, "%s: bad dtype %d", what, int(t));
     if (g.tiles == 0) return EC_OK;  // an empty raster
     const ec_status st = ensure_ready();
     if (st != EC_OK) return st;
     *done = false;
-    *a = FocalArgs{src, dst, src_mask, dst_mask, cols, rows, uint32_t(g.tiles_x), rx, ry, 0u, flags, 0u, 0u, ecf::layout_of(uint32_t(W), src_mask != nullptr, kind, rx, ry, TW, TH)};
-    const size_t bytes[2] = {size_t(cols * rows) * W, src_mask ? size_t(cols * rows) : 0};  // the streams that are loaded
+    *a = FocalArgs{src, dst, src_mask, dst_mask, cols, rows, uint32_t(g.tiles_x), rx, ry, op, flags, 0u, 0u, lds};
+    const size_t bytes[2] = {size_t(cols * rows) * ecl::size_of(t), src_mask ? size_t(cols * rows) : 0};  // the streams that are loaded
     a->cacheable = cache_plan(bytes, 2);
     // a slot starts TW-aligned in its row, so every slot of the values and of the mask bytes is 16-byte aligned when the pointers
     // are and a row is a multiple of 16 cells
@@ -68,10 +68,9 @@ extern "C" ec_status ec_focal(int32_t op, ec_dtype t, const void* src, const uin
     const bool sum = op == EC_FOCAL_SUM || op == EC_FOCAL_MEAN;
     FocalArgs a;
     bool done;
-    const ec_status st = focal_args("ec_focal", t, src, src_mask_or_null, cols, rows, rx, ry, flags, dst, dst_mask_or_null,
-                                    sum ? ecf::kSeparableSum : ecf::kSeparableMinMax, g, &a, &done);
+    const ecf::Layout lds = ecf::layout_of(uint32_t(ecl::size_of(t)), src_mask_or_null != nullptr, sum ? ecf::kSeparableSum : ecf::kSeparableMinMax, rx, ry, TW, TH);
+    const ec_status st = focal_args("ec_focal", t, src, src_mask_or_null, cols, rows, rx, ry, uint32_t(op), flags, dst, dst_mask_or_null, lds, g, &a, &done);
     if (done) return st;
-    a.op = uint32_t(op);
     return ecl::with_cell_type(t, [&](auto c) {
         using T = ecl::cell_t<decltype(c)>;
         return sum ? launch_focal<T, ecf::kSeparableSum>(a, g.tiles, S(stream)) : launch_focal<T, ecf::kSeparableMinMax>(a, g.tiles, S(stream));
@@ -86,7 +85,8 @@ extern "C" ec_status ec_focal_convolve(ec_dtype t, const void* src, const uint8_
         return set_error(EC_ERR_ARG, "ec_focal_convolve: %s", why);
     FocalArgs a;
     bool done;
-    const ec_status st = focal_args("ec_focal_convolve", t, src, src_mask_or_null, cols, rows, rx, ry, flags, dst, dst_mask_or_null, ecf::kConvolve, g, &a, &done);
+    const ecf::Layout lds = ecf::layout_of(uint32_t(ecl::size_of(t)), src_mask_or_null != nullptr, ecf::kConvolve, rx, ry, TW, TH);
+    const ec_status st = focal_args("ec_focal_convolve", t, src, src_mask_or_null, cols, rows, rx, ry, 0u, flags, dst, dst_mask_or_null, lds, g, &a, &done);
     if (done) return st;
     FocalWeights w;
     memset(&w, 0, sizeof w);

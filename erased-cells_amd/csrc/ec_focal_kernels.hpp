@@ -57,6 +57,10 @@ struct FocalArgs {
     ecf::Layout lds;
     uint32_t first_tile = 0;  // this launch covers the tiles [first_tile, first_tile + gridDim.x) of the raster (split_launch, ec_runtime.hpp)
 };
+// What every moving-window entry point does between its refusals and its dispatch (ec_focal.hip; ec_focal_rank.hip calls it too): the
+// dtype, the empty raster, the device, then *a with its cache plan and store form — or a status that ends the call (*done).
+ec_status focal_args(const char* what, ec_dtype t, const void* src, const uint8_t* src_mask, uint64_t cols, uint64_t rows, uint32_t rx, uint32_t ry,
+                     uint32_t op, uint32_t flags, void* dst, uint8_t* dst_mask, const ecf::Layout& lds, const ecf::Grid& g, FocalArgs* a, bool* done);
 struct FocalWeights {
     double w[(2 * EC_FOCAL_RADIUS_CAP + 1) * (2 * EC_FOCAL_RADIUS_CAP + 1)];
 };

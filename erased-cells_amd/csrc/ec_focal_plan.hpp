@@ -84,6 +84,22 @@ struct Grid {
     uint64_t tiles_x, tiles_y, tiles;
 };
 
+// The refusals every moving window ends on, behind its own: the output mask, the raster's size, the not-in-place rules and the tile
+// grid.  Fills *g (zeroes before) for a call that passes; an empty raster passes with g->tiles == 0.
+inline const char* raster_refusal(const void* src, const void* dst, const void* src_mask, const void* dst_mask, uint64_t cols, uint64_t rows,
+                                  uint32_t flags, uint32_t tw, uint32_t th, Grid* g) {
+    if (!dst_mask && (src_mask || (flags & kFlagWhole))) return "dst_mask is NULL where cells can be invalid (a source mask, or EC_FOCAL_WHOLE)";
+    if (cols != 0 && rows > UINT64_MAX / cols) return "cols * rows overflows 64 bits";
+    if (dst == src) return "dst == src: the operation is not in-place";
+    if (dst_mask && dst_mask == src_mask) return "dst_mask == src_mask: the operation is not in-place";
+    if (cols == 0 || rows == 0) return nullptr;
+    g->tiles_x = ceil_div(cols, tw);
+    g->tiles_y = ceil_div(rows, th);
+    if (g->tiles_y > kMaxTiles / g->tiles_x) return "more than 2^31 - 1 tiles";  // tiles_x >= 1; no overflow: the product is never formed
+    g->tiles = g->tiles_x * g->tiles_y;
+    return nullptr;
+}
+
 // Why a call is refused (EC_ERR_ARG), or null; fills *g for a call that is not.  `op` is looked at for ec_focal (convolve false),
 // `weights` for ec_focal_convolve.  An empty raster passes with g->tiles == 0.
 inline const char* refusal(bool convolve, int32_t op, const void* src, const void* dst, const void* weights, const void* src_mask,
@@ -96,16 +112,7 @@ inline const char* refusal(bool convolve, int32_t op, const void* src, const voi
     if (flags & ~(kFlagWhole | kFlagNormalize)) return "unknown flag bits";
     if (!convolve && (flags & kFlagNormalize)) return "EC_FOCAL_NORMALIZE is ec_focal_convolve's";
     if (rx > kRadiusCap || ry > kRadiusCap) return "a radius above EC_FOCAL_RADIUS_CAP (7)";
-    if (!dst_mask && (src_mask || (flags & kFlagWhole))) return "dst_mask is NULL where cells can be invalid (a source mask, or EC_FOCAL_WHOLE)";
-    if (cols != 0 && rows > UINT64_MAX / cols) return "cols * rows overflows 64 bits";
-    if (dst == src) return "dst == src: the operation is not in-place";
-    if (dst_mask && dst_mask == src_mask) return "dst_mask == src_mask: the operation is not in-place";
-    if (cols == 0 || rows == 0) return nullptr;
-    g->tiles_x = ceil_div(cols, tw);
-    g->tiles_y = ceil_div(rows, th);
-    if (g->tiles_y > kMaxTiles / g->tiles_x) return "more than 2^31 - 1 tiles";  // tiles_x >= 1; no overflow: the product is never formed
-    g->tiles = g->tiles_x * g->tiles_y;
-    return nullptr;
+    return raster_refusal(src, dst, src_mask, dst_mask, cols, rows, flags, tw, th, g);
 }
 
 // ---- ec_focal_rank / ec_focal_majority: the order statistics of a footprint (ec_focal_rank_kernels.hpp)
@@ -122,16 +129,7 @@ inline const char* rank_refusal(bool rank, const void* src, const void* dst, con
     if (flags & ~kFlagWhole) return "unknown flag bits";
     if (rx > kRadiusCap || ry > kRadiusCap) return "a radius above EC_FOCAL_RADIUS_CAP (7)";
     if ((2 * rx + 1) * (2 * ry + 1) > kRankMaxTaps) return "more than EC_FOCAL_RANK_MAX_TAPS (64) taps in the footprint";
-    if (!dst_mask && (src_mask || (flags & kFlagWhole))) return "dst_mask is NULL where cells can be invalid (a source mask, or EC_FOCAL_WHOLE)";
-    if (cols != 0 && rows > UINT64_MAX / cols) return "cols * rows overflows 64 bits";
-    if (dst == src) return "dst == src: the operation is not in-place";
-    if (dst_mask && dst_mask == src_mask) return "dst_mask == src_mask: the operation is not in-place";
-    if (cols != 0 && rows != 0) {
-        g->tiles_x = ceil_div(cols, tw);
-        g->tiles_y = ceil_div(rows, th);
-        if (g->tiles_y > kMaxTiles / g->tiles_x) return "more than 2^31 - 1 tiles";
-        g->tiles = g->tiles_x * g->tiles_y;
-    }
+    if (const char* why = raster_refusal(src, dst, src_mask, dst_mask, cols, rows, flags, tw, th, g)) return why;
     if (rank) {
         if (den < 1 || den > kRankMaxDen || num > den) {
             g->tiles = 0;

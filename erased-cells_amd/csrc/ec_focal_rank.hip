@@ -17,23 +17,16 @@ ec_status focal_rank_c2(int t, const FocalArgs& a, const RankTable& r, uint64_t 
 ec_status focal_rank_c4(int t, const FocalArgs& a, const RankTable& r, uint64_t tiles, hipStream_t s);
 ec_status focal_rank_c8(int t, const FocalArgs& a, const RankTable& r, uint64_t tiles, hipStream_t s);
 
-// both entry points behind their refusals: the launch arguments as ec_focal makes them (ec_focal.hip, focal_args), then the launch
+// both entry points behind their refusals: the launch arguments (focal_args, ec_focal.hip), then the launch
 static ec_status focal_rank_run(const char* what, uint32_t op, ec_dtype t, const void* src, const uint8_t* src_mask, uint64_t cols, uint64_t rows,
                                 uint32_t rx, uint32_t ry, const RankTable& rank, uint32_t flags, void* dst, uint8_t* dst_mask, const ecf::Grid& g,
                                 hipStream_t s) {
-    if (!ecl::valid(t)) return set_error(EC_ERR_UNSUPPORTED_TYPE, "%s: bad dtype %d", what, int(t));
-    if (g.tiles == 0) return EC_OK;  // an empty raster
-    const ec_status st = ensure_ready();
-    if (st != EC_OK) return st;
     const size_t W = ecl::size_of(t);
-    FocalArgs a{src, dst, src_mask, dst_mask, cols, rows, uint32_t(g.tiles_x), rx, ry, op, flags, 0u, 0u,
-                ecf::rank_layout_of(uint32_t(W), src_mask != nullptr, rx, ry, TW, TH)};
-    const size_t bytes[2] = {size_t(cols * rows) * W, src_mask ? size_t(cols * rows) : 0};  // the streams that are loaded
-    a.cacheable = cache_plan(bytes, 2);
-    // a slot starts TW-aligned in its row, so every slot of the values and of the mask bytes is 16-byte aligned when the pointers
-    // are and a row is a multiple of 16 cells
-    const bool aligned = reinterpret_cast<uintptr_t>(dst) % 16 == 0 && reinterpret_cast<uintptr_t>(dst_mask) % 16 == 0 && cols % 16 == 0;
-    a.cellwise_stores = !(tuning().unaligned_vector || aligned);
+    FocalArgs a;
+    bool done;
+    const ec_status st = focal_args(what, t, src, src_mask, cols, rows, rx, ry, op, flags, dst, dst_mask,
+                                    ecf::rank_layout_of(uint32_t(W), src_mask != nullptr, rx, ry, TW, TH), g, &a, &done);
+    if (done) return st;
     switch (W) {
         case 1: return focal_rank_c1(t, a, rank, g.tiles, s);
         case 2: return focal_rank_c2(t, a, rank, g.tiles, s);

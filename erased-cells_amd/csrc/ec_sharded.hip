@@ -615,15 +615,13 @@ extern "C" ec_status ec_sharded_reclass(ec_shard_group* g, ec_dtype t, const voi
     });
 }
 
-extern "C" ec_status ec_sharded_composite(ec_shard_group* g, int32_t op, ec_dtype t, const void* const* const* layers,
-                                          const uint8_t* const* const* masks_or_null, int32_t n_layers, const size_t* n, uint32_t min_count,
-                                          void* const* dst, uint8_t* const* dst_mask_or_null, uint8_t* const* aux_or_null) {
-    const char* what = "ec_sharded_composite";
-    ec_status st = check_group(g, what);
-    if (st != EC_OK) return st;
-    // the op, the layer count, min_count and the dtype, before any device work (n = 0: no pointer is looked at)
-    st = ec_composite(op, t, nullptr, nullptr, n_layers, 0, min_count, nullptr, nullptr, nullptr, nullptr);
-    if (st != EC_OK) return st;
+// A stack call (ec_sharded_composite, ec_sharded_composite_rank) behind its group check and its pre-check: the columns are checked
+// and copied on the calling thread, then shard i's job gathers its K layer and mask pointers and hands them to `each`, which makes
+// the unsharded call: each(p, m, n, dst, dst_mask, aux, stream).  A refused call posts nothing.
+template <typename Each>
+static ec_status post_stack(ec_shard_group* g, const char* what, const void* const* const* layers, const uint8_t* const* const* masks_or_null,
+                            int32_t n_layers, const size_t* n, void* const* dst, uint8_t* const* dst_mask_or_null, uint8_t* const* aux_or_null,
+                            Each each) {
     if (!layers || !dst || !n) return set_error(EC_ERR_ARG, "%s: null argument", what);
     struct Call {
         std::vector<const void*> p[64];
@@ -639,6 +637,7 @@ extern "C" ec_status ec_sharded_composite(ec_shard_group* g, int32_t op, ec_dtyp
         masked = masked || (masks_or_null && masks_or_null[k]);
     }
     if (masked && !dst_mask_or_null) return set_error(EC_ERR_ARG, "%s: a layer has a mask, so the result needs dst_mask", what);
+    ec_status st = EC_OK;
     for (int k = 0; k < n_layers; ++k) {
         c->p[k] = take(g, what, "layers[k]", layers[k], n, &st);
         c->m[k] = take_optional(g, what, "masks[k]", masks_or_null ? masks_or_null[k] : nullptr, n, &st);
@@ -649,16 +648,30 @@ extern "C" ec_status ec_sharded_composite(ec_shard_group* g, int32_t op, ec_dtyp
     if (st != EC_OK) return st;
     c->n = copy_col(g, n);
     std::lock_guard<std::mutex> lk(g->call_mu);
-    return post_each_shard(g, [g, c, op, t, n_layers, min_count](int i) -> ec_status {
+    return post_each_shard(g, [g, c, n_layers, each](int i) -> ec_status {
         const void* p[64];
         const uint8_t* m[64];
         for (int k = 0; k < n_layers; ++k) {
             p[k] = c->p[k][i];
             m[k] = c->m[k][i];
         }
-        return ec_composite(op, t, p, m, n_layers, c->n[i], min_count, c->dst[i], c->dm.empty() ? nullptr : c->dm[i],
-                            c->aux.empty() ? nullptr : c->aux[i], g->streams[i]);
+        return each(p, m, c->n[i], c->dst[i], c->dm.empty() ? nullptr : c->dm[i], c->aux.empty() ? nullptr : c->aux[i], g->streams[i]);
     });
+}
+
+extern "C" ec_status ec_sharded_composite(ec_shard_group* g, int32_t op, ec_dtype t, const void* const* const* layers,
+                                          const uint8_t* const* const* masks_or_null, int32_t n_layers, const size_t* n, uint32_t min_count,
+                                          void* const* dst, uint8_t* const* dst_mask_or_null, uint8_t* const* aux_or_null) {
+    const char* what = "ec_sharded_composite";
+    ec_status st = check_group(g, what);
+    if (st != EC_OK) return st;
+    // the op, the layer count, min_count and the dtype, before any device work (n = 0: no pointer is looked at)
+    st = ec_composite(op, t, nullptr, nullptr, n_layers, 0, min_count, nullptr, nullptr, nullptr, nullptr);
+    if (st != EC_OK) return st;
+    return post_stack(g, what, layers, masks_or_null, n_layers, n, dst, dst_mask_or_null, aux_or_null,
+                      [=](const void* const* p, const uint8_t* const* m, size_t ni, void* d, uint8_t* dm, uint8_t* aux, ec_stream s) {
+                          return ec_composite(op, t, p, m, n_layers, ni, min_count, d, dm, aux, s);
+                      });
 }
 
 extern "C" ec_status ec_sharded_composite_rank(ec_shard_group* g, ec_dtype t, const void* const* const* layers,
@@ -671,41 +684,10 @@ extern "C" ec_status ec_sharded_composite_rank(ec_shard_group* g, ec_dtype t, co
     // the layer count, q, the method, min_count and the dtype, before any device work (n = 0: no pointer is looked at)
     st = ec_composite_rank(t, nullptr, nullptr, n_layers, 0, num, den, method, min_count, nullptr, nullptr, nullptr, nullptr);
     if (st != EC_OK) return st;
-    if (!layers || !dst || !n) return set_error(EC_ERR_ARG, "%s: null argument", what);
-    struct Call {
-        std::vector<const void*> p[64];
-        std::vector<const uint8_t*> m[64];
-        std::vector<void*> dst;
-        std::vector<uint8_t*> dm, aux;
-        std::vector<size_t> n;
-    };
-    auto c = std::make_shared<Call>();
-    bool masked = false;
-    for (int k = 0; k < n_layers; ++k) {
-        if (!layers[k]) return set_error(EC_ERR_ARG, "%s: layer %d is a null column", what, k);
-        masked = masked || (masks_or_null && masks_or_null[k]);
-    }
-    if (masked && !dst_mask_or_null) return set_error(EC_ERR_ARG, "%s: a layer has a mask, so the result needs dst_mask", what);
-    for (int k = 0; k < n_layers; ++k) {
-        c->p[k] = take(g, what, "layers[k]", layers[k], n, &st);
-        c->m[k] = take_optional(g, what, "masks[k]", masks_or_null ? masks_or_null[k] : nullptr, n, &st);
-    }
-    c->dst = take(g, what, "dst", dst, n, &st);
-    if (dst_mask_or_null) c->dm = take(g, what, "dst_mask", dst_mask_or_null, n, &st);
-    if (aux_or_null) c->aux = take(g, what, "aux", aux_or_null, n, &st);
-    if (st != EC_OK) return st;
-    c->n = copy_col(g, n);
-    std::lock_guard<std::mutex> lk(g->call_mu);
-    return post_each_shard(g, [g, c, t, n_layers, num, den, method, min_count](int i) -> ec_status {
-        const void* p[64];
-        const uint8_t* m[64];
-        for (int k = 0; k < n_layers; ++k) {
-            p[k] = c->p[k][i];
-            m[k] = c->m[k][i];
-        }
-        return ec_composite_rank(t, p, m, n_layers, c->n[i], num, den, method, min_count, c->dst[i], c->dm.empty() ? nullptr : c->dm[i],
-                                 c->aux.empty() ? nullptr : c->aux[i], g->streams[i]);
-    });
+    return post_stack(g, what, layers, masks_or_null, n_layers, n, dst, dst_mask_or_null, aux_or_null,
+                      [=](const void* const* p, const uint8_t* const* m, size_t ni, void* d, uint8_t* dm, uint8_t* aux, ec_stream s) {
+                          return ec_composite_rank(t, p, m, n_layers, ni, num, den, method, min_count, d, dm, aux, s);
+                      });
 }
 
 extern "C" ec_status ec_sharded_fused(ec_shard_group* g, ec_op o1, ec_op o2, ec_op o3, const ec_dtype dt[4], const void* const* const p[4],

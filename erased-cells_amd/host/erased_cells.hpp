@@ -1098,21 +1098,47 @@ inline MaskedCellBuffer operator-(const MaskedCellBuffer& b) { return b.neg(); }
 // the valid cells; the rule is in include/erased_cells.h.  `aux` (optional) receives a UInt8 buffer: the layer each cell came from
 // (EC_COMPOSITE_NONE: none), for SUM / MEAN the number of valid layers.
 namespace detail {
-inline void composite_call(ec_composite_op op, CellType ct, size_t n, const std::vector<const void*>& p, const std::vector<const uint8_t*>* m,
-                           uint32_t min_count, CellBuffer& out, Mask* om, CellBuffer* aux) {
-    if (aux) *aux = CellBuffer(CellType::UInt8, n);
-    if (n == 0) return;  // an empty buffer has no memory to point at
-    check(ec_composite(op, static_cast<ec_dtype>(ct), p.data(), m ? m->data() : nullptr, static_cast<int32_t>(p.size()), n, min_count, out.ptr(),
-                       om ? om->ptr() : nullptr, aux ? static_cast<uint8_t*>(aux->ptr()) : nullptr, current_stream()));
-}
+// The operands of a stack call, from layers that are all CellBuffers or all MaskedCellBuffers: what the mirror refuses itself, with a
+// clear message (`what`: the caller's name, for its min_count text), then the cell type, the length, the pointers and the masks.
+struct Stack {
+    CellType ct;
+    size_t n;
+    std::vector<const void*> p;
+    std::vector<const uint8_t*> m;  // empty: no layer is masked
+};
 template <typename B>
-inline void composite_stack(const std::vector<const B*>& layers) {  // what the mirror refuses itself, with a clear message
+inline Stack composite_stack(const std::vector<const B*>& layers, const char* what, uint32_t min_count = 1) {
     if (layers.empty() || layers.size() > EC_COMPOSITE_MAX_LAYERS) throw Error(EC_ERR_ARG, "composite: the stack holds 1 .. EC_COMPOSITE_MAX_LAYERS (64) layers");
     for (const B* l : layers) {
         if (!l) throw Error(EC_ERR_ARG, "composite: null layer");
         if (l->cell_type() != layers[0]->cell_type()) throw Error(EC_ERR_ARG, "composite: layers of different cell types: cast the stack to one first");
         if (l->len() != layers[0]->len()) throw Error(EC_ERR_LENGTH, "composite: layers of different lengths");
     }
+    if (min_count < 1 || min_count > layers.size()) throw Error(EC_ERR_ARG, std::string(what) + ": min_count is not within 1 .. the number of layers");
+    Stack s{layers[0]->cell_type(), layers[0]->len(), {}, {}};
+    for (const B* l : layers) {
+        if constexpr (std::is_same<B, MaskedCellBuffer>::value) {
+            s.p.push_back(l->buffer().ptr());
+            s.m.push_back(l->mask().ptr());
+        } else {
+            s.p.push_back(l->ptr());
+        }
+    }
+    return s;
+}
+// The library call of a stack operation: `aux` is allocated when asked for, and nothing is called for an empty stack;
+// call(layers, masks or null, K, n, dst, dst_mask or null, aux or null) makes it.
+template <typename Call>
+inline void stack_call(const Stack& s, CellBuffer& out, Mask* om, CellBuffer* aux, Call call) {
+    if (aux) *aux = CellBuffer(CellType::UInt8, s.n);
+    if (s.n == 0) return;  // an empty buffer has no memory to point at
+    check(call(s.p.data(), s.m.empty() ? nullptr : s.m.data(), static_cast<int32_t>(s.p.size()), s.n, out.ptr(), om ? om->ptr() : nullptr,
+               aux ? static_cast<uint8_t*>(aux->ptr()) : nullptr));
+}
+inline void composite_call(ec_composite_op op, const Stack& s, uint32_t min_count, CellBuffer& out, Mask* om, CellBuffer* aux) {
+    stack_call(s, out, om, aux, [&](const void* const* p, const uint8_t* const* m, int32_t k, size_t n, void* dst, uint8_t* dm, uint8_t* ax) {
+        return ec_composite(op, static_cast<ec_dtype>(s.ct), p, m, k, n, min_count, dst, dm, ax, current_stream());
+    });
 }
 }  // namespace detail
 
@@ -1182,28 +1208,18 @@ inline MaskedCellBuffer CellBuffer::broadcast(const CellBuffer& table) const {
 
 // no layer is masked: every cell is valid and the result is a CellBuffer
 inline CellBuffer composite(const std::vector<const CellBuffer*>& layers, ec_composite_op op = EC_COMPOSITE_FIRST, CellBuffer* aux = nullptr) {
-    detail::composite_stack(layers);
-    const CellType ct = layers[0]->cell_type();
-    const size_t n = layers[0]->len();
-    CellBuffer out(static_cast<CellType>(ec_composite_result_type(op, static_cast<ec_dtype>(ct))), n);
-    std::vector<const void*> p;
-    for (const CellBuffer* l : layers) p.push_back(l->ptr());
-    detail::composite_call(op, ct, n, p, nullptr, 1, out, nullptr, aux);
+    const detail::Stack s = detail::composite_stack(layers, "composite");
+    CellBuffer out(static_cast<CellType>(ec_composite_result_type(op, static_cast<ec_dtype>(s.ct))), s.n);
+    detail::composite_call(op, s, 1, out, nullptr, aux);
     return out;
 }
 // a cell is valid when at least `min_count` layers are valid there (1: the ordinary composite; layers.size(): the AND rule)
 inline MaskedCellBuffer composite(const std::vector<const MaskedCellBuffer*>& layers, ec_composite_op op = EC_COMPOSITE_FIRST, uint32_t min_count = 1,
                                   CellBuffer* aux = nullptr) {
-    detail::composite_stack(layers);
-    const CellType ct = layers[0]->cell_type();
-    const size_t n = layers[0]->len();
-    CellBuffer out(static_cast<CellType>(ec_composite_result_type(op, static_cast<ec_dtype>(ct))), n);
-    Mask om(n);
-    std::vector<const void*> p;
-    std::vector<const uint8_t*> m;
-    for (const MaskedCellBuffer* l : layers) { p.push_back(l->buffer().ptr()); m.push_back(l->mask().ptr()); }
-    if (min_count < 1 || min_count > layers.size()) throw Error(EC_ERR_ARG, "composite: min_count is not within 1 .. the number of layers");
-    detail::composite_call(op, ct, n, p, &m, min_count, out, &om, aux);
+    const detail::Stack s = detail::composite_stack(layers, "composite", min_count);
+    CellBuffer out(static_cast<CellType>(ec_composite_result_type(op, static_cast<ec_dtype>(s.ct))), s.n);
+    Mask om(s.n);
+    detail::composite_call(op, s, min_count, out, &om, aux);
     return MaskedCellBuffer(std::move(out), std::move(om));
 }
 
@@ -1215,39 +1231,27 @@ struct RankFraction {
     uint32_t num = 1, den = 2;
 };
 namespace detail {
-inline void composite_rank_call(CellType ct, size_t n, const std::vector<const void*>& p, const std::vector<const uint8_t*>* m, RankFraction q,
-                                ec_rank_method method, uint32_t min_count, CellBuffer& out, Mask* om, CellBuffer* aux) {
+inline void composite_rank_call(const Stack& s, RankFraction q, ec_rank_method method, uint32_t min_count, CellBuffer& out, Mask* om, CellBuffer* aux) {
     if (q.den < 1 || q.den > EC_RANK_MAX_DEN || q.num > q.den) throw Error(EC_ERR_ARG, "composite_rank: q needs 1 <= den <= EC_RANK_MAX_DEN (65535) and num <= den");
     if (method != EC_RANK_LOWER && method != EC_RANK_UPPER) throw Error(EC_ERR_ARG, "composite_rank: the method is EC_RANK_LOWER or EC_RANK_UPPER");
-    if (aux) *aux = CellBuffer(CellType::UInt8, n);
-    if (n == 0) return;  // an empty buffer has no memory to point at
-    check(ec_composite_rank(static_cast<ec_dtype>(ct), p.data(), m ? m->data() : nullptr, static_cast<int32_t>(p.size()), n, q.num, q.den, method, min_count,
-                            out.ptr(), om ? om->ptr() : nullptr, aux ? static_cast<uint8_t*>(aux->ptr()) : nullptr, current_stream()));
+    stack_call(s, out, om, aux, [&](const void* const* p, const uint8_t* const* m, int32_t k, size_t n, void* dst, uint8_t* dm, uint8_t* ax) {
+        return ec_composite_rank(static_cast<ec_dtype>(s.ct), p, m, k, n, q.num, q.den, method, min_count, dst, dm, ax, current_stream());
+    });
 }
 }  // namespace detail
 inline CellBuffer composite_rank(const std::vector<const CellBuffer*>& layers, RankFraction q = {}, ec_rank_method method = EC_RANK_LOWER,
                                  CellBuffer* aux = nullptr) {
-    detail::composite_stack(layers);
-    const CellType ct = layers[0]->cell_type();
-    const size_t n = layers[0]->len();
-    CellBuffer out(ct, n);
-    std::vector<const void*> p;
-    for (const CellBuffer* l : layers) p.push_back(l->ptr());
-    detail::composite_rank_call(ct, n, p, nullptr, q, method, 1, out, nullptr, aux);
+    const detail::Stack s = detail::composite_stack(layers, "composite_rank");
+    CellBuffer out(s.ct, s.n);
+    detail::composite_rank_call(s, q, method, 1, out, nullptr, aux);
     return out;
 }
 inline MaskedCellBuffer composite_rank(const std::vector<const MaskedCellBuffer*>& layers, RankFraction q = {}, ec_rank_method method = EC_RANK_LOWER,
                                        uint32_t min_count = 1, CellBuffer* aux = nullptr) {
-    detail::composite_stack(layers);
-    const CellType ct = layers[0]->cell_type();
-    const size_t n = layers[0]->len();
-    CellBuffer out(ct, n);
-    Mask om(n);
-    std::vector<const void*> p;
-    std::vector<const uint8_t*> m;
-    for (const MaskedCellBuffer* l : layers) { p.push_back(l->buffer().ptr()); m.push_back(l->mask().ptr()); }
-    if (min_count < 1 || min_count > layers.size()) throw Error(EC_ERR_ARG, "composite_rank: min_count is not within 1 .. the number of layers");
-    detail::composite_rank_call(ct, n, p, &m, q, method, min_count, out, &om, aux);
+    const detail::Stack s = detail::composite_stack(layers, "composite_rank", min_count);
+    CellBuffer out(s.ct, s.n);
+    Mask om(s.n);
+    detail::composite_rank_call(s, q, method, min_count, out, &om, aux);
     return MaskedCellBuffer(std::move(out), std::move(om));
 }
 inline CellBuffer composite_median(const std::vector<const CellBuffer*>& layers, ec_rank_method method = EC_RANK_LOWER, CellBuffer* aux = nullptr) {

@@ -1472,6 +1472,25 @@ def _composite_stack(layers, min_count):
     return pairs, ct, n
 
 
+def _stack_call(layers, min_count, aux: bool, result_type, call):
+    """What `composite` and `composite_rank` do but for their own arguments: the stack's checks, the result (cells of
+    `result_type(cell type)`), its Mask when a layer is masked and the UInt8 `aux` buffer when asked for, and
+    `call(cell type, layers, masks or None, K, n, dst, dst_mask or None, aux or None)`, which makes the library call.  A CellBuffer when
+    no layer is masked, otherwise a MaskedCellBuffer; with `aux` a pair (result, aux buffer)."""
+    pairs, ct, n = _composite_stack(layers, min_count)
+    masked = any(m is not None for _, m in pairs)
+    out = CellBuffer.empty(n, result_type(ct))
+    om = Mask.empty(n) if masked else None
+    ax = CellBuffer.empty(n, UInt8) if aux else None
+    if n:  # an empty buffer has no memory to point at
+        k = len(pairs)
+        lp = (C.c_void_p * k)(*[b.mem.ptr for b, _ in pairs])
+        mp = (C.c_void_p * k)(*[m.mem.ptr if m is not None else None for _, m in pairs])
+        check(call(ct, lp, mp if masked else None, k, n, out.mem.ptr, om.mem.ptr if masked else None, ax.mem.ptr if aux else None))
+    res = MaskedCellBuffer(out, om) if masked else out
+    return (res, ax) if aux else res
+
+
 def composite(layers, op="first", min_count: int = 1, aux: bool = False):
     """One buffer from a stack of co-registered `layers` (CellBuffers and MaskedCellBuffers, mixed allowed, one cell type and length), in
     one pass (ec_composite; the rule is in include/erased_cells.h).  `op`: "first" / "last" valid layer, "min" / "max" valid cell, "sum" /
@@ -1479,19 +1498,8 @@ def composite(layers, op="first", min_count: int = 1, aux: bool = False):
     otherwise a MaskedCellBuffer; with `aux` a pair (result, UInt8 CellBuffer): the layer each cell came from (255: none), for sum / mean
     the number of valid layers."""
     o = _composite_op(op)
-    pairs, ct, n = _composite_stack(layers, min_count)
-    masked = any(m is not None for _, m in pairs)
-    out = CellBuffer.empty(n, lib().ec_composite_result_type(o, ct))
-    om = Mask.empty(n) if masked else None
-    ax = CellBuffer.empty(n, UInt8) if aux else None
-    if n:  # an empty buffer has no memory to point at
-        k = len(pairs)
-        lp = (C.c_void_p * k)(*[b.mem.ptr for b, _ in pairs])
-        mp = (C.c_void_p * k)(*[m.mem.ptr if m is not None else None for _, m in pairs])
-        check(lib().ec_composite(o, ct, lp, mp if masked else None, k, n, int(min_count), out.mem.ptr, om.mem.ptr if masked else None,
-                                 ax.mem.ptr if aux else None, _stream))
-    res = MaskedCellBuffer(out, om) if masked else out
-    return (res, ax) if aux else res
+    return _stack_call(layers, min_count, aux, lambda ct: lib().ec_composite_result_type(o, ct),
+                       lambda ct, lp, mp, k, n, dst, dm, ax: lib().ec_composite(o, ct, lp, mp, k, n, int(min_count), dst, dm, ax, _stream))
 
 
 # the spellings of an ec_rank_method
@@ -1521,19 +1529,8 @@ def composite_rank(layers, q=(1, 2), method="lower", min_count: int = 1, aux: bo
     when at least `min_count` layers are.  A CellBuffer when no layer is masked, otherwise a MaskedCellBuffer; with `aux` a pair
     (result, UInt8 CellBuffer): the layer each cell came from (255: none)."""
     num, den, m = _rank_args(q, method)
-    pairs, ct, n = _composite_stack(layers, min_count)
-    masked = any(mk is not None for _, mk in pairs)
-    out = CellBuffer.empty(n, ct)
-    om = Mask.empty(n) if masked else None
-    ax = CellBuffer.empty(n, UInt8) if aux else None
-    if n:  # an empty buffer has no memory to point at
-        k = len(pairs)
-        lp = (C.c_void_p * k)(*[b.mem.ptr for b, _ in pairs])
-        mp = (C.c_void_p * k)(*[mk.mem.ptr if mk is not None else None for _, mk in pairs])
-        check(lib().ec_composite_rank(ct, lp, mp if masked else None, k, n, num, den, m, int(min_count), out.mem.ptr,
-                                      om.mem.ptr if masked else None, ax.mem.ptr if aux else None, _stream))
-    res = MaskedCellBuffer(out, om) if masked else out
-    return (res, ax) if aux else res
+    return _stack_call(layers, min_count, aux, lambda ct: ct,
+                       lambda ct, lp, mp, k, n, dst, dm, ax: lib().ec_composite_rank(ct, lp, mp, k, n, num, den, m, int(min_count), dst, dm, ax, _stream))
 
 
 def composite_median(layers, method="lower", min_count: int = 1, aux: bool = False):

@@ -265,69 +265,53 @@ class ShardGroup:
         return self.reclassify(src, breaks, np.arange(len(breaks) + 1, dtype=np.uint8), right=right, mask=mask,
                                nodata=None if mask is None else (255 if len(breaks) < 255 else 0), breaks_dtype=breaks_dtype)
 
-    def composite(self, layers, op="first", min_count: int = 1, aux: bool = False, masks=None):
-        """`composite` on every shard, fire-and-forget: `layers` up to 64 identically sharded buffers of one cell type, `masks` (optional)
-        one sharded mask or None per layer.  Returns the sharded result, `(result, mask)` when a layer has a mask, and with `aux` the
-        sharded UInt8 aux buffer as the last element."""
+    def _stack_call(self, what: str, layers, masks, min_count, aux: bool, result_type, call):
+        """What `composite` and `composite_rank` do but for their own arguments: the stack's checks (texts start with `what`), the
+        sharded result (cells of `result_type(cell type)`), its mask when a layer has one and the UInt8 aux buffer when asked for, and
+        `call(cell type, layers, masks or None, K, n, dst, dst_mask or None, aux or None)`, which makes the library call."""
         from ._ffi import EC_COMPOSITE_MAX_LAYERS, EC_ERR_ARG, EcError, PVP
-        o, layers = B._composite_op(op), list(layers)
+        layers = list(layers)
         k = len(layers)
         if not 1 <= k <= EC_COMPOSITE_MAX_LAYERS:
-            raise EcError(EC_ERR_ARG, f"composite: {k} layers, not within 1 .. EC_COMPOSITE_MAX_LAYERS ({EC_COMPOSITE_MAX_LAYERS})")
+            raise EcError(EC_ERR_ARG, f"{what}: {k} layers, not within 1 .. EC_COMPOSITE_MAX_LAYERS ({EC_COMPOSITE_MAX_LAYERS})")
         masks = list(masks) if masks is not None else [None] * k
         if len(masks) != k:
-            raise EcError(EC_ERR_ARG, f"composite: {len(masks)} masks for {k} layers")
+            raise EcError(EC_ERR_ARG, f"{what}: {len(masks)} masks for {k} layers")
         ct, lens = layers[0].ct, layers[0].lens
         for i, b in enumerate(layers):
             if b.ct != ct:
-                raise EcError(EC_ERR_ARG, f"composite: layer {i} is {B.CT_NAMES[b.ct]}, layer 0 {B.CT_NAMES[ct]}: cast the stack to one cell type first")
+                raise EcError(EC_ERR_ARG, f"{what}: layer {i} is {B.CT_NAMES[b.ct]}, layer 0 {B.CT_NAMES[ct]}: cast the stack to one cell type first")
             if b.lens != lens or (masks[i] is not None and masks[i].lens != lens):
-                raise EcError(EC_ERR_ARG, f"composite: layer {i} or its mask is not sharded like layer 0")
+                raise EcError(EC_ERR_ARG, f"{what}: layer {i} or its mask is not sharded like layer 0")
         if isinstance(min_count, bool) or not isinstance(min_count, int) or not 1 <= min_count <= k:
-            raise EcError(EC_ERR_ARG, f"composite: min_count {min_count!r} is not within 1 .. {k}, the number of layers")
+            raise EcError(EC_ERR_ARG, f"{what}: min_count {min_count!r} is not within 1 .. {k}, the number of layers")
         masked = any(m is not None for m in masks)
-        out = self.alloc(lib().ec_composite_result_type(o, ct), lens)
+        out = self.alloc(result_type(ct), lens)
         om = self.alloc(B.UInt8, lens) if masked else None
         ax = self.alloc(B.UInt8, lens) if aux else None
         p = (PVP * k)(*[C.cast(b.ptrs, PVP) for b in layers])
         m = (PVP * k)(*[C.cast(b.ptrs, PVP) if b is not None else PVP() for b in masks]) if masked else None
-        check(lib().ec_sharded_composite(self.handle, o, ct, p, m, k, (C.c_size_t * self.n)(*lens), min_count, out.ptrs,
-                                         om.ptrs if masked else None, ax.ptrs if aux else None))
+        check(call(ct, p, m, k, (C.c_size_t * self.n)(*lens), out.ptrs, om.ptrs if masked else None, ax.ptrs if aux else None))
         res = (out, om) if masked else (out,)
         res = res + (ax,) if aux else res
         return res[0] if len(res) == 1 else res
+
+    def composite(self, layers, op="first", min_count: int = 1, aux: bool = False, masks=None):
+        """`composite` on every shard, fire-and-forget: `layers` up to 64 identically sharded buffers of one cell type, `masks` (optional)
+        one sharded mask or None per layer.  Returns the sharded result, `(result, mask)` when a layer has a mask, and with `aux` the
+        sharded UInt8 aux buffer as the last element."""
+        o = B._composite_op(op)
+        return self._stack_call("composite", layers, masks, min_count, aux, lambda ct: lib().ec_composite_result_type(o, ct),
+                                lambda ct, p, m, k, n, dst, dm, ax: lib().ec_sharded_composite(self.handle, o, ct, p, m, k, n, min_count, dst, dm, ax))
 
     def composite_rank(self, layers, q=(1, 2), method="lower", min_count: int = 1, aux: bool = False, masks=None):
         """`composite_rank` on every shard, fire-and-forget: the per-cell order statistic (q = (num, den); (1, 2) the median) of up to 64
         identically sharded buffers of one cell type, `masks` (optional) one sharded mask or None per layer.  Returns what `composite`
         returns: the sharded result, `(result, mask)` when a layer has a mask, and with `aux` the sharded UInt8 aux buffer last."""
-        from ._ffi import EC_COMPOSITE_MAX_LAYERS, EC_ERR_ARG, EcError, PVP
-        (num, den, mth), layers = B._rank_args(q, method), list(layers)
-        k = len(layers)
-        if not 1 <= k <= EC_COMPOSITE_MAX_LAYERS:
-            raise EcError(EC_ERR_ARG, f"composite_rank: {k} layers, not within 1 .. EC_COMPOSITE_MAX_LAYERS ({EC_COMPOSITE_MAX_LAYERS})")
-        masks = list(masks) if masks is not None else [None] * k
-        if len(masks) != k:
-            raise EcError(EC_ERR_ARG, f"composite_rank: {len(masks)} masks for {k} layers")
-        ct, lens = layers[0].ct, layers[0].lens
-        for i, b in enumerate(layers):
-            if b.ct != ct:
-                raise EcError(EC_ERR_ARG, f"composite_rank: layer {i} is {B.CT_NAMES[b.ct]}, layer 0 {B.CT_NAMES[ct]}: cast the stack to one cell type first")
-            if b.lens != lens or (masks[i] is not None and masks[i].lens != lens):
-                raise EcError(EC_ERR_ARG, f"composite_rank: layer {i} or its mask is not sharded like layer 0")
-        if isinstance(min_count, bool) or not isinstance(min_count, int) or not 1 <= min_count <= k:
-            raise EcError(EC_ERR_ARG, f"composite_rank: min_count {min_count!r} is not within 1 .. {k}, the number of layers")
-        masked = any(m is not None for m in masks)
-        out = self.alloc(ct, lens)
-        om = self.alloc(B.UInt8, lens) if masked else None
-        ax = self.alloc(B.UInt8, lens) if aux else None
-        p = (PVP * k)(*[C.cast(b.ptrs, PVP) for b in layers])
-        m = (PVP * k)(*[C.cast(b.ptrs, PVP) if b is not None else PVP() for b in masks]) if masked else None
-        check(lib().ec_sharded_composite_rank(self.handle, ct, p, m, k, (C.c_size_t * self.n)(*lens), num, den, mth, min_count, out.ptrs,
-                                              om.ptrs if masked else None, ax.ptrs if aux else None))
-        res = (out, om) if masked else (out,)
-        res = res + (ax,) if aux else res
-        return res[0] if len(res) == 1 else res
+        num, den, mth = B._rank_args(q, method)
+        return self._stack_call("composite_rank", layers, masks, min_count, aux, lambda ct: ct,
+                                lambda ct, p, m, k, n, dst, dm, ax: lib().ec_sharded_composite_rank(self.handle, ct, p, m, k, n, num, den, mth, min_count,
+                                                                                                    dst, dm, ax))
 
     def program(self, streams, scalars, steps, masks=None):
         """An expression program (`fused.program`: steps `(op, a, b, dst)`) on every shard, fire-and-forget: `streams` up to four

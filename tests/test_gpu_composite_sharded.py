@@ -84,17 +84,23 @@ def test_a_refused_call_posts_nothing(ec):
         posted = g.stat("jobs_posted")
         call = lambda op=0, t=ct, l=lp, m=mp, kk=k, nn=n, mc=1, d=out.ptrs, dm=om.ptrs, a=aux.ptrs: \
             L.ec_sharded_composite(g.handle, op, t, l, m, kk, nn, mc, d, dm, a)
+        said = lambda st: (st, L.ec_last_error_string().decode())   # the status and the text the calling thread was left with
+        own, pre = "ec_sharded_composite: ", "ec_composite: "        # refused by the group's entry point, or by its pre-check
         refused = [
-            (call(op=6), E.EC_ERR_ARG), (call(op=-1), E.EC_ERR_ARG),
-            (call(kk=0), E.EC_ERR_ARG), (call(kk=65), E.EC_ERR_ARG),
-            (call(mc=0), E.EC_ERR_ARG), (call(mc=k + 1), E.EC_ERR_ARG),
-            (call(t=10), E.EC_ERR_UNSUPPORTED_TYPE), (call(t=255), E.EC_ERR_UNSUPPORTED_TYPE),
-            (call(l=None), E.EC_ERR_ARG), (call(d=None), E.EC_ERR_ARG), (call(nn=None), E.EC_ERR_ARG),
-            (call(l=cols([sl[0], None, sl[2]])), E.EC_ERR_ARG),       # a null layer column
-            (call(l=cols([sl[0], holed, sl[2]])), E.EC_ERR_ARG),      # a null pointer in a column of a shard that has cells
-            (call(dm=None), E.EC_ERR_ARG),                            # a layer has a mask: dst_mask is required
+            (said(call(op=6)), E.EC_ERR_ARG, pre, "ec_composite_op"), (said(call(op=-1)), E.EC_ERR_ARG, pre, "ec_composite_op"),
+            (said(call(kk=0)), E.EC_ERR_ARG, pre, "EC_COMPOSITE_MAX_LAYERS"), (said(call(kk=65)), E.EC_ERR_ARG, pre, "EC_COMPOSITE_MAX_LAYERS"),
+            (said(call(mc=0)), E.EC_ERR_ARG, pre, "min_count"), (said(call(mc=k + 1)), E.EC_ERR_ARG, pre, "min_count"),
+            (said(call(t=10)), E.EC_ERR_UNSUPPORTED_TYPE, pre, "bad dtype 10"), (said(call(t=255)), E.EC_ERR_UNSUPPORTED_TYPE, pre, "bad dtype 255"),
+            (said(call(l=None)), E.EC_ERR_ARG, own, "null argument"), (said(call(d=None)), E.EC_ERR_ARG, own, "null argument"),
+            (said(call(nn=None)), E.EC_ERR_ARG, own, "null argument"),
+            (said(call(l=cols([sl[0], None, sl[2]]))), E.EC_ERR_ARG, own, "layer 1 is a null column"),
+            # a null pointer in a column of a shard that has cells
+            (said(call(l=cols([sl[0], holed, sl[2]]))), E.EC_ERR_ARG, own, "layers[k][1] is null with n[1] = 24"),
+            (said(call(dm=None)), E.EC_ERR_ARG, own, "a layer has a mask, so the result needs dst_mask"),
         ]
-        assert [st for st, _ in refused] == [e for _, e in refused]
+        assert [st for (st, _), *_ in refused] == [e for _, e, *_ in refused]
+        for (_, text), _, head, words in refused:
+            assert text.startswith(head) and words in text, text
         assert g.stat("jobs_posted") == posted, "a refused call posted a job"
         with pytest.raises(ec.EcError):
             g.composite(sl, "median")
