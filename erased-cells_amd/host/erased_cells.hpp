@@ -339,6 +339,9 @@ class Mask;
 class MaskedCellBuffer;
 
 namespace detail {
+// ec_regions with labels on raw pointers (src null: the mask form): what the three regions methods share
+inline std::pair<MaskedCellBuffer, uint64_t> regions_of(ec_dtype t, const void* src, const uint8_t* src_mask, size_t n, size_t cols, int32_t connectivity,
+                                                        uint64_t min_cells, ec_regions_numbering numbering);
 // ec_focal_rank, or ec_focal_majority when `q` is null, on raw pointers: what the focal_rank / focal_median / focal_majority methods share
 inline void focal_rank_call(ec_dtype t, const void* src, const uint8_t* src_mask, size_t n, size_t cols, std::pair<uint32_t, uint32_t> radius,
                             const std::pair<uint32_t, uint32_t>* q, ec_rank_method method, bool whole, void* dst, uint8_t* dst_mask) {
@@ -628,6 +631,12 @@ public:
                                       std::pair<uint32_t, uint32_t> radius = {1, 1}) const;
     MaskedCellBuffer focal_median_whole(size_t cols, std::pair<uint32_t, uint32_t> radius = {1, 1}, ec_rank_method method = EC_RANK_LOWER) const;
     MaskedCellBuffer focal_majority_whole(size_t cols, std::pair<uint32_t, uint32_t> radius = {1, 1}) const;
+    // The connected regions of equal cells of this buffer read as rows of `cols` cells (ec_regions; the rule is in
+    // include/erased_cells.h): Int32 labels with their validity, and K, the number of regions kept.  "Equal" is equal bits,
+    // connectivity is 4 or 8, a region of fewer than min_cells cells is invalidated.  The labels are a zone raster:
+    // zonal_stats(labels.buffer(), K + 1).
+    std::pair<MaskedCellBuffer, uint64_t> regions(size_t cols, int32_t connectivity = 4, uint64_t min_cells = 0,
+                                                  ec_regions_numbering numbering = EC_REGIONS_DENSE) const;
 
     // ---- Ord/Eq (buffer.rs:373-436): cell type first, then lexicographic total order, then length
     int cmp(const CellBuffer& o) const {  // decided on the device: first differing cell, no download
@@ -774,6 +783,18 @@ public:
         return m;
     }
 
+    // The connected regions of the SET bytes of the mask read as rows of `cols` bytes (ec_regions without cells: every set byte equals
+    // every other), as CellBuffer::regions gives them; and the mask without its regions of fewer than min_cells set bytes
+    // (ec_regions' sieve-only form: no label is ever written).
+    std::pair<MaskedCellBuffer, uint64_t> regions(size_t cols, int32_t connectivity = 4, uint64_t min_cells = 0,
+                                                  ec_regions_numbering numbering = EC_REGIONS_DENSE) const;
+    Mask sieve(size_t cols, uint64_t min_cells, int32_t connectivity = 4) const {
+        if (cols ? n_ % cols != 0 : n_ != 0) throw std::logic_error("the mask is not rows of " + std::to_string(cols) + " bytes");
+        Mask m(n_);
+        if (n_) check(ec_regions(EC_U8, nullptr, ptr(), cols, n_ / cols, connectivity, EC_REGIONS_ROOT, min_cells, nullptr, m.ptr(), nullptr, nullptr, current_stream()));
+        return m;
+    }
+
     Mask operator!() const& {  // Not for &Mask (mask.rs:111-116)
         Mask m(n_);
         check(ec_mask_not(ptr(), n_, m.ptr(), current_stream()));
@@ -917,6 +938,20 @@ public:
         detail::focal_rank_call(static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), len(), cols, radius, nullptr, EC_RANK_LOWER, whole, b.ptr(), m.ptr());
         return MaskedCellBuffer(std::move(b), std::move(m));
     }
+    // CellBuffer::regions over the cells whose mask byte is set: an invalid cell belongs to no region and joins none.  sieve: the
+    // same cells with every region of fewer than min_cells cells invalidated (GDAL's sieve merges such a patch into its largest
+    // neighbour; this one drops it).
+    std::pair<MaskedCellBuffer, uint64_t> regions(size_t cols, int32_t connectivity = 4, uint64_t min_cells = 0,
+                                                  ec_regions_numbering numbering = EC_REGIONS_DENSE) const {
+        return detail::regions_of(static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), len(), cols, connectivity, min_cells, numbering);
+    }
+    MaskedCellBuffer sieve(size_t cols, uint64_t min_cells, int32_t connectivity = 4) const {
+        if (cols ? len() % cols != 0 : len() != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
+        Mask m(len());
+        if (len()) check(ec_regions(static_cast<ec_dtype>(cell_type()), buf_.ptr(), mask_.ptr(), cols, len() / cols, connectivity, EC_REGIONS_ROOT, min_cells,
+                                    nullptr, m.ptr(), nullptr, nullptr, current_stream()));
+        return MaskedCellBuffer(buf_.clone(), std::move(m));
+    }
     void put_window(size_t cols, std::pair<size_t, size_t> window, std::pair<size_t, size_t> window_size, const MaskedCellBuffer& tile) {
         if (cols ? len() % cols != 0 : len() != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
         if (tile.cell_type() != cell_type() || tile.len() != window_size.first * window_size.second)
@@ -1056,6 +1091,26 @@ inline MaskedCellBuffer CellBuffer::convolve_whole(size_t cols, const std::vecto
     if (n_) check(ec_focal_convolve(static_cast<ec_dtype>(ct_), ptr(), nullptr, cols, n_ / cols, weights.data(), radius.first, radius.second,
                                     EC_FOCAL_WHOLE | (normalize ? EC_FOCAL_NORMALIZE : 0), b.ptr(), m.ptr(), current_stream()));
     return MaskedCellBuffer(std::move(b), std::move(m));
+}
+
+inline std::pair<MaskedCellBuffer, uint64_t> detail::regions_of(ec_dtype t, const void* src, const uint8_t* src_mask, size_t n, size_t cols,
+                                                                int32_t connectivity, uint64_t min_cells, ec_regions_numbering numbering) {
+    if (cols ? n % cols != 0 : n != 0) throw std::logic_error("the buffer is not rows of " + std::to_string(cols) + " cells");
+    CellBuffer labels(CellType::Int32, n), k(CellType::UInt64, 1);
+    Mask m(n);
+    uint64_t kept = 0;
+    if (n) {
+        check(ec_regions(t, src, src_mask, cols, n / cols, connectivity, numbering, min_cells, static_cast<int32_t*>(labels.ptr()), m.ptr(),
+                         static_cast<uint64_t*>(k.ptr()), nullptr, current_stream()));
+        kept = k.to_vec<uint64_t>()[0];
+    }
+    return {MaskedCellBuffer(std::move(labels), std::move(m)), kept};
+}
+inline std::pair<MaskedCellBuffer, uint64_t> CellBuffer::regions(size_t cols, int32_t connectivity, uint64_t min_cells, ec_regions_numbering numbering) const {
+    return detail::regions_of(static_cast<ec_dtype>(ct_), ptr(), nullptr, n_, cols, connectivity, min_cells, numbering);
+}
+inline std::pair<MaskedCellBuffer, uint64_t> Mask::regions(size_t cols, int32_t connectivity, uint64_t min_cells, ec_regions_numbering numbering) const {
+    return detail::regions_of(EC_U8, nullptr, ptr(), n_, cols, connectivity, min_cells, numbering);
 }
 
 inline MaskedCellBuffer Mask::distance(size_t cols, double max_distance, bool squared) const {

@@ -34,6 +34,8 @@ EC_ZONAL_MAX_ZONES = 256
 EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES = 255, 4384
 EC_RECLASS_HAS_NODATA, EC_RECLASS_DROPS = 1, 2  # ec_reclass_table.flags
 EC_DISTANCE_MAX_SIDE, EC_DISTANCE_UNLIMITED = 32768, 0xFFFFFFFF  # ec_distance: the longest side, max_sq of "no limit"
+EC_REGIONS_MAX_SIDE = 32768  # ec_regions: the longest side
+EC_REGIONS_ROOT, EC_REGIONS_DENSE = range(2)  # ec_regions_numbering
 
 
 class _Payload(C.Union):
@@ -220,6 +222,8 @@ SIGNATURES = {
     "ec_sharded_reclass": (I32, [VP, C.c_uint8, PVP, PVP, PSZ, C.c_uint8, PVP, PVP, PVP]),
     "ec_distance_workspace_bytes": (SZ, [C.c_uint64, C.c_uint64]),
     "ec_distance": (I32, [U8P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint8, VP, U8P, VP, VP]),
+    "ec_regions_workspace_bytes": (SZ, [C.c_uint64, C.c_uint64]),
+    "ec_regions": (I32, [C.c_uint8, VP, U8P, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_uint64, VP, U8P, VP, VP, VP]),
     "ec_composite_result_type": (C.c_uint8, [I32, C.c_uint8]),
     "ec_composite": (I32, [I32, C.c_uint8, PVP, PVP, I32, SZ, C.c_uint32, VP, U8P, U8P, VP]),
     "ec_sharded_composite": (I32, [VP, I32, C.c_uint8, C.POINTER(PVP), C.POINTER(PVP), I32, PSZ, C.c_uint32, PVP, PVP, PVP]),

@@ -21,7 +21,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_COMPOSITE_MAX_LAYERS, EC_DISTANCE_UNLIMITED, EC_RANK_LOWER, EC_RANK_MAX_DEN, EC_RANK_UPPER, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_ZONAL_MAX_ZONES, EC_RECLASS_DROPS, EC_RECLASS_HAS_NODATA, EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES, EC_RESAMPLE_BILINEAR, EcError, EcReclassTable, EcStats, EcValue, check, lib
+from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_COMPOSITE_MAX_LAYERS, EC_DISTANCE_UNLIMITED, EC_REGIONS_DENSE, EC_REGIONS_ROOT, EC_RANK_LOWER, EC_RANK_MAX_DEN, EC_RANK_UPPER, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_ZONAL_MAX_ZONES, EC_RECLASS_DROPS, EC_RECLASS_HAS_NODATA, EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES, EC_RESAMPLE_BILINEAR, EcError, EcReclassTable, EcStats, EcValue, check, lib
 
 # CellType (src/ctype.rs:11-20; order of with_ct!, src/lib.rs:89-98)
 UInt8, UInt16, UInt32, UInt64, Int8, Int16, Int32, Int64, Float32, Float64 = range(10)
@@ -453,6 +453,28 @@ def _max_sq(max_distance) -> int:
     return min(sq.numerator // sq.denominator, EC_DISTANCE_UNLIMITED)
 
 
+def _regions(buf, mask, n: int, cols: int, connectivity: int, min_cells: int, numbering, labels: bool):
+    """ec_regions of `buf` (or None: the mask form) under `mask` (or None) read as rows of `cols` cells, with the workspace from the
+    library's pool -> (MaskedCellBuffer of Int32 labels, K), or with `labels` False — the sieve-only form — the Mask of the kept cells."""
+    if isinstance(numbering, str):
+        if numbering not in ("root", "dense"):
+            raise EcError(EC_ERR_ARG, f"regions: the numbering {numbering!r} is neither 'root' nor 'dense'")
+        numbering = EC_REGIONS_DENSE if numbering == "dense" else EC_REGIONS_ROOT
+    if isinstance(min_cells, bool) or int(min_cells) != min_cells or not 0 <= min_cells < 1 << 64:
+        raise EcError(EC_ERR_ARG, f"regions: min_cells {min_cells!r} is not an integer within 0 .. 2^64 - 1")
+    rows = _raster_rows(n, cols)
+    out = CellBuffer.empty(n, Int32) if labels else None
+    om = Mask.empty(n)
+    k = CellBuffer.empty(1, UInt64) if labels else None
+    if n:  # an empty raster has no memory to point at, and no region
+        check(lib().ec_regions(buf.ct if buf is not None else UInt8, buf.mem.ptr if buf is not None else None, mask.mem.ptr if mask is not None else None,
+                               cols, rows, int(connectivity), int(numbering), int(min_cells), out.mem.ptr if labels else None, om.mem.ptr,
+                               k.mem.ptr if labels else None, None, _stream))
+    if not labels:
+        return om
+    return MaskedCellBuffer(out, om), (int(k.to_numpy()[0]) if n else 0)
+
+
 def _radius(radius):
     rx, ry = radius
     if not 0 <= min(rx, ry) <= max(rx, ry) <= EC_FOCAL_RADIUS_CAP:  # here, not in C: a radius of 2^32 + 1 would arrive there as 1
@@ -635,6 +657,13 @@ class CellBuffer:
         those that tie under the total order; "equal" is equal bits.  Returns what `focal(cols, "min", ...)` returns."""
         out, om = _focal_rank(self, None, cols, None, None, radius, whole)
         return out if om is None else MaskedCellBuffer(out, om)
+
+    def regions(self, cols: int, connectivity: int = 4, min_cells: int = 0, numbering="dense"):
+        """The connected regions of equal cells of this buffer read as rows of `cols` cells (ec_regions; the rule is in
+        include/erased_cells.h) -> (MaskedCellBuffer of Int32 labels, K): "equal" is equal bits, `connectivity` 4 or 8, regions of
+        fewer than `min_cells` cells are invalidated, and the K kept ones are numbered 1 .. K in raster order of their first cell
+        ("dense") or by that cell's index plus one ("root").  The labels are a zone raster: `zonal_stats(labels, K + 1)`."""
+        return _regions(self, None, self.n, cols, connectivity, min_cells, numbering, True)
 
     def put_window(self, cols: int, window, tile: "CellBuffer", window_size) -> None:
         """Writes `tile` (`window_size` = (w, h) contiguous cells of this buffer's type) into the window at `window` = (x, y) of this
@@ -983,6 +1012,16 @@ class Mask:
         (`dilate` is the rectangle).  ec_distance's mask-only form: no distance is ever written."""
         return self._distance(cols, _max_sq(distance), None)[1]
 
+    def regions(self, cols: int, connectivity: int = 4, min_cells: int = 0, numbering="dense"):
+        """The connected regions of the SET bytes of the mask read as rows of `cols` bytes (ec_regions without cells: every set
+        byte equals every other) -> (MaskedCellBuffer of Int32 labels, K), as `CellBuffer.regions`; with "dense" this is
+        scipy.ndimage.label's numbering."""
+        return _regions(None, self, self.n, cols, connectivity, min_cells, numbering, True)
+
+    def sieve(self, cols: int, min_cells: int, connectivity: int = 4) -> "Mask":
+        """The mask without its regions of fewer than `min_cells` set bytes (ec_regions' sieve-only form)."""
+        return _regions(None, self, self.n, cols, connectivity, min_cells, EC_REGIONS_ROOT, False)
+
     def counts(self) -> tuple[int, int]:
         """(data, nodata) — mask.rs:72-80."""
         a, b = C.c_uint64(), C.c_uint64()
@@ -1137,6 +1176,15 @@ class MaskedCellBuffer:
     def focal_majority(self, cols: int, radius=(1, 1), whole: bool = False) -> "MaskedCellBuffer":
         """`CellBuffer.focal_majority` over the cells whose mask byte is set."""
         return MaskedCellBuffer(*_focal_rank(self._buf, self._mask, cols, None, None, radius, whole))
+
+    def regions(self, cols: int, connectivity: int = 4, min_cells: int = 0, numbering="dense"):
+        """`CellBuffer.regions` over the cells whose mask byte is set: an invalid cell belongs to no region and joins none."""
+        return _regions(self._buf, self._mask, self.len(), cols, connectivity, min_cells, numbering, True)
+
+    def sieve(self, cols: int, min_cells: int, connectivity: int = 4) -> "MaskedCellBuffer":
+        """The same cells with every region of fewer than `min_cells` cells invalidated (ec_regions' sieve-only form: no label is
+        ever written).  GDAL's sieve merges such a patch into its largest neighbour; this one drops it."""
+        return MaskedCellBuffer(self._buf, _regions(self._buf, self._mask, self.len(), cols, connectivity, min_cells, EC_REGIONS_ROOT, False))
 
     def put_window(self, cols: int, window, tile: "MaskedCellBuffer", window_size) -> None:
         """CellBuffer.put_window for values and mask in one launch."""

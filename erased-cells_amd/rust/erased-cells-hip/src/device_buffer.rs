@@ -744,6 +744,56 @@ impl CellBuffer {
     }
 }
 
+/// How [`CellBuffer::regions`] numbers the regions it keeps (`ec_regions_numbering`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum RegionNumbering {
+    /// The region's least row-major cell index plus one.
+    Root = EC_REGIONS_ROOT,
+    /// 1 .. K in increasing order of that index: `scipy.ndimage.label`'s numbering for a single class.
+    Dense = EC_REGIONS_DENSE,
+}
+
+/// `ec_regions` over `len` cells read as rows of `cols`, with the workspace from the library's pool: cells (or none: the mask
+/// form) and validity bytes (or null) in; the Int32 labels with the number of kept regions (or neither: the sieve-only form) and the
+/// validity bytes out.
+#[cfg(feature = "masked")]
+pub(crate) fn regions_raw(cells: Option<&CellBuffer>, mask: *const u8, len: usize, cols: usize, connectivity: u32, min_cells: u64,
+                          numbering: RegionNumbering, labels: bool) -> Result<(Option<(CellBuffer, u64)>, Mask)> {
+    assert!(if cols == 0 { len == 0 } else { len % cols == 0 }, "{len} cells are not rows of {cols} cells");
+    let out_mask = Mask::uninit(len);
+    let out = if labels { Some((CellBuffer::uninit(CellType::Int32, len), CellBuffer::uninit(CellType::UInt64, 1))) } else { None };
+    if len == 0 {
+        return Ok((out.map(|(l, _)| (l, 0)), out_mask));
+    }
+    let (t, src) = match cells {
+        Some(b) => (b.ct as u8, b.dev_ptr()),
+        None => (CellType::UInt8 as u8, std::ptr::null()),
+    };
+    let (dst, k) = match &out {
+        Some((l, k)) => (l.mem.ptr() as *mut i32, k.mem.ptr() as *mut u64),
+        None => (std::ptr::null_mut(), std::ptr::null_mut()),
+    };
+    check(unsafe {
+        ec_regions(t, src, mask, cols as u64, (len / cols) as u64, connectivity as i32, numbering as i32, min_cells, dst, out_mask.dev_ptr_mut(), k,
+                   std::ptr::null_mut(), stream())
+    })?;
+    Ok((out.map(|(l, k)| (l, download::<u64>(k.dev_ptr(), 1)[0])), out_mask))
+}
+
+#[cfg(feature = "masked")]
+impl CellBuffer {
+    /// The connected regions of equal cells of this buffer read as rows of `cols` cells (`ec_regions`; the rule is in
+    /// include/erased_cells.h): Int32 labels with their validity, and K, the number of regions kept.  "Equal" is equal bits,
+    /// `connectivity` is 4 or 8, a region of fewer than `min_cells` cells is invalidated.  The labels are a zone raster:
+    /// `zonal_stats(&labels, K + 1)`.
+    pub fn regions(&self, cols: usize, connectivity: u32, min_cells: u64, numbering: RegionNumbering) -> Result<(crate::MaskedCellBuffer, u64)> {
+        let (out, mask) = regions_raw(Some(self), std::ptr::null(), self.len, cols, connectivity, min_cells, numbering, true)?;
+        let (labels, k) = out.expect("asked for");
+        Ok((crate::MaskedCellBuffer::new(labels, mask), k))
+    }
+}
+
 /// Which neighbour [`CellBuffer::composite_rank`] keeps when `q * (count - 1)` is no whole position (`ec_rank_method`).
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 #[repr(i32)]

@@ -219,6 +219,21 @@ impl Mask {
     }
 }
 
+impl Mask {
+    /// The connected regions of the SET bytes of the mask read as rows of `cols` bytes (`ec_regions` without cells: every set byte
+    /// equals every other): Int32 labels with their validity, and K, as [`CellBuffer::regions`][crate::CellBuffer::regions] gives them.
+    pub fn regions(&self, cols: usize, connectivity: u32, min_cells: u64, numbering: crate::RegionNumbering) -> Result<(crate::MaskedCellBuffer, u64)> {
+        let (out, mask) = crate::regions_raw(None, self.dev_ptr(), self.len, cols, connectivity, min_cells, numbering, true)?;
+        let (labels, k) = out.expect("asked for");
+        Ok((crate::MaskedCellBuffer::new(labels, mask), k))
+    }
+
+    /// The mask without its regions of fewer than `min_cells` set bytes: `ec_regions`' sieve-only form, no label is ever written.
+    pub fn sieve(&self, cols: usize, min_cells: u64, connectivity: u32) -> Result<Mask> {
+        Ok(crate::regions_raw(None, self.dev_ptr(), self.len, cols, connectivity, min_cells, crate::RegionNumbering::Root, false)?.1)
+    }
+}
+
 impl Default for Mask {
     fn default() -> Self {
         Self::uninit(0)

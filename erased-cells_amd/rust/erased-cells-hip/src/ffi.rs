@@ -65,6 +65,10 @@ pub const EC_FOCAL_RANK_MAX_TAPS: u32 = 64;
 /// The longest side of a raster `ec_distance` takes (`EC_DISTANCE_MAX_SIDE`) and its `max_sq` of "no limit" (`EC_DISTANCE_UNLIMITED`).
 pub const EC_DISTANCE_MAX_SIDE: u64 = 32768;
 pub const EC_DISTANCE_UNLIMITED: u32 = 0xFFFF_FFFF;
+/// The longest side of a raster `ec_regions` takes (`EC_REGIONS_MAX_SIDE`) and its two numberings (`ec_regions_numbering`, taken as an `i32`).
+pub const EC_REGIONS_MAX_SIDE: u64 = 32768;
+pub const EC_REGIONS_ROOT: i32 = 0;
+pub const EC_REGIONS_DENSE: i32 = 1;
 /// The most zones one `ec_zonal_stats_*` call serves (`EC_ZONAL_MAX_ZONES`).
 pub const EC_ZONAL_MAX_ZONES: usize = 256;
 /// The most breaks one reclass table holds (`EC_RECLASS_MAX_BREAKS`), the size of its record and the flags of the record.
@@ -379,6 +383,11 @@ extern "C" {
     pub fn ec_distance_workspace_bytes(cols: u64, rows: u64) -> usize;
     pub fn ec_distance(mask: *const u8, cols: u64, rows: u64, max_sq: u32, out_type: ec_dtype, dst_or_null: *mut c_void,
                        dst_mask_or_null: *mut u8, workspace_dev_or_null: *mut c_void, stream: ec_stream) -> ec_status;
+    // connected-component labels and the sieve of a raster: i32 labels, validity bytes, the number of kept regions at a device address
+    pub fn ec_regions_workspace_bytes(cols: u64, rows: u64) -> usize;
+    pub fn ec_regions(t: ec_dtype, src_or_null: *const c_void, src_mask_or_null: *const u8, cols: u64, rows: u64, connectivity: i32,
+                      numbering: i32, min_cells: u64, dst_or_null: *mut i32, dst_mask_or_null: *mut u8, n_regions_dev_or_null: *mut u64,
+                      workspace_dev_or_null: *mut c_void, stream: ec_stream) -> ec_status;
     pub fn ec_composite_result_type(op: i32, t: ec_dtype) -> ec_dtype;
     pub fn ec_composite(op: i32, t: ec_dtype, layers: *const *const c_void, masks_or_null: *const *const u8, n_layers: i32, n: usize,
                         min_count: u32, dst: *mut c_void, dst_mask_or_null: *mut u8, aux_or_null: *mut u8, s: ec_stream) -> ec_status;

@@ -551,6 +551,22 @@ impl MaskedCellBuffer {
 }
 
 impl MaskedCellBuffer {
+    /// [`CellBuffer::regions`] over the cells whose mask byte is set: an invalid cell belongs to no region and joins none.
+    pub fn regions(&self, cols: usize, connectivity: u32, min_cells: u64, numbering: crate::RegionNumbering) -> Result<(Self, u64)> {
+        let (out, mask) = crate::regions_raw(Some(&self.0), self.1.dev_ptr(), self.0.len(), cols, connectivity, min_cells, numbering, true)?;
+        let (labels, k) = out.expect("asked for");
+        Ok((MaskedCellBuffer(labels, mask), k))
+    }
+
+    /// The same cells with every region of fewer than `min_cells` cells invalidated (`ec_regions`' sieve-only form).  GDAL's sieve
+    /// merges such a patch into its largest neighbour; this one drops it.
+    pub fn sieve(&self, cols: usize, min_cells: u64, connectivity: u32) -> Result<Self> {
+        let kept = crate::regions_raw(Some(&self.0), self.1.dev_ptr(), self.0.len(), cols, connectivity, min_cells, crate::RegionNumbering::Root, false)?.1;
+        Ok(MaskedCellBuffer(self.0.clone(), kept))
+    }
+}
+
+impl MaskedCellBuffer {
     /// [`CellBuffer::reclassify`] of the valid cells: a cell that is not valid receives the table's nodata value whatever it holds
     /// and stays invalid; a cell of a class the table drops becomes invalid.
     pub fn reclassify(&self, table: &crate::ReclassTable) -> Result<Self> {

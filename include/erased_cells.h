@@ -1032,6 +1032,64 @@ ec_status ec_distance(const uint8_t *mask, uint64_t cols, uint64_t rows, uint32_
                       void *dst_or_null, uint8_t *dst_mask_or_null, void *workspace_dev_or_null, ec_stream stream);
 
 /* ---------------------------------------------------------------- *
+ * Regions: connected-component labels and the sieve of a raster — the contiguous patches of one class, the single clouds, lakes
+ * or fields (GDAL's gdal_sieve and gdal_polygonize, GRASS' and terra's clump, scipy.ndimage.label): the step between cleaning a
+ * class raster and summarising it by zone.  The reference has nothing of the kind.
+ *
+ * The rule.  src is a row-major raster of cols x rows cells of cell type t, src_mask_or_null its validity bytes.
+ * 1 <= cols, rows <= EC_REGIONS_MAX_SIDE, so n = cols * rows <= 2^30.
+ *   Validity.      Cell i is VALID iff there is no mask or mask[i] != 0.
+ *   The mask form. With src_or_null == NULL (a mask is then required) every valid cell counts as equal to every other: the
+ *                  regions of the mask itself.
+ *   Equality.      Otherwise two cells are EQUAL iff their bits are equal — ec_focal_majority's rule, and equality under the total
+ *                  order: -0.0 and +0.0 differ, a NaN equals only the same NaN.  Only the cell's WIDTH matters.
+ *   Connectivity.  connectivity 4: cells (y, x) and (y', x') are NEIGHBOURS iff |y - y'| + |x - x'| == 1; connectivity 8: iff
+ *                  max(|y - y'|, |x - x'|) == 1.  The raster does not wrap: (y, cols - 1) and (y + 1, 0) are not neighbours.
+ *   Regions.       Valid cells are CONNECTED iff a chain of neighbouring, valid, pairwise equal cells joins them.  A REGION is a
+ *                  maximal connected set, its SIZE its cell count, its ROOT the least row-major index among its cells.
+ *   The sieve.     A region is KEPT iff size >= min_cells; 0 and 1 keep everything.
+ *   Numbering.     EC_REGIONS_ROOT: the label is root + 1.  EC_REGIONS_DENSE: the kept regions are numbered 1 .. K in increasing
+ *                  order of root, dropped regions take no number; for a single class this is scipy.ndimage.label's numbering.
+ *   Output.        dst is int32_t labels (EC_I32: a zone raster for ec_zonal_*, label 0 being "no region").  A valid cell of a
+ *                  kept region stores its label, with mask byte 1; every other cell all-zero bits and mask byte 0; the zero bits
+ *                  are written even where dst_mask_or_null is NULL.  n_regions_dev_or_null, when given, receives K, the number of
+ *                  kept regions under either numbering, as a uint64_t at a DEVICE address.  dst_or_null == NULL with a dst_mask
+ *                  is the sieve-only form: only the validity bytes are written (what "within" is to ec_distance).
+ * A pure function of the inputs: every cell has one right answer whatever the launch shape.
+ *
+ * The algorithm is the union-find labelling of Komura (2015) and Playne & Hawick (2018): tiles labelled in LDS, their seams
+ * joined with atomic minima, the trees flattened, the kept roots counted and numbered by a reduce-then-scan.  The workspace holds
+ * a parent and a size per cell (u32 each) and the scan's block sums.
+ * ---------------------------------------------------------------- */
+enum { EC_REGIONS_MAX_SIDE = 32768 };
+typedef enum { EC_REGIONS_ROOT = 0, EC_REGIONS_DENSE = 1 } ec_regions_numbering;
+/* Bytes of the workspace ec_regions wants for a raster of cols x rows cells; 0 for a shape it refuses.  Host only. */
+size_t ec_regions_workspace_bytes(uint64_t cols, uint64_t rows);
+/* The rule above.  Asynchronous, no synchronisation.  With a workspace of the caller's (ec_regions_workspace_bytes(cols, rows)
+ * bytes at a 16-byte-aligned DEVICE address, contents scrap afterwards) there is no allocation and the call is capturable (after
+ * ec_prepare_stream for a foreign stream); with workspace_dev_or_null == NULL the workspace comes from the library's
+ * stream-ordered pool and goes back to it on the same stream, exactly as ec_distance's — still asynchronous.  src_mask and dst_mask
+ * may sit at any byte address, src and dst are aligned to their cell type, n_regions_dev_or_null to 8 bytes.  Writes exactly
+ * cols * rows cells of dst, cols * rows bytes of dst_mask and the one uint64_t, each where given.
+ * Refused before any device work and without a device, writing nothing, each with its own text, in this order (EC_ERR_ARG unless
+ * said otherwise):
+ *   1. cols or rows is 0 or above EC_REGIONS_MAX_SIDE;
+ *   2. t is a bad cell type: EC_ERR_UNSUPPORTED_TYPE; checked only when src_or_null is given;
+ *   3. connectivity is neither 4 nor 8;
+ *   4. numbering is neither EC_REGIONS_ROOT nor EC_REGIONS_DENSE;
+ *   5. src_or_null and src_mask_or_null are both NULL;
+ *   6. dst_or_null, dst_mask_or_null and n_regions_dev_or_null are all NULL;
+ *   7. src, dst, n_regions_dev_or_null or the workspace is misaligned;
+ *   8. an output or the workspace overlaps an input or another output.
+ * Not here: a sharded form (a row-block shard needs its neighbours' seams); a per-region size table (up to 256 regions
+ * ec_zonal_stats gives it); merging a dropped region into its largest neighbour (GDAL's sieve does; this one invalidates); sides
+ * above EC_REGIONS_MAX_SIDE. */
+ec_status ec_regions(ec_dtype t, const void *src_or_null, const uint8_t *src_mask_or_null, uint64_t cols, uint64_t rows,
+                     int32_t connectivity, int32_t numbering, uint64_t min_cells,
+                     int32_t *dst_or_null, uint8_t *dst_mask_or_null, uint64_t *n_regions_dev_or_null,
+                     void *workspace_dev_or_null, ec_stream stream);
+
+/* ---------------------------------------------------------------- *
  * Test/bench support (not part of the reference surface).
  * ---------------------------------------------------------------- */
 /* x[i] = lo + splitmix64(seed ^ (base + i)) % (hi - lo + 1), t in {EC_U8, EC_U16, EC_F32}
