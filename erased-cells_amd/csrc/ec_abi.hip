@@ -392,6 +392,7 @@ extern "C" ec_status ec_mask_counts_device(const uint8_t* m, size_t n, uint64_t*
     Scratch sc;
     ec_status st = get_scratch(S(stream), &sc);
     if (st != EC_OK) return st;
+    const ScratchTurn turn(sc);  // the partials slot is min/max's and first difference's too: one call's launches at a time
     unsigned grid = 0;
     if (n > 0) {
         const size_t stream_bytes[1] = {n};

@@ -25,13 +25,16 @@ namespace ecd {
 // The sequence: as many workgroups per CU as are resident at once, at most PER_CU (the masked kernels of some types need more
 // than 64 VGPRs and fit 3, not 4, workgroups of 512 threads on a CU), so that the grid runs as ONE round — probed once per
 // family, cell type and shape, also when the plan then picks the cell-wise kernel ("unaligned_vector" off), which has no use
-// for the answer; the plan; the partials kernel; then the finalize launch unless one workgroup has written the result.
+// for the answer; the plan; the partials kernel; then the finalize launch unless one workgroup has written the result.  The call
+// holds the stream's turn at its scratch (ScratchTurn) while it queues the two, so host threads that share a stream cannot
+// interleave their launches on the partials slot.
 template <typename R, int U, int BLOCK, int PER_CU>
 ec_status launch_reduction(const void* p, const uint8_t* mask, size_t n, typename R::Out* out, hipStream_t s) {
     using T = typename R::Cell;
     Scratch sc;
     ec_status st = get_scratch(s, &sc);
     if (st != EC_OK) return st;
+    const ScratchTurn turn(sc);  // partials and finalize are one unit: no other host thread's partials land between them
     const T* tp = static_cast<const T*>(p);
     auto* partials = reinterpret_cast<typename R::Partial*>(sc.at(R::kPartials));
     unsigned grid = 0;
@@ -73,7 +76,8 @@ constexpr ResultSlot kResultStatsRecord = {kScratchStatsRecord, false, "hipMemcp
 
 // The one hand-over of the synchronous-result entry points: takes the stream's turn at its scratch (host threads that share a
 // stream take turns, so no call sees another's result words), has `run(sc, where)` queue the kernels whose last one writes
-// `bytes` bytes at `where`, waits for the stream and leaves them in `out`.  Nothing of the call is in flight on return.
+// `bytes` bytes at `where`, waits for the stream and leaves them in `out`.  Nothing of the call is in flight on return.  The
+// asynchronous entry points that `run` calls find the turn taken by their own thread and do not take it again (ScratchTurn).
 // (Polling the stream with hipStreamQuery before blocking was tried for the 5 µs kernels of fixture-sized rasters: 19.5 µs per
 // ec_min_max call against 15.1 µs — hipStreamSynchronize's own wait is the faster one; profiles/r04/sync_result_latency.txt.)
 template <typename Run>
@@ -81,7 +85,7 @@ ec_status sync_result(hipStream_t s, const ResultSlot& rs, void* out, size_t byt
     Scratch sc;
     ec_status st = get_scratch(s, &sc);
     if (st != EC_OK) return st;
-    std::lock_guard<std::mutex> turn(*sc.mu);
+    const ScratchTurn turn(sc);
     const bool zero_copy = rs.mapped && sc.host_dev;
     int64_t* where = zero_copy ? sc.host_dev : sc.at(rs.slot);
     st = run(sc, where);

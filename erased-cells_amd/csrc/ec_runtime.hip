@@ -221,7 +221,8 @@ ec_status get_scratch(hipStream_t s, Scratch* out) {
         if (st != EC_OK) return st;
         // the accumulator words (kScratchAcc) start at zero, the result words before them too; every kernel that uses an
         // accumulator leaves it at zero again
-        st = check_hip(hipMemset(own->dev + kScratchResult.word, 0, (kScratchAcc.end() - kScratchResult.word) * sizeof(int64_t)), "hipMemset(scratch)");
+        // (on the stream the scratch is for: every kernel that reads these words is queued on it, behind this)
+        st = check_hip(hipMemsetAsync(own->dev + kScratchResult.word, 0, (kScratchAcc.end() - kScratchResult.word) * sizeof(int64_t), s), "hipMemsetAsync(scratch)");
         if (st != EC_OK) return st;
         st = check_hip(hipHostMalloc(reinterpret_cast<void**>(&own->host), 4 * sizeof(int64_t), hipHostMallocDefault),
                        "hipHostMalloc(scratch)");

@@ -233,10 +233,13 @@ inline unsigned grid_capped(size_t blocks, int bpc) {
     return static_cast<unsigned>(blocks < cap ? blocks : cap);
 }
 
-// Per-(device, stream) scratch for reduction partials (device) and results (pinned host).  Launches that use the
-// partials are ordered by the stream itself; `mu` serialises the synchronous-result entry points (sync_result,
-// ec_reduce_launch.hpp), which read a result slot after waiting for the stream — two host threads sharing one stream
-// therefore take turns instead of racing on it.
+// Per-(device, stream) scratch for reduction partials (device) and results (pinned host).  The stream orders the LAUNCHES
+// that use a slot, not the CALLS that make them: a two-launch reduction queues a partials kernel and then a finalize kernel
+// that reads the same slot, and a second host thread on the same stream could queue its own partials between the two.  `mu`
+// is therefore the stream's turn at its scratch (ScratchTurn below): every call that queues more than one launch on a slot —
+// launch_reduction, the two-launch ec_mask_counts_device — holds it while it queues them, and the synchronous-result entry
+// points (sync_result, ec_reduce_launch.hpp) hold it until they have read their result words.  Host threads that share a
+// stream take turns; threads on streams of their own never meet.
 //
 // The layout of Scratch::dev, in 64-bit words: every slot is named here and nowhere else.
 constexpr int kStatsRecordWords = 8;  // one ec_moments (64 bytes); a Moments partial (ec_reduce_kernels.hpp) is no larger
@@ -265,6 +268,32 @@ struct Scratch {
     int64_t* at(const ScratchSlot& slot) const { return dev + slot.word; }
 };
 ec_status get_scratch(hipStream_t s, Scratch* out);
+
+// The calling thread's turn at a stream's scratch: locks sc.mu for the guard's lifetime, unless this thread holds that very
+// mutex already — sync_result calls the asynchronous entry points under it, and std::mutex is not recursive.  No allocation,
+// no synchronisation with the device: a turn lasts as long as queueing the call's launches does (capturable).
+inline thread_local const std::mutex* t_scratch_turn = nullptr;  // the mutex this thread holds through a ScratchTurn, if any
+class ScratchTurn {
+  public:
+    explicit ScratchTurn(const Scratch& sc) {
+        if (t_scratch_turn == sc.mu) return;  // the caller up the stack has the turn
+        sc.mu->lock();
+        mu_ = sc.mu;
+        outer_ = t_scratch_turn;
+        t_scratch_turn = sc.mu;
+    }
+    ~ScratchTurn() {
+        if (!mu_) return;
+        t_scratch_turn = outer_;
+        mu_->unlock();
+    }
+    ScratchTurn(const ScratchTurn&) = delete;
+    ScratchTurn& operator=(const ScratchTurn&) = delete;
+
+  private:
+    std::mutex* mu_ = nullptr;
+    const std::mutex* outer_ = nullptr;
+};
 
 // Workgroups of `kernel` (BLOCK threads, no dynamic LDS) that fit on one CU at a time, at most `want`.
 template <typename K>
