@@ -325,6 +325,11 @@ ec_status check_zonal_host_args(const char* who, ec_dtype t, const void* p, cons
                                 int32_t n_zones, const void* stats_out);
 ec_status zonal_records_host(ec_dtype t, const void* p, const uint8_t* mask, ec_dtype zt, const void* zones, size_t n, int32_t n_zones,
                              ec_moments* recs, ec_stream stream);
+// The same two of the table family (ec_zonal_table.hip): ec_zonal_table_compute's refusals and its records on the host.
+ec_status check_zonal_table_host_args(const char* who, ec_dtype t, const void* p, const uint8_t* mask, ec_dtype zt, const void* zones, size_t n,
+                                      int32_t n_zones, const void* stats_out);
+ec_status zonal_table_records_host(ec_dtype t, const void* p, const uint8_t* mask, ec_dtype zt, const void* zones, size_t n, int32_t n_zones,
+                                   ec_moments* recs, ec_stream stream);
 
 // binary arithmetic, one translation unit per op
 template <int OP>

@@ -962,3 +962,37 @@ extern "C" ec_status ec_sharded_zonal_stats(ec_shard_group* g, ec_dtype t, const
     }
     return EC_OK;
 }
+
+// The same over the table family (ec_zonal_table_device per shard, workspace and records from the shard's pool): up to
+// EC_ZONAL_TABLE_MAX_ZONES zones, the fold unchanged.
+extern "C" ec_status ec_sharded_zonal_table(ec_shard_group* g, ec_dtype t, const void* const* p, const uint8_t* const* masks_or_null, ec_dtype zt,
+                                            const void* const* zones, const size_t* n, int32_t n_zones, void* stats_out) {
+    ec_status st = check_group(g, "ec_sharded_zonal_table");
+    if (st != EC_OK) return st;
+    if (!p || !zones || !n || !stats_out) return set_error(EC_ERR_ARG, "ec_sharded_zonal_table: null argument");
+    // the whole-call refusals of ec_zonal_table_compute first (n_zones, the types), on no cells
+    if ((st = check_zonal_table_host_args("ec_sharded_zonal_table", t, nullptr, nullptr, zt, nullptr, 0, n_zones, stats_out)) != EC_OK) return st;
+    if ((st = check_col(g, "ec_sharded_zonal_table", "p", p, n)) != EC_OK) return st;
+    if ((st = check_col(g, "ec_sharded_zonal_table", "zones", zones, n)) != EC_OK) return st;
+    if (masks_or_null && (st = check_col(g, "ec_sharded_zonal_table", "masks", masks_or_null, n)) != EC_OK) return st;
+    for (int i = 0; i < g->n; ++i)  // a shard's cell count against the kind's bound
+        if ((st = check_zonal_table_host_args("ec_sharded_zonal_table", t, p[i], nullptr, zt, zones[i], n[i], n_zones, stats_out)) != EC_OK) return st;
+    std::lock_guard<std::mutex> lk(g->call_mu);
+    const size_t nz = static_cast<size_t>(n_zones);
+    std::vector<ec_moments> recs(static_cast<size_t>(g->n) * nz);  // shard-major
+    st = for_each_shard(g, [&](int i) {
+        return zonal_table_records_host(t, p[i], masks_or_null ? masks_or_null[i] : nullptr, zt, zones[i], n[i], n_zones, &recs[static_cast<size_t>(i) * nz],
+                                        g->streams[i]);
+    });
+    const std::string keep = last_error_text();
+    const ec_status deferred = take_deferred(g);
+    if (deferred != EC_OK) return deferred;
+    if (st != EC_OK) return set_error_text(st, keep);
+    std::vector<ec_moments> of_zone(static_cast<size_t>(g->n));
+    ec_stats* out = static_cast<ec_stats*>(stats_out);
+    for (size_t z = 0; z < nz; ++z) {
+        for (int i = 0; i < g->n; ++i) of_zone[static_cast<size_t>(i)] = recs[static_cast<size_t>(i) * nz + z];
+        if ((st = ec_stats_fold(of_zone.data(), g->n, out + z)) != EC_OK) return st;
+    }
+    return EC_OK;
+}

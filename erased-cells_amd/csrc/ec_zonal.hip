@@ -11,24 +11,12 @@
 #include "ec_lattice.hpp"
 #include "ec_runtime.hpp"
 #include "ec_stats_fold.hpp"
+#include "ec_zonal_host.hpp"
 #include "ec_zonal_kernels.hpp"
 
 namespace ecd {
 
 static_assert(EC_ZONAL_MAX_ZONES == ecz::kMaxZones, "the plan header restates the C ABI's limit");
-static_assert(EC_U8 == 0 && EC_U16 == 1 && EC_I32 == 6, "ec_zonal_plan.hpp names the zone types by their codes");
-
-// f(cell_tag<ZT>) for the zone type zt (checked before: one of the three)
-template <typename F>
-static ec_status with_zone_type(int zt, F&& f) {
-    switch (zt) {
-        case EC_U8: return f(ecl::cell_tag<uint8_t>{});
-        case EC_U16: return f(ecl::cell_tag<uint16_t>{});
-        case EC_I32: return f(ecl::cell_tag<int32_t>{});
-    }
-    return kTypeChecked;
-}
-
 // The launch sequence of launch_reduction (ec_reduce_launch.hpp) with what differs here: a second stream that every launch
 // has (the zone ids, whose alignment the plan's `residue1` covers beside the mask's), the tables' dynamic LDS, the partials in
 // the caller's workspace, one finalize workgroup per zone.  ecz::kPerCu workgroups per CU: not probed — the LDS of four

@@ -536,6 +536,12 @@ public:
     // this buffer as a zone raster, each cell replaced by table[id] (ec_zonal_broadcast): a cell whose id is outside
     // 0 .. table.len() - 1 is zero and not valid in the result.  Defined below MaskedCellBuffer.
     MaskedCellBuffer broadcast(const CellBuffer& table) const;
+    // zonal_stats for up to EC_ZONAL_TABLE_MAX_ZONES zones (ec_zonal_table_compute; the rule is in include/erased_cells.h): the
+    // n_zones ec_stats as one vector — a million Stats objects is not an interface; Stats(v[z]) wraps one
+    std::vector<ec_stats> zonal_table(const CellBuffer& zones, int32_t n_zones) const { return zonal_table_of(*this, nullptr, zones, n_zones); }
+    // broadcast for a table of up to EC_ZONAL_TABLE_MAX_ZONES cells, read from device memory (ec_zonal_lookup).  Defined below
+    // MaskedCellBuffer.
+    MaskedCellBuffer lookup(const CellBuffer& table) const;
     // each cell replaced by the value of its class among the table's breaks, in one pass (ec_reclass; the rule is in
     // include/erased_cells.h).  The table must have no dropped class and no nodata value (those are MaskedCellBuffer's, below).
     CellBuffer reclassify(const class ReclassTable& table) const;
@@ -549,6 +555,14 @@ public:
         check(ec_zonal_stats_compute(static_cast<ec_dtype>(values.ct_), values.ptr(), mask_or_null, static_cast<ec_dtype>(zones.ct_), zones.ptr(), values.n_,
                                      n_zones, out.data(), current_stream()));
         return std::vector<Stats>(out.begin(), out.end());
+    }
+    static std::vector<ec_stats> zonal_table_of(const CellBuffer& values, const uint8_t* mask_or_null, const CellBuffer& zones, int32_t n_zones) {
+        if (zones.n_ != values.n_) throw Error(EC_ERR_LENGTH, "zonal_table: the zone raster and the values differ in length");
+        if (n_zones < 1 || n_zones > EC_ZONAL_TABLE_MAX_ZONES) throw Error(EC_ERR_ARG, "zonal_table: n_zones is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES");
+        std::vector<ec_stats> out(static_cast<size_t>(n_zones));
+        check(ec_zonal_table_compute(static_cast<ec_dtype>(values.ct_), values.ptr(), mask_or_null, static_cast<ec_dtype>(zones.ct_), zones.ptr(), values.n_,
+                                     n_zones, out.data(), current_stream()));
+        return out;
     }
     template <typename T> std::vector<T> to_vec() const {  // buffer.rs:175-185
         CellBuffer r = convert(CellEncoding<T>::cell_type());
@@ -1018,6 +1032,8 @@ public:
     }
     // CellBuffer::zonal_stats over the valid cells: a masked-out cell belongs to no zone, whatever it holds
     std::vector<Stats> zonal_stats(const CellBuffer& zones, int32_t n_zones) const { return CellBuffer::zonal_stats_of(buf_, mask_.ptr(), zones, n_zones); }
+    // CellBuffer::zonal_table over the valid cells
+    std::vector<ec_stats> zonal_table(const CellBuffer& zones, int32_t n_zones) const { return CellBuffer::zonal_table_of(buf_, mask_.ptr(), zones, n_zones); }
     // CellBuffer::reclassify of the valid cells: a cell that is not valid receives the table's nodata value whatever it holds and stays
     // invalid; a cell of a class the table drops becomes invalid.  The table must have been built with a nodata value.
     MaskedCellBuffer reclassify(const class ReclassTable& table) const;
@@ -1258,6 +1274,15 @@ inline MaskedCellBuffer CellBuffer::broadcast(const CellBuffer& table) const {
     Mask m(n_);
     check(ec_zonal_broadcast(static_cast<ec_dtype>(ct_), ptr(), n_, static_cast<int32_t>(table.n_), static_cast<ec_dtype>(table.ct_), table.ptr(), out.ptr(),
                              m.ptr(), current_stream()));
+    return MaskedCellBuffer(std::move(out), std::move(m));
+}
+
+inline MaskedCellBuffer CellBuffer::lookup(const CellBuffer& table) const {
+    if (table.n_ < 1 || table.n_ > size_t(EC_ZONAL_TABLE_MAX_ZONES)) throw Error(EC_ERR_ARG, "lookup: the table is not of 1 .. EC_ZONAL_TABLE_MAX_ZONES cells");
+    CellBuffer out(table.ct_, n_);
+    Mask m(n_);
+    check(ec_zonal_lookup(static_cast<ec_dtype>(ct_), ptr(), n_, static_cast<int32_t>(table.n_), static_cast<ec_dtype>(table.ct_), table.ptr(), out.ptr(),
+                          m.ptr(), current_stream()));
     return MaskedCellBuffer(std::move(out), std::move(m));
 }
 
@@ -1841,6 +1866,19 @@ public:
         check(ec_sharded_zonal_stats(grp_->raw(), static_cast<ec_dtype>(ct_), p.data(), mask ? m.data() : nullptr, static_cast<ec_dtype>(zones.ct_), z.data(),
                                      lens_.data(), n_zones, out.data()));
         return std::vector<Stats>(out.begin(), out.end());
+    }
+    // CellBuffer::zonal_table of the whole raster (ec_sharded_zonal_table): up to EC_ZONAL_TABLE_MAX_ZONES zones, the fold unchanged
+    std::vector<ec_stats> zonal_table(const ShardedCellBuffer& zones, int32_t n_zones, const ShardedCellBuffer* mask = nullptr) const {
+        if (zones.lens_ != lens_) throw Error(EC_ERR_LENGTH, "the zone raster must be sharded identically");
+        if (mask && (mask->ct_ != CellType::UInt8 || mask->lens_ != lens_)) throw Error(EC_ERR_LENGTH, "the mask must be UInt8 and sharded identically");
+        if (n_zones < 1 || n_zones > EC_ZONAL_TABLE_MAX_ZONES) throw Error(EC_ERR_ARG, "zonal_table: n_zones is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES");
+        std::vector<ec_stats> out(static_cast<size_t>(n_zones));
+        std::vector<const void*> p(ptrs_.begin(), ptrs_.end()), z(zones.ptrs_.begin(), zones.ptrs_.end());
+        std::vector<const uint8_t*> m;
+        if (mask) for (void* q : mask->ptrs_) m.push_back(static_cast<const uint8_t*>(q));
+        check(ec_sharded_zonal_table(grp_->raw(), static_cast<ec_dtype>(ct_), p.data(), mask ? m.data() : nullptr, static_cast<ec_dtype>(zones.ct_), z.data(),
+                                     lens_.data(), n_zones, out.data()));
+        return out;
     }
     template <typename T> std::vector<T> to_vec() const {  // gather; T must be the buffer's own cell type
         if (CellEncoding<T>::cell_type() != ct_) throw NarrowingError(ct_, CellEncoding<T>::cell_type());

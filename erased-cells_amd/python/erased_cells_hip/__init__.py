@@ -10,7 +10,7 @@
 `tuned`    `with tuned(knob=value, ...)`: knobs of ec_tune_set for a block, put back on exit
 """
 from . import _ffi, fused, raster, wire
-from ._ffi import EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES, EC_ZONAL_MAX_ZONES, EcError, NarrowingError, build, lib, tuned
+from ._ffi import EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES, EC_ZONAL_MAX_ZONES, EC_ZONAL_TABLE_MAX_ZONES, EcError, NarrowingError, build, lib, tuned
 from .buffer import (ADD, CAST_MODES, CELL_TYPES, COMPOSITE_OPS, CT_NAMES, DIV, FOCAL_OPS, MUL, NP_DTYPES, RANK_METHODS, SUB, CellBuffer, CellValue, DeviceMem,
                      Float32, Float64, Int8, Int16, Int32, Int64, Mask, MaskedCellBuffer, NoData, ReclassTable, Stats, UInt8,
                      UInt16, UInt32, UInt64, ParseError, can_fit_into, cell_type_from_str, cell_type_of,

@@ -31,6 +31,7 @@ EC_COMPOSITE_MAX_LAYERS, EC_COMPOSITE_NONE = 64, 255
 EC_RANK_LOWER, EC_RANK_UPPER = range(2)  # ec_rank_method
 EC_RANK_MAX_DEN = 65535
 EC_ZONAL_MAX_ZONES = 256
+EC_ZONAL_TABLE_MAX_ZONES = 1 << 24
 EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES = 255, 4384
 EC_RECLASS_HAS_NODATA, EC_RECLASS_DROPS = 1, 2  # ec_reclass_table.flags
 EC_DISTANCE_MAX_SIDE, EC_DISTANCE_UNLIMITED = 32768, 0xFFFFFFFF  # ec_distance: the longest side, max_sq of "no limit"
@@ -217,6 +218,11 @@ SIGNATURES = {
     "ec_zonal_stats_compute": (I32, [C.c_uint8, VP, U8P, C.c_uint8, VP, SZ, I32, VP, VP]),
     "ec_sharded_zonal_stats": (I32, [VP, C.c_uint8, PVP, PVP, C.c_uint8, PVP, PSZ, I32, VP]),
     "ec_zonal_broadcast": (I32, [C.c_uint8, VP, SZ, I32, C.c_uint8, VP, VP, U8P, VP]),
+    "ec_zonal_table_workspace_bytes": (SZ, [C.c_uint8, I32]),
+    "ec_zonal_table_device": (I32, [C.c_uint8, VP, U8P, C.c_uint8, VP, SZ, I32, VP, VP, VP]),
+    "ec_zonal_table_compute": (I32, [C.c_uint8, VP, U8P, C.c_uint8, VP, SZ, I32, VP, VP]),
+    "ec_sharded_zonal_table": (I32, [VP, C.c_uint8, PVP, PVP, C.c_uint8, PVP, PSZ, I32, VP]),
+    "ec_zonal_lookup": (I32, [C.c_uint8, VP, SZ, I32, C.c_uint8, VP, VP, U8P, VP]),
     "ec_reclass_table_build": (I32, [C.c_uint8, C.c_uint8, VP, I32, I32, C.c_uint8, PV, U8P, PV, VP]),
     "ec_reclass": (I32, [C.c_uint8, VP, U8P, SZ, C.c_uint8, VP, VP, U8P, VP]),
     "ec_sharded_reclass": (I32, [VP, C.c_uint8, PVP, PVP, PSZ, C.c_uint8, PVP, PVP, PVP]),

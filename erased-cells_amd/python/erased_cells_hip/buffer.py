@@ -21,7 +21,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_COMPOSITE_MAX_LAYERS, EC_DISTANCE_UNLIMITED, EC_REGIONS_DENSE, EC_REGIONS_ROOT, EC_RANK_LOWER, EC_RANK_MAX_DEN, EC_RANK_UPPER, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_ZONAL_MAX_ZONES, EC_RECLASS_DROPS, EC_RECLASS_HAS_NODATA, EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES, EC_RESAMPLE_BILINEAR, EcError, EcReclassTable, EcStats, EcValue, check, lib
+from ._ffi import EC_CAST_AS, EC_CAST_ROUND, EC_COMPOSITE_MAX_LAYERS, EC_DISTANCE_UNLIMITED, EC_REGIONS_DENSE, EC_REGIONS_ROOT, EC_RANK_LOWER, EC_RANK_MAX_DEN, EC_RANK_UPPER, EC_CMP_EQ, EC_CMP_GE, EC_CMP_GT, EC_CMP_LE, EC_CMP_LT, EC_CMP_NE, EC_ERR_ARG, EC_FOCAL_MAX, EC_FOCAL_MEAN, EC_FOCAL_MIN, EC_FOCAL_NORMALIZE, EC_FOCAL_RADIUS_CAP, EC_FOCAL_SUM, EC_FOCAL_WHOLE, EC_RESAMPLE_AVERAGE, EC_ZONAL_MAX_ZONES, EC_ZONAL_TABLE_MAX_ZONES, EC_RECLASS_DROPS, EC_RECLASS_HAS_NODATA, EC_RECLASS_MAX_BREAKS, EC_RECLASS_TABLE_BYTES, EC_RESAMPLE_BILINEAR, EcError, EcReclassTable, EcStats, EcValue, check, lib
 
 # CellType (src/ctype.rs:11-20; order of with_ct!, src/lib.rs:89-98)
 UInt8, UInt16, UInt32, UInt64, Int8, Int16, Int32, Int64, Float32, Float64 = range(10)
@@ -786,6 +786,28 @@ class CellBuffer:
         check(lib().ec_zonal_broadcast(self.ct, self.mem.ptr, self.n, table.n, table.ct, table.mem.ptr, out.mem.ptr, om.ptr, _stream))
         return MaskedCellBuffer(out, Mask(self.n, om))
 
+    def zonal_table(self, zones: "CellBuffer", n_zones: int) -> np.ndarray:
+        """`zonal_stats` for up to EC_ZONAL_TABLE_MAX_ZONES (2^24) zones — the K + 1 labels of `regions`, a UInt16 parcel raster — as
+        ONE numpy structured array of `n_zones` rows with the fields count, min, max, sum, mean and stddev (ec_zonal_table_compute;
+        the rule, whose Float and 64-bit sums are truncated fixed-point sums independent of any order, is in include/erased_cells.h).
+        `per_patch = ndvi.zonal_table(labels, K + 1); per_patch["mean"]`."""
+        return _zonal_table(self, None, zones, n_zones)
+
+    def lookup(self, table, cell_type: Optional[int] = None) -> "MaskedCellBuffer":
+        """`broadcast` for a table of up to EC_ZONAL_TABLE_MAX_ZONES cells, read from device memory (ec_zonal_lookup): each cell
+        replaced by `table[id]`; a cell whose id is outside 0 .. len(table) - 1 is zero and not valid in the result.
+        `anomaly = ndvi - labels.lookup(per_patch["mean"])`."""
+        if not isinstance(table, CellBuffer):
+            a = np.asarray(table)
+            table = CellBuffer.from_vec(a.astype(NP_DTYPES[cell_type]) if cell_type is not None else a)
+        elif cell_type is not None and table.ct != cell_type:
+            raise EcError(EC_ERR_ARG, f"lookup: the table is {CT_NAMES[table.ct]}, not {CT_NAMES[cell_type]}")
+        if not 1 <= table.n <= EC_ZONAL_TABLE_MAX_ZONES:
+            raise EcError(EC_ERR_ARG, f"lookup: a table of {table.n} cells, not within 1 .. EC_ZONAL_TABLE_MAX_ZONES ({EC_ZONAL_TABLE_MAX_ZONES})")
+        out, om = CellBuffer.empty(self.n, table.ct), DeviceMem(self.n)
+        check(lib().ec_zonal_lookup(self.ct, self.mem.ptr, self.n, table.n, table.ct, table.mem.ptr, out.mem.ptr, om.ptr, _stream))
+        return MaskedCellBuffer(out, Mask(self.n, om))
+
     def reclassify(self, table_or_breaks, values=None, right: bool = False, dtype: Optional[int] = None, valid=None, breaks_dtype: Optional[int] = None):
         """Each cell replaced by the value of its class among the breaks, in one pass (ec_reclass; the rule is in
         include/erased_cells.h): class c = the number of breaks <= the cell (`right`: < the cell), result `values[c]`.  Pass a
@@ -1267,6 +1289,10 @@ class MaskedCellBuffer:
         """`CellBuffer.zonal_stats` over the valid cells: a masked-out cell belongs to no zone, whatever it holds."""
         return _zonal_stats(self._buf, self._mask, zones, n_zones)
 
+    def zonal_table(self, zones: "CellBuffer", n_zones: int) -> np.ndarray:
+        """`CellBuffer.zonal_table` over the valid cells: a masked-out cell belongs to no zone, whatever it holds."""
+        return _zonal_table(self._buf, self._mask, zones, n_zones)
+
     def reclassify(self, table_or_breaks, values=None, right: bool = False, dtype: Optional[int] = None, valid=None, nodata=None,
                    breaks_dtype: Optional[int] = None) -> "MaskedCellBuffer":
         """`CellBuffer.reclassify` of the valid cells: a cell that is not valid receives `nodata` (default: 0) whatever it holds and stays
@@ -1388,6 +1414,44 @@ def _zonal_stats(buf: "CellBuffer", mask, zones, n_zones: int) -> list:
     check(lib().ec_zonal_stats_compute(buf.ct, buf.mem.ptr, mask.mem.ptr if mask is not None else None, zones.ct, zones.mem.ptr, buf.n,
                                        int(n_zones), out, _stream))
     return [Stats.from_ec(s) for s in out]
+
+
+# ec_stats as numpy sees it: the u64, two 16-byte ec_value (a type byte, padding, the payload in 8 bytes), three doubles
+_EC_STATS_DTYPE = np.dtype([("count", "<u8"), ("min_dtype", "u1"), ("min_pad", "V7"), ("min_bits", "<u8"), ("max_dtype", "u1"), ("max_pad", "V7"),
+                            ("max_bits", "<u8"), ("sum", "<f8"), ("mean", "<f8"), ("stddev", "<f8")])
+assert _EC_STATS_DTYPE.itemsize == C.sizeof(EcStats) == 64
+
+
+def stats_table(raw, ct: int) -> np.ndarray:
+    """An array of ec_stats (anything with their bytes) as a structured array with the fields count, min, max, sum, mean, stddev; min
+    and max in the numpy type of cell type `ct`."""
+    rows = np.frombuffer(raw, dtype=_EC_STATS_DTYPE)
+    value = NP_DTYPES[ct]
+    out = np.empty(rows.size, dtype=[("count", np.uint64), ("min", value), ("max", value), ("sum", np.float64), ("mean", np.float64), ("stddev", np.float64)])
+    for name in ("count", "sum", "mean", "stddev"):
+        out[name] = rows[name]
+    for name in ("min", "max"):  # the payload's low bytes are the value (little-endian union)
+        bits = np.ascontiguousarray(rows[name + "_bits"])
+        out[name] = bits.view(np.uint8).reshape(-1, 8)[:, :value.itemsize].copy().view(value).reshape(-1)
+    return out
+
+
+def _check_table_call(what: str, buf: "CellBuffer", zones, n_zones) -> None:
+    if isinstance(zones, MaskedCellBuffer) or not isinstance(zones, CellBuffer):
+        raise EcError(EC_ERR_ARG, f"{what}: the zone raster is a {type(zones).__name__}, not a CellBuffer")
+    if isinstance(n_zones, bool) or not isinstance(n_zones, (int, np.integer)) or not 1 <= n_zones <= EC_ZONAL_TABLE_MAX_ZONES:
+        raise EcError(EC_ERR_ARG, f"{what}: n_zones {n_zones!r} is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES ({EC_ZONAL_TABLE_MAX_ZONES})")
+    if zones.n != buf.n:
+        raise EcError(EC_ERR_ARG, f"{what}: the zone raster has {zones.n} cells, the values {buf.n}")
+
+
+def _zonal_table(buf: "CellBuffer", mask, zones, n_zones: int) -> np.ndarray:
+    """`n_zones` rows of statistics of `buf` under `mask` (or None) per zone of the CellBuffer `zones` (ec_zonal_table_compute)."""
+    _check_table_call("zonal_table", buf, zones, n_zones)
+    raw = np.empty(int(n_zones), dtype=_EC_STATS_DTYPE)
+    check(lib().ec_zonal_table_compute(buf.ct, buf.mem.ptr, mask.mem.ptr if mask is not None else None, zones.ct, zones.mem.ptr, buf.n,
+                                       int(n_zones), raw.ctypes.data, _stream))
+    return stats_table(raw, buf.ct)
 
 
 def _typed_array(what: str, xs, ct: Optional[int], default_for_numbers) -> np.ndarray:

@@ -399,6 +399,21 @@ class ShardGroup:
                                            (C.c_size_t * self.n)(*sb.lens), n_zones, out))
         return [B.Stats.from_ec(s) for s in out]
 
+    def zonal_table(self, sb: ShardedBuffer, zones: ShardedBuffer, n_zones: int, mask: ShardedBuffer = None):
+        """`CellBuffer.zonal_table` of the whole sharded raster (ec_sharded_zonal_table): up to EC_ZONAL_TABLE_MAX_ZONES zones, every
+        shard's records folded zone by zone on the host in shard order; one numpy structured array of `n_zones` rows."""
+        import numpy as np
+        from ._ffi import EC_ERR_ARG, EC_ZONAL_TABLE_MAX_ZONES, EcError
+        if list(zones.lens) != list(sb.lens) or (mask is not None and list(mask.lens) != list(sb.lens)):
+            raise EcError(EC_ERR_ARG, "zonal_table: the zone raster or the mask is not sharded like the values")
+        if isinstance(n_zones, bool) or not isinstance(n_zones, (int, np.integer)) or not 1 <= n_zones <= EC_ZONAL_TABLE_MAX_ZONES:
+            raise EcError(EC_ERR_ARG, f"zonal_table: n_zones {n_zones!r} is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES ({EC_ZONAL_TABLE_MAX_ZONES})")
+        n_zones = int(n_zones)   # the K of `regions`, a numpy maximum: as CellBuffer.zonal_table takes them
+        raw = np.empty(n_zones, dtype=B._EC_STATS_DTYPE)
+        check(lib().ec_sharded_zonal_table(self.handle, sb.ct, sb.ptrs, mask.ptrs if mask is not None else None, zones.ct, zones.ptrs,
+                                           (C.c_size_t * self.n)(*sb.lens), n_zones, raw.ctypes.data))
+        return B.stats_table(raw, sb.ct)
+
     def counts(self, mask: ShardedBuffer) -> tuple[int, int]:
         t, f = C.c_uint64(), C.c_uint64()
         check(lib().ec_sharded_counts(self.handle, mask.ptrs, (C.c_size_t * self.n)(*mask.lens), C.byref(t), C.byref(f)))

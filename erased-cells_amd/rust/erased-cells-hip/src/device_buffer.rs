@@ -973,6 +973,38 @@ impl CellBuffer {
         })?;
         Ok((out, mask))
     }
+
+    /// `ec_zonal_table_compute`: [`CellBuffer::zonal_stats`] for up to `EC_ZONAL_TABLE_MAX_ZONES` zones, over a per-zone table in
+    /// device memory.  `mask`: the device bytes of a mask of the same length, or null.
+    pub(crate) fn zonal_table_raw(&self, mask: *const u8, zones: &CellBuffer, n_zones: usize) -> Result<Vec<Stats>> {
+        assert_eq!(zones.len, self.len, "the zone raster and the values share one length");
+        assert!((1..=EC_ZONAL_TABLE_MAX_ZONES).contains(&n_zones), "1 .. {EC_ZONAL_TABLE_MAX_ZONES} zones, not {n_zones}");
+        let mut out = vec![Stats::blank(); n_zones];
+        check(unsafe {
+            ec_zonal_table_compute(self.ct as u8, self.dev_ptr(), mask, zones.ct as u8, zones.dev_ptr(), self.len, n_zones as i32,
+                                   out.as_mut_ptr() as *mut c_void, stream())
+        })?;
+        Ok(out.iter().map(Stats::from_ffi).collect())
+    }
+
+    /// [`CellBuffer::zonal_stats`] for up to `EC_ZONAL_TABLE_MAX_ZONES` zones — the labels of [`CellBuffer::regions`], a `UInt16` parcel
+    /// raster.  The rule, whose float and 64-bit sums are truncated fixed-point sums independent of any order, is at
+    /// `ec_zonal_table_device` in include/erased_cells.h.
+    pub fn zonal_table(&self, zones: &CellBuffer, n_zones: usize) -> Result<Vec<Stats>> {
+        self.zonal_table_raw(std::ptr::null(), zones, n_zones)
+    }
+
+    /// [`CellBuffer::broadcast`] for a table of up to `EC_ZONAL_TABLE_MAX_ZONES` cells, read from device memory (`ec_zonal_lookup`).
+    pub fn lookup(&self, table: &CellBuffer) -> Result<(CellBuffer, Mask)> {
+        assert!((1..=EC_ZONAL_TABLE_MAX_ZONES).contains(&table.len), "a table of 1 .. {EC_ZONAL_TABLE_MAX_ZONES} cells, not {}", table.len);
+        let out = Self::uninit(table.ct, self.len);
+        let mask = Mask::uninit(self.len);
+        check(unsafe {
+            ec_zonal_lookup(self.ct as u8, self.dev_ptr(), self.len, table.len as i32, table.ct as u8, table.dev_ptr(), out.mem.ptr(),
+                            mask.dev_ptr_mut(), stream())
+        })?;
+        Ok((out, mask))
+    }
 }
 
 /// The table of [`CellBuffer::reclassify`] for rasters of one cell type: built on the host (`ec_reclass_table_build`), uploaded once,

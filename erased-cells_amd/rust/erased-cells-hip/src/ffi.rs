@@ -71,6 +71,8 @@ pub const EC_REGIONS_ROOT: i32 = 0;
 pub const EC_REGIONS_DENSE: i32 = 1;
 /// The most zones one `ec_zonal_stats_*` call serves (`EC_ZONAL_MAX_ZONES`).
 pub const EC_ZONAL_MAX_ZONES: usize = 256;
+/// The most zones one `ec_zonal_table_*` / `ec_zonal_lookup` call serves (`EC_ZONAL_TABLE_MAX_ZONES`).
+pub const EC_ZONAL_TABLE_MAX_ZONES: usize = 1 << 24;
 /// The most breaks one reclass table holds (`EC_RECLASS_MAX_BREAKS`), the size of its record and the flags of the record.
 pub const EC_RECLASS_MAX_BREAKS: usize = 255;
 pub const EC_RECLASS_TABLE_BYTES: usize = 4384;
@@ -348,6 +350,16 @@ extern "C" {
                                   zt: ec_dtype, zones: *const *const c_void, n: *const usize, n_zones: i32, stats_out: *mut c_void) -> ec_status;
     pub fn ec_zonal_broadcast(zt: ec_dtype, zones: *const c_void, n: usize, n_zones: i32, t: ec_dtype, table_dev: *const c_void,
                               dst: *mut c_void, dst_mask_or_null: *mut u8, stream: ec_stream) -> ec_status;
+    // the same records over a per-zone table in global memory: up to EC_ZONAL_TABLE_MAX_ZONES zones, integer atomics only
+    pub fn ec_zonal_table_workspace_bytes(t: ec_dtype, n_zones: i32) -> usize;
+    pub fn ec_zonal_table_device(t: ec_dtype, p: *const c_void, mask_or_null: *const u8, zt: ec_dtype, zones: *const c_void, n: usize,
+                                 n_zones: i32, moments_dev: *mut c_void, workspace_dev: *mut c_void, stream: ec_stream) -> ec_status;
+    pub fn ec_zonal_table_compute(t: ec_dtype, p: *const c_void, mask_or_null: *const u8, zt: ec_dtype, zones: *const c_void, n: usize,
+                                  n_zones: i32, stats_out: *mut c_void, stream: ec_stream) -> ec_status;
+    pub fn ec_sharded_zonal_table(g: *mut ec_shard_group, t: ec_dtype, p: *const *const c_void, masks_or_null: *const *const u8,
+                                  zt: ec_dtype, zones: *const *const c_void, n: *const usize, n_zones: i32, stats_out: *mut c_void) -> ec_status;
+    pub fn ec_zonal_lookup(zt: ec_dtype, zones: *const c_void, n: usize, n_zones: i32, t: ec_dtype, table_dev: *const c_void,
+                           dst: *mut c_void, dst_mask_or_null: *mut u8, stream: ec_stream) -> ec_status;
     // a raster classified by break values: the table built on the host, uploaded by the caller, read by every launch
     pub fn ec_reclass_table_build(t: ec_dtype, bt: ec_dtype, breaks_host: *const c_void, n_breaks: i32, right: i32, dt: ec_dtype,
                                   values: *const ec_value, valid_or_null: *const u8, nodata_or_null: *const ec_value,

@@ -543,6 +543,11 @@ impl MaskedCellBuffer {
         self.0.zonal_stats_raw(self.1.dev_ptr(), zones, n_zones)
     }
 
+    /// [`CellBuffer::zonal_table`] over the valid cells: a masked-out cell belongs to no zone, whatever it holds.
+    pub fn zonal_table(&self, zones: &CellBuffer, n_zones: usize) -> Result<Vec<Stats>> {
+        self.0.zonal_table_raw(self.1.dev_ptr(), zones, n_zones)
+    }
+
     /// [`CellBuffer::broadcast`] as one value: `table[id]` where the zone raster's id names an entry of `table`, not valid elsewhere.
     pub fn broadcast(zones: &CellBuffer, table: &CellBuffer) -> Result<Self> {
         let (cells, mask) = zones.broadcast(table)?;

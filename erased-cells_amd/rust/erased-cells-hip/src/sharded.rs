@@ -350,6 +350,24 @@ impl ShardedCellBuffer<'_> {
         Ok(out.iter().map(Stats::from_ffi).collect())
     }
 
+    /// [`CellBuffer::zonal_table`] of the whole raster (`ec_sharded_zonal_table`): up to `EC_ZONAL_TABLE_MAX_ZONES` zones, the fold
+    /// of [`Self::zonal_stats`] unchanged.
+    pub fn zonal_table(&self, zones: &Self, n_zones: usize, mask: Option<&Self>) -> Result<Vec<Stats>> {
+        assert_eq!(zones.lens, self.lens, "the zone raster must be sharded identically");
+        assert!((1..=EC_ZONAL_TABLE_MAX_ZONES).contains(&n_zones), "1 .. {EC_ZONAL_TABLE_MAX_ZONES} zones, not {n_zones}");
+        if let Some(m) = mask {
+            assert_eq!(m.ct, CellType::UInt8, "a mask is UInt8 bytes");
+            assert_eq!(m.lens, self.lens, "the mask must be sharded identically");
+        }
+        let masks: Vec<*const u8> = mask.map_or(Vec::new(), |m| m.ptrs.iter().map(|p| *p as *const u8).collect());
+        let mut out = vec![Stats::blank(); n_zones];
+        check(unsafe {
+            ec_sharded_zonal_table(self.group.g, self.ct as u8, self.const_ptrs().as_ptr(), if mask.is_some() { masks.as_ptr() } else { ptr::null() },
+                                   zones.ct as u8, zones.const_ptrs().as_ptr(), self.lens.as_ptr(), n_zones as i32, out.as_mut_ptr() as *mut c_void)
+        })?;
+        Ok(out.iter().map(Stats::from_ffi).collect())
+    }
+
     /// [`CellBuffer::reclassify`] on every shard (no communication, fire-and-forget).  `tables`: the table's record on every
     /// shard's device — a `UInt8` buffer of `EC_RECLASS_TABLE_BYTES` per shard, uploaded by the caller ([`ShardGroup::scatter`] of the
     /// record's bytes repeated, one row of `EC_RECLASS_TABLE_BYTES` cells per shard) — for rasters of this cell type, results of `result_type`; `mask`: a `UInt8` raster of 0 / 1 bytes cut the

@@ -874,7 +874,8 @@ ec_status ec_sharded_stats(ec_shard_group *g, ec_dtype t, const void *const *p,
  *           No float atomics anywhere: the records are a pure function of the cells, the zones and the launch plan, and the
  *           same call twice gives the same bytes.
  * A zone with no cells gets the empty record (count 0, the sentinels' keys, zero sums, the call's pivot); n == 0 writes
- * n_zones empty records with pivot 0.0.  More than EC_ZONAL_MAX_ZONES zones: relabel in chunks and call again.
+ * n_zones empty records with pivot 0.0.  More than EC_ZONAL_MAX_ZONES zones: ec_zonal_table_* below (up to 2^24 zones; its kind-1
+ * sums follow another rule).
  * ---------------------------------------------------------------- */
 enum { EC_ZONAL_MAX_ZONES = 256 };
 /* Bytes of the workspace ec_zonal_stats_device wants for n_zones zones (a function of n_zones only); 0 for n_zones outside
@@ -908,6 +909,72 @@ ec_status ec_sharded_zonal_stats(ec_shard_group *g, ec_dtype t, const void *cons
  * sharded form: run it under ec_shard_group_foreach. */
 ec_status ec_zonal_broadcast(ec_dtype zt, const void *zones, size_t n, int32_t n_zones, ec_dtype t,
                              const void *table_dev, void *dst, uint8_t *dst_mask_or_null, ec_stream stream);
+
+/* ---------------------------------------------------------------- *
+ * Zonal statistics over a table in global memory: the same ec_moments records for up to 2^24 zones — the K labels of ec_regions,
+ * a UInt16 parcel raster — where ec_zonal_stats_* stops at EC_ZONAL_MAX_ZONES.  A second family beside the first, which keeps
+ * its cap, its refusals and its kind-1 sums; ec_stats_fold and the ec_stats layout are unchanged.
+ *
+ * Membership is ec_zonal_stats_device's rule unchanged: zt is EC_U8, EC_U16 or EC_I32; cell i belongs to zone z = zones[i] iff
+ * 0 <= z < n_zones and (there is no mask or mask[i] != 0); everything else contributes nothing, by a select and never by a
+ * multiplication.  n_zones may exceed what zt can hold (the records above the type's range are empty).
+ *
+ * Record z.  count, keys2, kind, dtype, reserved and the kind-0 sum and 128-bit sq are as ec_zonal_stats_device writes them:
+ * exact, independent of launch shape, shard cut and order; for n_zones <= EC_ZONAL_MAX_ZONES the kind-0 records are
+ * byte-identical to that call's.  Kind-1 records (u64, i64, f32, f64) DIFFER from that call's in s1 and s2, by construction:
+ *   pivot  the call's, as there: to_f64(p[0]) if n > 0 and that is finite, else 0.0, whatever p[0]'s mask byte or zone is.
+ *          d = to_f64(x) - pivot, one rounded subtraction.
+ *   s1     a truncated fixed-point sum, rounded once, defined per zone.  For the zone's deviations d_1 .. d_m, all finite:
+ *          d_j = m_j * 2^-1074 with an integer m_j (exact for every finite f64); L = the bit length of max |m_j|;
+ *          k = max(L - 63, 0); t_j = sign(m_j) * (|m_j| >> k) (truncation toward zero, |t_j| < 2^63); T = the exact sum of the
+ *          t_j; s1 = T * 2^(k - 1074) rounded to nearest-even f64: +0.0 when T == 0, +-infinity on overflow, as IEEE rounds.
+ *   s2     the same rule over w_j = fl(d_j * d_j), one f64 multiply rounded to nearest even (the largest w is fl(dmax * dmax)).
+ *          If any w_j is +infinity, s2 = +infinity.
+ *   If any d_j is NaN, s1 = s2 = the quiet NaN 0x7FF8000000000000.  Otherwise, with infinities among the d_j: s1 is +infinity or
+ *   -infinity for one sign and that NaN for both, s2 = +infinity.  An empty zone has zero sums.
+ * What follows: the sums do not depend on order, launch shape, the number of workgroups or how cells are grouped before they
+ * are added — permuting the cells of index >= 1 with their zones and mask leaves every byte.  When every d_j is a multiple of the
+ * zone's unit 2^(k - 1074) — all data whose deviations span fewer than 63 bits — the sums are the exact sums rounded once.
+ * Otherwise |s1 - sum d| < m * 2^(k - 1074) + 1/2 ulp(s1), at least 2^9 times tighter than the (m + 1) u sum|d| bound any order of
+ * f64 additions has.  No double rounding at finalize: T * 2^(k - 1074) is a multiple of 2^-1074, and a |T| < 2^53 converts exactly.
+ *
+ * n.  Kind 0 keeps ec_stats_device's limits.  Kind 1 refuses n > 2^32, which bounds |T| by 2^95.
+ *
+ * Not here: more than 2^24 zones; UInt32 or 64-bit ids; per-zone medians or histograms; a device-side fold to a table of
+ * means (the route back is the host fold, an upload and ec_zonal_lookup); a sharded ec_regions.
+ * ---------------------------------------------------------------- */
+enum { EC_ZONAL_TABLE_MAX_ZONES = 1 << 24 }; /* a condition, not a measurement: 2^24 records are 1 GiB, and every byte offset
+                                              * into the records and the workspace stays below 2^32 */
+/* Bytes of the workspace ec_zonal_table_device wants for n_zones zones of values of type t; 0 for a refused n_zones or type.
+ * Host only. */
+size_t ec_zonal_table_workspace_bytes(ec_dtype t, int32_t n_zones);
+/* n_zones ec_moments at DEVICE address moments_dev, record z for zone z.  Asynchronous, no allocation, no synchronisation,
+ * capturable (after ec_prepare_stream for a foreign stream); the per-zone table lives in the caller's workspace_dev
+ * (ec_zonal_table_workspace_bytes(t, n_zones) bytes, contents scrap afterwards).  n == 0 is legal: n_zones empty records with
+ * pivot 0.0.  Refused before any device work and without a device, each with its own text, in this order: n_zones outside
+ * 1 .. EC_ZONAL_TABLE_MAX_ZONES (EC_ERR_ARG); a bad t or zt (EC_ERR_UNSUPPORTED_TYPE); a null pointer (moments_dev,
+ * workspace_dev; p and zones unless n == 0); n above the kind's bound; moments_dev or workspace_dev not 16-byte aligned, or
+ * overlapping an input or each other (all EC_ERR_ARG).  A refused call writes nothing. */
+ec_status ec_zonal_table_device(ec_dtype t, const void *p, const uint8_t *mask_or_null, ec_dtype zt,
+                                const void *zones, size_t n, int32_t n_zones, void *moments_dev,
+                                void *workspace_dev, ec_stream stream);
+/* ec_zonal_table_device with its workspace and records from the library's stream-ordered pool, the records' download and
+ * ec_stats_fold once per zone: n_zones ec_stats at HOST address stats_out.  The same refusals but the workspace's and the
+ * alignment's.  Synchronous result. */
+ec_status ec_zonal_table_compute(ec_dtype t, const void *p, const uint8_t *mask_or_null, ec_dtype zt,
+                                 const void *zones, size_t n, int32_t n_zones, void *stats_out, ec_stream stream);
+/* The same over a sharded raster, columns as ec_sharded_zonal_stats: every shard's n_zones records come down and zone z's
+ * records fold in shard order by ec_stats_fold.  No collective: kind 0 equals the unsharded figures bit for bit; each shard's
+ * kind-1 record follows the rule above over that shard's cells and pivot.  Synchronous result. */
+ec_status ec_sharded_zonal_table(ec_shard_group *g, ec_dtype t, const void *const *p,
+                                 const uint8_t *const *masks_or_null, ec_dtype zt, const void *const *zones,
+                                 const size_t *n, int32_t n_zones, void *stats_out);
+/* ec_zonal_broadcast's rule, word for word, for 1 <= n_zones <= EC_ZONAL_TABLE_MAX_ZONES, with the table read from global
+ * memory: dst[i] = table[zones[i]] (bits copied) with mask byte 1; zero bits and mask byte 0 for an id of no zone, also where
+ * dst_mask_or_null is NULL.  Element-wise and asynchronous: any n, any cell offset; n == 0 is legal.  Refused as
+ * ec_zonal_broadcast refuses, with this family's cap. */
+ec_status ec_zonal_lookup(ec_dtype zt, const void *zones, size_t n, int32_t n_zones, ec_dtype t,
+                          const void *table_dev, void *dst, uint8_t *dst_mask_or_null, ec_stream stream);
 
 /* ---------------------------------------------------------------- *
  * Reclassification: a raster classified by break values in ONE pass — NDVI into vegetation classes, a DEM into elevation
@@ -1081,8 +1148,8 @@ size_t ec_regions_workspace_bytes(uint64_t cols, uint64_t rows);
  *   6. dst_or_null, dst_mask_or_null and n_regions_dev_or_null are all NULL;
  *   7. src, dst, n_regions_dev_or_null or the workspace is misaligned;
  *   8. an output or the workspace overlaps an input or another output.
- * Not here: a sharded form (a row-block shard needs its neighbours' seams); a per-region size table (up to 256 regions
- * ec_zonal_stats gives it); merging a dropped region into its largest neighbour (GDAL's sieve does; this one invalidates); sides
+ * Not here: a sharded form (a row-block shard needs its neighbours' seams); a per-region size table (the counts of
+ * ec_zonal_table_compute over the labels give it, for any K this call can return); merging a dropped region into its largest neighbour (GDAL's sieve does; this one invalidates); sides
  * above EC_REGIONS_MAX_SIDE. */
 ec_status ec_regions(ec_dtype t, const void *src_or_null, const uint8_t *src_mask_or_null, uint64_t cols, uint64_t rows,
                      int32_t connectivity, int32_t numbering, uint64_t min_cells,

@@ -12,7 +12,7 @@ the source with comment pairs
 This tool lists the marked ranges (the PROVENANCE table of INTEGRATION.md §2 is its `--table` output) and measures, per
 crate file, difflib similarity against every file of the reference — with the marked ranges removed and with them in —
 by characters and by lines, on the non-test part of both sides (the measure the round-2 review used).  `--record` keeps
-what the tests need of the reference in tests/golden/reference_provenance_regions.json (`RECORD` below): the line count of every reference source
+what the tests need of the reference in tests/golden/reference_provenance_zonal_table.json (`RECORD` below): the line count of every reference source
 file (for the citations) and, per crate file, its SHA-256 with the similarity measured for exactly that text.
 
     python tools/rust_provenance.py --table                                  # markdown table of the marked ranges
@@ -37,8 +37,9 @@ CRATE = os.path.join(ROOT, "erased-cells_amd", "rust", "erased-cells-hip", "src"
 # focal / convolve did, reference_provenance_focal.json the crate before composite did, reference_provenance_composite.json the crate
 # before the zonal statistics did, reference_provenance_zonal.json the crate before reclassify did, reference_provenance_reclass.json the crate before
 # composite_rank did, reference_provenance_composite_rank.json the crate before focal_rank / focal_majority did, reference_provenance_focal_rank.json the crate before
-# distance / within did, reference_provenance_distance.json the crate before regions / sieve did; all are kept as they were recorded).
-RECORD = os.path.join(ROOT, "tests", "golden", "reference_provenance_regions.json")
+# distance / within did, reference_provenance_distance.json the crate before regions / sieve did, reference_provenance_regions.json the crate before
+# zonal_table / lookup did; all are kept as they were recorded).
+RECORD = os.path.join(ROOT, "tests", "golden", "reference_provenance_zonal_table.json")
 OPEN = re.compile(r"^\s*// api-surface\(([^)]*)\):\s*(.*)$")
 CLOSE = re.compile(r"^\s*// end api-surface\s*$")
 
