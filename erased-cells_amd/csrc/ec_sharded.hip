@@ -46,6 +46,7 @@
 #include "ec_reclass_plan.hpp"
 #include "ec_runtime.hpp"
 #include "ec_worker.hpp"
+#include "ec_zonal_host.hpp"
 
 using namespace ecd;
 
@@ -928,71 +929,52 @@ extern "C" ec_status ec_sharded_stats(ec_shard_group* g, ec_dtype t, const void*
     return ec_stats_fold(recs.data(), g->n, stats_out);
 }
 
-// Zonal statistics of the whole raster (ec_zonal_stats_device per shard with a workspace from the shard's pool): every
-// shard's n_zones records come down, and zone z's records fold in shard order on the host, as ec_sharded_stats' do.  No
-// collective — kind 0 equals the unsharded figures bit for bit.
-extern "C" ec_status ec_sharded_zonal_stats(ec_shard_group* g, ec_dtype t, const void* const* p, const uint8_t* const* masks_or_null, ec_dtype zt,
-                                            const void* const* zones, const size_t* n, int32_t n_zones, void* stats_out) {
-    ec_status st = check_group(g, "ec_sharded_zonal_stats");
+// Zonal statistics of the whole raster, the body of both families' sharded forms: `check` is the family's *_host_args (first on
+// no cells: the whole-call refusals of its compute form, n_zones and the types), shard_check(i) refuses shard i's cell count,
+// `records` is the family's *_records_host (workspace and records from the shard's pool).  Every shard's n_zones records come
+// down, and zone z's records fold in shard order on the host, as ec_sharded_stats' do.  No collective — kind 0 equals the
+// unsharded figures bit for bit.
+using ZonalHostCheck = ec_status (*)(const char*, ec_dtype, const void*, const uint8_t*, ec_dtype, const void*, size_t, int32_t, const void*);
+using ZonalRecordsHost = ec_status (*)(ec_dtype, const void*, const uint8_t*, ec_dtype, const void*, size_t, int32_t, ec_moments*, ec_stream);
+
+template <typename SHARD_CHECK>
+static ec_status sharded_zonal(const char* who, ZonalHostCheck check, SHARD_CHECK&& shard_check, ZonalRecordsHost records, ec_shard_group* g, ec_dtype t,
+                               const void* const* p, const uint8_t* const* masks_or_null, ec_dtype zt, const void* const* zones, const size_t* n,
+                               int32_t n_zones, void* stats_out) {
+    ec_status st = check_group(g, who);
     if (st != EC_OK) return st;
-    if (!p || !zones || !n || !stats_out) return set_error(EC_ERR_ARG, "ec_sharded_zonal_stats: null argument");
-    // the whole-call refusals of ec_zonal_stats_compute first (n_zones, the types), on no cells
-    if ((st = check_zonal_host_args("ec_sharded_zonal_stats", t, nullptr, nullptr, zt, nullptr, 0, n_zones, stats_out)) != EC_OK) return st;
-    if ((st = check_col(g, "ec_sharded_zonal_stats", "p", p, n)) != EC_OK) return st;
-    if ((st = check_col(g, "ec_sharded_zonal_stats", "zones", zones, n)) != EC_OK) return st;
-    if (masks_or_null && (st = check_col(g, "ec_sharded_zonal_stats", "masks", masks_or_null, n)) != EC_OK) return st;
+    if (!p || !zones || !n || !stats_out) return set_error(EC_ERR_ARG, "%s: null argument", who);
+    if ((st = check(who, t, nullptr, nullptr, zt, nullptr, 0, n_zones, stats_out)) != EC_OK) return st;
+    if ((st = check_col(g, who, "p", p, n)) != EC_OK) return st;
+    if ((st = check_col(g, who, "zones", zones, n)) != EC_OK) return st;
+    if (masks_or_null && (st = check_col(g, who, "masks", masks_or_null, n)) != EC_OK) return st;
     for (int i = 0; i < g->n; ++i)
-        if ((st = check_stats_cells("ec_sharded_zonal_stats", i, t, n[i], "shard it finer")) != EC_OK) return st;
+        if ((st = shard_check(i)) != EC_OK) return st;
     std::lock_guard<std::mutex> lk(g->call_mu);
     const size_t nz = static_cast<size_t>(n_zones);
     std::vector<ec_moments> recs(static_cast<size_t>(g->n) * nz);  // shard-major
     st = for_each_shard(g, [&](int i) {
-        return zonal_records_host(t, p[i], masks_or_null ? masks_or_null[i] : nullptr, zt, zones[i], n[i], n_zones, &recs[static_cast<size_t>(i) * nz],
-                                  g->streams[i]);
+        return records(t, p[i], masks_or_null ? masks_or_null[i] : nullptr, zt, zones[i], n[i], n_zones, &recs[static_cast<size_t>(i) * nz], g->streams[i]);
     });
     const std::string keep = last_error_text();
     const ec_status deferred = take_deferred(g);
     if (deferred != EC_OK) return deferred;
     if (st != EC_OK) return set_error_text(st, keep);
-    std::vector<ec_moments> of_zone(static_cast<size_t>(g->n));
-    ec_stats* out = static_cast<ec_stats*>(stats_out);
-    for (size_t z = 0; z < nz; ++z) {
-        for (int i = 0; i < g->n; ++i) of_zone[static_cast<size_t>(i)] = recs[static_cast<size_t>(i) * nz + z];
-        if ((st = ec_stats_fold(of_zone.data(), g->n, out + z)) != EC_OK) return st;
-    }
-    return EC_OK;
+    return fold_zone_records(recs.data(), g->n, nz, stats_out);
 }
 
-// The same over the table family (ec_zonal_table_device per shard, workspace and records from the shard's pool): up to
-// EC_ZONAL_TABLE_MAX_ZONES zones, the fold unchanged.
+// ec_zonal_stats_device per shard: up to EC_ZONAL_MAX_ZONES zones.
+extern "C" ec_status ec_sharded_zonal_stats(ec_shard_group* g, ec_dtype t, const void* const* p, const uint8_t* const* masks_or_null, ec_dtype zt,
+                                            const void* const* zones, const size_t* n, int32_t n_zones, void* stats_out) {
+    return sharded_zonal("ec_sharded_zonal_stats", check_zonal_host_args,
+                         [&](int i) { return check_stats_cells("ec_sharded_zonal_stats", i, t, n[i], "shard it finer"); }, zonal_records_host, g, t, p,
+                         masks_or_null, zt, zones, n, n_zones, stats_out);
+}
+
+// ec_zonal_table_device per shard: up to EC_ZONAL_TABLE_MAX_ZONES zones; a shard's cell count against the kind's bound.
 extern "C" ec_status ec_sharded_zonal_table(ec_shard_group* g, ec_dtype t, const void* const* p, const uint8_t* const* masks_or_null, ec_dtype zt,
                                             const void* const* zones, const size_t* n, int32_t n_zones, void* stats_out) {
-    ec_status st = check_group(g, "ec_sharded_zonal_table");
-    if (st != EC_OK) return st;
-    if (!p || !zones || !n || !stats_out) return set_error(EC_ERR_ARG, "ec_sharded_zonal_table: null argument");
-    // the whole-call refusals of ec_zonal_table_compute first (n_zones, the types), on no cells
-    if ((st = check_zonal_table_host_args("ec_sharded_zonal_table", t, nullptr, nullptr, zt, nullptr, 0, n_zones, stats_out)) != EC_OK) return st;
-    if ((st = check_col(g, "ec_sharded_zonal_table", "p", p, n)) != EC_OK) return st;
-    if ((st = check_col(g, "ec_sharded_zonal_table", "zones", zones, n)) != EC_OK) return st;
-    if (masks_or_null && (st = check_col(g, "ec_sharded_zonal_table", "masks", masks_or_null, n)) != EC_OK) return st;
-    for (int i = 0; i < g->n; ++i)  // a shard's cell count against the kind's bound
-        if ((st = check_zonal_table_host_args("ec_sharded_zonal_table", t, p[i], nullptr, zt, zones[i], n[i], n_zones, stats_out)) != EC_OK) return st;
-    std::lock_guard<std::mutex> lk(g->call_mu);
-    const size_t nz = static_cast<size_t>(n_zones);
-    std::vector<ec_moments> recs(static_cast<size_t>(g->n) * nz);  // shard-major
-    st = for_each_shard(g, [&](int i) {
-        return zonal_table_records_host(t, p[i], masks_or_null ? masks_or_null[i] : nullptr, zt, zones[i], n[i], n_zones, &recs[static_cast<size_t>(i) * nz],
-                                        g->streams[i]);
-    });
-    const std::string keep = last_error_text();
-    const ec_status deferred = take_deferred(g);
-    if (deferred != EC_OK) return deferred;
-    if (st != EC_OK) return set_error_text(st, keep);
-    std::vector<ec_moments> of_zone(static_cast<size_t>(g->n));
-    ec_stats* out = static_cast<ec_stats*>(stats_out);
-    for (size_t z = 0; z < nz; ++z) {
-        for (int i = 0; i < g->n; ++i) of_zone[static_cast<size_t>(i)] = recs[static_cast<size_t>(i) * nz + z];
-        if ((st = ec_stats_fold(of_zone.data(), g->n, out + z)) != EC_OK) return st;
-    }
-    return EC_OK;
+    return sharded_zonal("ec_sharded_zonal_table", check_zonal_table_host_args, [&](int i) {
+        return check_zonal_table_host_args("ec_sharded_zonal_table", t, p[i], nullptr, zt, zones[i], n[i], n_zones, stats_out);
+    }, zonal_table_records_host, g, t, p, masks_or_null, zt, zones, n, n_zones, stats_out);
 }

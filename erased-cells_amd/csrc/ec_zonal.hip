@@ -65,26 +65,17 @@ static ec_status check_zonal_args(const char* who, ec_dtype t, const void* p, co
     bool bad_type = false;
     const char* why = ecz::stats_refusal(n_zones, ecl::size_of(t), zt, p, mask, zones, n, stats_max_cells(t), out, out_bytes, workspace,
                                          caller_workspace, &bad_type);
-    if (!why) return EC_OK;
-    return set_error(bad_type ? EC_ERR_UNSUPPORTED_TYPE : EC_ERR_ARG, "%s: %s (dtype %d, zones of dtype %d, %zu cells, %d zones)", who, why, int(t),
-                     int(zt), n, int(n_zones));
+    return zonal_refused(who, why, bad_type, t, zt, n, n_zones);
 }
 
-// The n_zones records of one launch at HOST address recs: workspace and records from the stream-ordered pool, the launch, the
-// download, the stream drained.  Arguments checked by the caller (check_zonal_args with a workspace of its own making).
+// The n_zones records of one launch at HOST address recs (records_host).  Arguments checked by the caller (check_zonal_args with
+// a workspace of its own making).
 ec_status zonal_records_host(ec_dtype t, const void* p, const uint8_t* mask, ec_dtype zt, const void* zones, size_t n, int32_t n_zones,
                              ec_moments* recs, ec_stream stream) {
-    ec_status st = ensure_ready();
-    if (st != EC_OK) return st;
-    const size_t ws = ecz::workspace_bytes(n_zones), out = size_t(n_zones) * sizeof(ec_moments);
-    void* block = nullptr;  // the workspace, then the records (ws is a multiple of 64)
-    if ((st = ec_alloc_async(&block, ws + out, stream)) != EC_OK) return st;
-    ec_moments* recs_dev = reinterpret_cast<ec_moments*>(static_cast<char*>(block) + ws);
-    st = dispatch_zonal(t, p, mask, zt, zones, n, n_zones, recs_dev, block, S(stream));
-    if (st == EC_OK) st = check_hip(hipMemcpyAsync(recs, recs_dev, out, hipMemcpyDeviceToHost, S(stream)), "hipMemcpyAsync(zonal records)");
-    const ec_status freed = ec_free_async(block, stream);
-    const ec_status synced = check_hip(hipStreamSynchronize(S(stream)), "hipStreamSynchronize");
-    return st != EC_OK ? st : freed != EC_OK ? freed : synced;
+    auto dispatch = [&](ec_moments* recs_dev, void* workspace, hipStream_t s) {
+        return dispatch_zonal(t, p, mask, zt, zones, n, n_zones, recs_dev, workspace, s);
+    };
+    return records_host(ecz::workspace_bytes(n_zones), "hipMemcpyAsync(zonal records)", n_zones, recs, stream, dispatch);
 }
 
 // Arguments of the forms that make their own workspace: the device form's refusals without the workspace's.
@@ -93,24 +84,14 @@ ec_status check_zonal_host_args(const char* who, ec_dtype t, const void* p, cons
     return check_zonal_args(who, t, p, mask, zt, zones, n, n_zones, stats_out, 0, nullptr, false);
 }
 
-template <typename W, typename ZT>
-static ec_status launch_broadcast(const void* zones, const void* table, size_t n, int32_t n_zones, void* dst, uint8_t* dst_mask, hipStream_t s) {
-    constexpr size_t CPL = ecz::broadcast_cpl(sizeof(W), sizeof(ZT));
-    const ZT* zp = static_cast<const ZT*>(zones);
-    const W* tab = static_cast<const W*>(table);
-    W* out = static_cast<W*>(dst);
-    const bool aligned = aligned_to(zones, CPL * sizeof(ZT)) && aligned_to(dst, CPL * sizeof(W)) && (!dst_mask || aligned_to(dst_mask, CPL));
-    auto launch = [&](auto maskout) -> ec_status {
-        constexpr bool MASKOUT = decltype(maskout)::value;
-        if (aligned)
-            return split_launch(ecz::broadcast_tiles(n, CPL), "zonal_broadcast", [&](size_t first, unsigned grid) {
-                k_zonal_broadcast<W, ZT, MASKOUT, ecz::kBroadcastU><<<grid, kBlock, 0, s>>>(zp, tab, n_zones, out, dst_mask, n, first);
-            });
-        k_zonal_broadcast_cellwise<W, ZT, MASKOUT><<<grid_capped((n + kBlock - 1) / kBlock, 8), kBlock, 0, s>>>(zp, tab, n_zones, out, dst_mask, n);
-        return check_launch("zonal_broadcast");
-    };
-    return dst_mask ? launch(std::true_type{}) : launch(std::false_type{});
-}
+// launch_gather's kernels: the table staged in LDS
+struct BroadcastKernels {
+    static constexpr const char* what = "zonal_broadcast";
+    template <typename W, typename ZT, bool MASKOUT>
+    static constexpr auto vector = k_zonal_broadcast<W, ZT, MASKOUT, ecz::kBroadcastU>;
+    template <typename W, typename ZT, bool MASKOUT>
+    static constexpr auto cellwise = k_zonal_broadcast_cellwise<W, ZT, MASKOUT>;
+};
 
 }  // namespace ecd
 
@@ -131,26 +112,13 @@ extern "C" ec_status ec_zonal_stats_compute(ec_dtype t, const void* p, const uin
                                             int32_t n_zones, void* stats_out, ec_stream stream) {
     ec_status st = check_zonal_host_args("ec_zonal_stats_compute", t, p, mask_or_null, zt, zones, n, n_zones, stats_out);
     if (st != EC_OK) return st;
-    std::vector<ec_moments> recs(static_cast<size_t>(n_zones));
-    if ((st = zonal_records_host(t, p, mask_or_null, zt, zones, n, n_zones, recs.data(), stream)) != EC_OK) return st;
-    ec_stats* out = static_cast<ec_stats*>(stats_out);
-    for (int32_t z = 0; z < n_zones; ++z)
-        if ((st = ec_stats_fold(&recs[static_cast<size_t>(z)], 1, out + z)) != EC_OK) return st;
-    return EC_OK;
+    return zonal_compute(n_zones, stats_out,
+                         [&](ec_moments* recs) { return zonal_records_host(t, p, mask_or_null, zt, zones, n, n_zones, recs, stream); });
 }
 
 extern "C" ec_status ec_zonal_broadcast(ec_dtype zt, const void* zones, size_t n, int32_t n_zones, ec_dtype t, const void* table_dev, void* dst,
                                         uint8_t* dst_mask_or_null, ec_stream stream) {
     bool bad_type = false;
-    if (const char* why = ecz::broadcast_refusal(n_zones, ecl::size_of(t), zt, zones, table_dev, n, dst, dst_mask_or_null, &bad_type))
-        return set_error(bad_type ? EC_ERR_UNSUPPORTED_TYPE : EC_ERR_ARG, "ec_zonal_broadcast: %s (dtype %d, zones of dtype %d, %zu cells, %d zones)", why,
-                         int(t), int(zt), n, int(n_zones));
-    if (n == 0) return EC_OK;
-    const ec_status st = ensure_ready();
-    if (st != EC_OK) return st;
-    return ecl::with_cell_width(ecl::size_of(t), [&](auto w) {
-        return with_zone_type(zt, [&](auto z) {
-            return launch_broadcast<ecl::cell_t<decltype(w)>, ecl::cell_t<decltype(z)>>(zones, table_dev, n, n_zones, dst, dst_mask_or_null, S(stream));
-        });
-    }, kTypeChecked);
+    const char* why = ecz::broadcast_refusal(n_zones, ecl::size_of(t), zt, zones, table_dev, n, dst, dst_mask_or_null, &bad_type);
+    return zonal_gather_call<BroadcastKernels>("ec_zonal_broadcast", why, bad_type, zt, zones, n, n_zones, t, table_dev, dst, dst_mask_or_null, stream);
 }

@@ -2,9 +2,10 @@
 // ec_zonal_broadcast (include/erased_cells.h).  A reduction whose destination is data-dependent: cell i goes to the record
 // of zone zones[i].
 //
-// The frame is the reductions' (ec_reduce_plan.hpp): the launch shape of reduce_plan(), a read-only stream at 16 B of values
-// per lane with the zone ids (and mask bytes) of the same cells beside them, every load nt, the peeled head and the ragged
-// tail folded cell by cell by workgroup 0, a cell-wise kernel for "unaligned_vector" off, one Moments per workgroup AND ZONE
+// The frame is the reductions' (ec_reduce_plan.hpp), walked by zonal_walk (below, shared with the table family): the
+// launch shape of reduce_plan(), a read-only stream at 16 B of values per lane with the zone ids (and mask bytes) of the same
+// cells beside them, every load nt, the peeled head and the ragged tail folded cell by cell by workgroup 0, a cell-wise kernel
+// for "unaligned_vector" off.  ZoneScan is the walk's visitor; what it leaves is this family's: one Moments per workgroup AND ZONE
 // in the caller's workspace, one finalize workgroup per zone over block_fold — or, with a one-workgroup grid, the records
 // written by that workgroup itself.  What is folded is ec_stats_kernels.hpp's: CellMoments, FoldMoments, write_record.
 //
@@ -14,9 +15,9 @@
 //      and nothing else happens: on a spatially coherent zone raster that is nearly every group.
 //   2. Otherwise the wave flushes — the lanes' records go to the tables by wave_scatter — and folds the group slot by slot:
 //      wave_scatter over the 64 cells of a slot.
-//   wave_scatter loops over the DISTINCT ids of the wave's lanes: the id of the first lane not yet served (readlane), the
-//   ballot of the lanes that hold it, their contributions folded by wave_fold with every other lane SELECTED to the identity
-//   (never multiplied by 0), and lane 0 adds the result to the table entry.  Iterations = distinct ids.
+//   wave_scatter serves the DISTINCT ids of the wave's lanes a round each (wave_rounds): the contributions of the lanes that
+//   hold the id folded by wave_fold with every other lane SELECTED to the identity (never multiplied by 0), and lane 0 adds the
+//   result to the table entry.
 // Kind 1 sums live in one {s1, s2} table per wave that only its wave touches, with plain LDS reads and writes.  So the order
 // of the additions is fixed: the wave's own program order, lanes by wave_fold's butterfly, then waves in wave order (the
 // workgroup's epilogue), then workgroups in workgroup order (the finalize fold).  No float atomics: the records are a pure
@@ -35,13 +36,165 @@
 
 namespace ecd {
 
-static_assert(ecz::kBlock == kBlock && ecz::kWave == kWave, "the plan header restates the workgroup of the cell-wise kernels");
 static_assert(sizeof(Moments) == ecz::kPartialBytes && sizeof(ec_moments) == ecz::kRecordBytes, "the workspace is sized in Moments");
+static_assert(ecz::kBlock == kBlock && ecz::kWave == kWave, "the plan header restates the workgroup of the cell-wise kernels");
+
+// ---- The frame both zonal families share (this one: tables in LDS; ec_zonal_table_kernels.hpp: a table in global memory): the zone
+// ids, the walk over the cells, the rounds over a wave's distinct ids, the gather dst[i] = table[zones[i]].  What a family does with
+// a cell is its visitor's; nothing in the frame knows the families.
 
 // zone ids are u8, u16 (never negative) or i32; a cell belongs to zone z iff 0 <= z < n_zones
 template <typename ZT>
 __device__ __forceinline__ int32_t zone_id(ZT z) { return static_cast<int32_t>(z); }
 __device__ __forceinline__ bool zone_in_range(int32_t z, int32_t n_zones) { return static_cast<uint32_t>(z) < static_cast<uint32_t>(n_zones); }
+
+// The whole wave, converged: f(zid, member, first) once for each DISTINCT id among the lanes that hold something (`has`; lane l
+// holds z) — the id of the first lane not yet served (readlane), `member`: this lane holds it, `first`: that lane.  Rounds =
+// distinct ids.  Which lane then issues anything is the caller's.
+template <typename F>
+__device__ __forceinline__ void wave_rounds(bool has, int32_t z, F&& f) {
+    uint64_t rest = __builtin_amdgcn_ballot_w64(has);
+    while (rest) {
+        const int first = __builtin_ctzll(rest);
+        const int32_t zid = __builtin_amdgcn_readlane(z, first);
+        const bool member = has && z == zid;
+        rest &= ~__builtin_amdgcn_ballot_w64(member);
+        f(zid, member, first);
+    }
+}
+
+// The edges of the walk below, by workgroup 0, a cell per lane: the ragged tail [first_cell, n) of the peeled streams and the `head`
+// cells in front of them.  visitor.cell(in, x, m, z) is called by whole waves, converged: the loop bounds are the workgroup's; a lane
+// past the end gets in == false, and its dummy load is at `first`, an address inside the buffer.
+template <typename T, typename ZT, bool MASKED, typename V>
+__device__ __forceinline__ void zonal_walk_edges(const T* __restrict__ p, const uint8_t* __restrict__ mask, const ZT* __restrict__ zones, size_t first_cell,
+                                                 size_t n, unsigned head, V& visitor) {
+    if (blockIdx.x != 0) return;
+    for (size_t first = first_cell; first < n; first += ecz::kBlock) {
+        const size_t i = first + threadIdx.x;
+        const bool in = i < n;
+        const size_t at = in ? i : first;
+        visitor.cell(in, ld_cell(p + at), MASKED ? ld_cell(mask + at) : uint8_t(1), zone_id(ld_cell(zones + at)));
+    }
+    for (unsigned first = 0; first < head; first += ecz::kBlock) {
+        const unsigned h = first + threadIdx.x;
+        const bool in = h < head;
+        const ptrdiff_t at = -static_cast<ptrdiff_t>(in ? h : first) - 1;
+        visitor.cell(in, ld_cell(p + at), MASKED ? ld_cell(mask + at) : uint8_t(1), zone_id(ld_cell(zones + at)));
+    }
+}
+
+// The walk of one workgroup over the values p, their zone ids and (MASKED) mask bytes, in the reductions' frame: the grid-stride
+// tiles of reduce_plan(), U 16-byte groups of values per lane with the ids and mask bytes of the same cells beside them, every load
+// nt; then zonal_walk_edges.  `head`: the cells peeled so that the value loads start 16-byte aligned (reduce_head); the bits above
+// bit 7 (the launch's load policy) are not looked at.
+// Every visitor.group<MASKED, CPL, ZT>(in, x, m, z) and visitor.cell(in, x, m, z) is called by whole waves, converged: the loop
+// bounds are the workgroup's; a lane past the end gets in == false, and its dummy load is at `first`, inside the buffer.
+template <typename T, typename ZT, bool MASKED, int U, typename V>
+__device__ __forceinline__ void zonal_walk(const T* __restrict__ p, const uint8_t* __restrict__ mask, const ZT* __restrict__ zones, size_t n, unsigned head,
+                                           V& visitor) {
+    head &= 0xffu;
+    p += head;
+    zones += head;
+    if constexpr (MASKED) mask += head;
+    n -= head;
+    constexpr int CPL = 16 / sizeof(T);
+    using TV = cells<T, CPL>;
+    using MV = cells<uint8_t, CPL>;
+    using ZV = cells<ZT, CPL>;
+    const size_t ngroups = n / CPL;
+    constexpr size_t TILE = size_t(ecz::kBlock) * U;
+    const size_t ntiles = (ngroups + TILE - 1) / TILE;
+    for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const size_t base = tile * TILE + threadIdx.x;
+        TV x[U] = {};
+        MV m[U] = {};
+        ZV z[U] = {};
+        bool in[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const size_t g = base + size_t(j) * ecz::kBlock;
+            in[j] = g < ngroups;
+            if (in[j]) {
+                x[j] = load_cells<true, T, CPL>(p + g * CPL);
+                z[j] = load_cells<true, ZT, CPL>(zones + g * CPL);
+                if constexpr (MASKED) m[j] = load_cells<true, uint8_t, CPL>(mask + g * CPL);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) visitor.template group<MASKED, CPL, ZT>(in[j], x[j], m[j], z[j]);
+    }
+    zonal_walk_edges<T, ZT, MASKED>(p, mask, zones, ngroups * CPL, n, head, visitor);
+}
+
+// Same walk, cell-wise loads: any alignment (the plan's other outcome, "unaligned_vector" off).
+template <typename T, typename ZT, bool MASKED, typename V>
+__device__ __forceinline__ void zonal_walk_cellwise(const T* __restrict__ p, const uint8_t* __restrict__ mask, const ZT* __restrict__ zones, size_t n,
+                                                    V& visitor) {
+    const size_t stride = size_t(gridDim.x) * ecz::kBlock;
+    for (size_t first = size_t(blockIdx.x) * ecz::kBlock; first < n; first += stride) {
+        const size_t i = first + threadIdx.x;
+        const bool in = i < n;
+        const size_t at = in ? i : first;
+        visitor.cell(in, p[at], MASKED ? mask[at] : uint8_t(1), zone_id(zones[at]));
+    }
+}
+
+// ---- The gather dst[i] = tab[zones[i]], bits copied by cell width W, mask byte 1; an id that belongs to no zone gives all-zero
+// bits and mask byte 0.  The map kernels' frame (k_map, ec_map_kernels.hpp: one workgroup per tile of U groups per lane, two
+// fronts, nt loads and stores, the ragged tail by workgroup 0).  `tab`: the n_zones cells wherever the kernel keeps them.
+template <typename W, typename ZT, bool MASKOUT>
+__device__ __forceinline__ void zonal_gather_cell(const ZT* __restrict__ zones, const W* tab, int32_t n_zones, W* __restrict__ dst,
+                                                  uint8_t* __restrict__ dst_mask, size_t i) {
+    const int32_t zk = zone_id(ld_cell(zones + i));
+    const bool ok = zone_in_range(zk, n_zones);
+    st_cell<W>(ok ? tab[ok ? zk : 0] : W(0), dst + i);
+    if constexpr (MASKOUT) st_cell<uint8_t>(ok ? 1 : 0, dst_mask + i);
+}
+
+template <typename W, typename ZT, bool MASKOUT, int U>
+__device__ __forceinline__ void zonal_gather(const ZT* __restrict__ zones, const W* tab, int32_t n_zones, W* __restrict__ dst,
+                                             uint8_t* __restrict__ dst_mask, size_t n, size_t first_tile) {
+    constexpr int CPL = 16 / max_of<sizeof(W), sizeof(ZT)>::value;
+    using DV = vec<W, CPL>;
+    using MV = vec<uint8_t, CPL>;
+    const size_t ngroups = n / CPL;
+    constexpr size_t TILE = size_t(kBlock) * U;
+    const size_t base = two_front_tile(first_tile) * TILE + threadIdx.x;
+    cells<ZT, CPL> z[U] = {};
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+        const size_t g = base + size_t(j) * kBlock;
+        if (g < ngroups) z[j] = load_cells<true, ZT, CPL>(zones + g * CPL);
+    }
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+        const size_t g = base + size_t(j) * kBlock;
+        if (g >= ngroups) continue;
+        DV o;
+        MV m;
+#pragma unroll
+        for (int k = 0; k < CPL; ++k) {
+            const int32_t zk = zone_id(z[j][k]);
+            const bool ok = zone_in_range(zk, n_zones);
+            o[k] = ok ? tab[ok ? zk : 0] : W(0);
+            m[k] = ok ? 1 : 0;
+        }
+        nt_store(o, reinterpret_cast<DV*>(dst) + g);
+        if constexpr (MASKOUT) mask_store(m, reinterpret_cast<MV*>(dst_mask) + g);
+    }
+    if (first_group(first_tile))
+        for (size_t i = ngroups * CPL + threadIdx.x; i < n; i += kBlock) zonal_gather_cell<W, ZT, MASKOUT>(zones, tab, n_zones, dst, dst_mask, i);
+}
+
+template <typename W, typename ZT, bool MASKOUT>
+__device__ __forceinline__ void zonal_gather_cellwise(const ZT* __restrict__ zones, const W* tab, int32_t n_zones, W* __restrict__ dst,
+                                                      uint8_t* __restrict__ dst_mask, size_t n) {
+    const size_t stride = size_t(gridDim.x) * kBlock;
+    for (size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) zonal_gather_cell<W, ZT, MASKOUT>(zones, tab, n_zones, dst, dst_mask, i);
+}
+
+// ---- This family
 
 // The first cell of a lane's group, and the group moved up by one cell: the slot loop of ZoneScan::group stays a loop (one copy
 // of wave_scatter per group, not one per slot) without indexing registers by a loop variable.
@@ -133,12 +286,7 @@ struct ZoneScan {
     // The whole wave, converged.  Lane l contributes `mine` to zone z iff valid; z is in range wherever valid is set.
     __device__ __forceinline__ void wave_scatter(bool valid, int32_t z, const Moments& mine) {
         const Moments id = moments_identity<T>();
-        uint64_t rest = __builtin_amdgcn_ballot_w64(valid);
-        while (rest) {
-            const int first = __builtin_ctzll(rest);
-            const int32_t zid = __builtin_amdgcn_readlane(z, first);
-            const bool member = valid && z == zid;
-            rest &= ~__builtin_amdgcn_ballot_w64(member);
+        wave_rounds(valid, z, [&](int32_t zid, bool member, int) {
             Moments c;
             c.count = member ? mine.count : id.count;
             c.kmin = member ? mine.kmin : id.kmin;
@@ -148,7 +296,7 @@ struct ZoneScan {
             c.c = member ? mine.c : id.c;
             c = wave_fold(c, FoldMoments<KIND>{});
             if ((threadIdx.x & (kWave - 1)) == 0) add_to_tables(zid, c);
-        }
+        });
     }
 
     // The whole wave, converged: the lanes' running records to the tables.
@@ -252,64 +400,17 @@ struct ZoneScan {
     }
 };
 
-// partials[partial_index(z, b, grid)] = the Moments of zone z in workgroup b's cells.  `head`: the cells peeled so that the
-// value loads start 16-byte aligned (reduce_head); the bits above bit 7 (the launch's load policy) are not looked at: every
-// load is nt.  records_if_single != nullptr (one-workgroup grid): the workgroup writes the n_zones records itself.
+// partials[partial_index(z, b, grid)] = the Moments of zone z in workgroup b's cells, over zonal_walk (`head`: its peel).
+// records_if_single != nullptr (one-workgroup grid): the workgroup writes the n_zones records itself.
 template <typename T, typename ZT, bool MASKED, int U>
 __global__ __launch_bounds__(ecz::kBlock) void k_zonal_partials(const T* __restrict__ p, const uint8_t* __restrict__ mask,
                                                                  const ZT* __restrict__ zones, size_t n, int32_t n_zones,
                                                                  Moments* __restrict__ partials, unsigned head,
                                                                  ec_moments* __restrict__ records_if_single) {
     extern __shared__ __attribute__((aligned(16))) unsigned char zonal_lds[];
-    const double pivot = stats_pivot<T>(p);  // the FIRST cell of the buffer, before the peel moves p
-    head &= 0xffu;
-    p += head;
-    zones += head;
-    if constexpr (MASKED) mask += head;
-    n -= head;
-    constexpr int CPL = 16 / sizeof(T);
-    using TV = cells<T, CPL>;
-    using MV = cells<uint8_t, CPL>;
-    using ZV = cells<ZT, CPL>;
     ZoneScan<T> scan;
-    scan.init(zonal_lds, n_zones, pivot);
-
-    const size_t ngroups = n / CPL;
-    constexpr size_t TILE = size_t(ecz::kBlock) * U;
-    const size_t ntiles = (ngroups + TILE - 1) / TILE;
-    for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // the bounds are the workgroup's: every wave stays whole
-        const size_t base = tile * TILE + threadIdx.x;
-        TV x[U] = {};
-        MV m[U] = {};
-        ZV z[U] = {};
-        bool in[U];
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const size_t g = base + size_t(j) * ecz::kBlock;
-            in[j] = g < ngroups;
-            if (in[j]) {
-                x[j] = load_cells<true, T, CPL>(p + g * CPL);
-                z[j] = load_cells<true, ZT, CPL>(zones + g * CPL);
-                if constexpr (MASKED) m[j] = load_cells<true, uint8_t, CPL>(mask + g * CPL);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < U; ++j) scan.template group<MASKED, CPL, ZT>(in[j], x[j], m[j], z[j]);
-    }
-    if (blockIdx.x == 0) {  // the ragged tail and the peeled head, a cell per lane
-        for (size_t first = ngroups * CPL; first < n; first += ecz::kBlock) {
-            const size_t i = first + threadIdx.x;
-            const bool in = i < n;
-            const size_t at = in ? i : first;
-            scan.cell(in, ld_cell(p + at), MASKED ? ld_cell(mask + at) : uint8_t(1), zone_id(ld_cell(zones + at)));
-        }
-        for (unsigned first = 0; first < head; first += ecz::kBlock) {
-            const unsigned h = first + threadIdx.x;
-            const bool in = h < head;
-            const ptrdiff_t at = -static_cast<ptrdiff_t>(in ? h : first) - 1;
-            scan.cell(in, ld_cell(p + at), MASKED ? ld_cell(mask + at) : uint8_t(1), zone_id(ld_cell(zones + at)));
-        }
-    }
+    scan.init(zonal_lds, n_zones, stats_pivot<T>(p));  // the FIRST cell of the buffer, before the walk's peel
+    zonal_walk<T, ZT, MASKED, U>(p, mask, zones, n, head, scan);
     scan.write_out(partials, records_if_single);
 }
 
@@ -322,13 +423,7 @@ __global__ __launch_bounds__(ecz::kBlock) void k_zonal_partials_cellwise(const T
     extern __shared__ __attribute__((aligned(16))) unsigned char zonal_lds[];
     ZoneScan<T> scan;
     scan.init(zonal_lds, n_zones, stats_pivot<T>(p));
-    const size_t stride = size_t(gridDim.x) * ecz::kBlock;
-    for (size_t first = size_t(blockIdx.x) * ecz::kBlock; first < n; first += stride) {
-        const size_t i = first + threadIdx.x;
-        const bool in = i < n;
-        const size_t at = in ? i : first;
-        scan.cell(in, p[at], MASKED ? mask[at] : uint8_t(1), zone_id(zones[at]));
-    }
+    zonal_walk_cellwise<T, ZT, MASKED>(p, mask, zones, n, scan);
     scan.write_out(partials, records_if_single);
 }
 
@@ -347,51 +442,15 @@ __global__ __launch_bounds__(kStatsFinalizeBlock) void k_zonal_finalize(const Mo
     if (block_fold<kStatsFinalizeBlock>(acc, op)) write_record<T>(records + z, acc, first_cell_or_null ? stats_pivot<T>(first_cell_or_null) : 0.0);
 }
 
-// ---- ec_zonal_broadcast: dst[i] = table[zones[i]], bits copied by cell width W, mask byte 1; an id that belongs to no zone
-// gives all-zero bits and mask byte 0.  The map kernels' frame (k_map, ec_map_kernels.hpp: one workgroup per tile of U groups
-// per lane, two fronts, nt loads and stores, the ragged tail by workgroup 0) with the table staged in LDS first (2 KiB at the most,
-// loaded nt like every other access: the L2 serves the workgroups' re-reads all the same).
+// ---- ec_zonal_broadcast: zonal_gather (above) with the table staged in LDS first (2 KiB at the most, loaded nt
+// like every other access: the L2 serves the workgroups' re-reads all the same).
 template <typename W, typename ZT, bool MASKOUT, int U>
 __global__ __launch_bounds__(kBlock) void k_zonal_broadcast(const ZT* __restrict__ zones, const W* __restrict__ table, int32_t n_zones,
                                                             W* __restrict__ dst, uint8_t* __restrict__ dst_mask, size_t n, size_t first_tile) {
     __shared__ W tab[ecz::kMaxZones];
     for (int z = threadIdx.x; z < n_zones; z += kBlock) tab[z] = ld_cell(table + z);
     __syncthreads();
-    constexpr int CPL = 16 / max_of<sizeof(W), sizeof(ZT)>::value;
-    using DV = vec<W, CPL>;
-    using MV = vec<uint8_t, CPL>;
-    const size_t ngroups = n / CPL;
-    constexpr size_t TILE = size_t(kBlock) * U;
-    const size_t base = two_front_tile(first_tile) * TILE + threadIdx.x;
-    cells<ZT, CPL> z[U] = {};
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        const size_t g = base + size_t(j) * kBlock;
-        if (g < ngroups) z[j] = load_cells<true, ZT, CPL>(zones + g * CPL);
-    }
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        const size_t g = base + size_t(j) * kBlock;
-        if (g >= ngroups) continue;
-        DV o;
-        MV m;
-#pragma unroll
-        for (int k = 0; k < CPL; ++k) {
-            const int32_t zk = zone_id(z[j][k]);
-            const bool ok = zone_in_range(zk, n_zones);
-            o[k] = ok ? tab[ok ? zk : 0] : W(0);
-            m[k] = ok ? 1 : 0;
-        }
-        nt_store(o, reinterpret_cast<DV*>(dst) + g);
-        if constexpr (MASKOUT) mask_store(m, reinterpret_cast<MV*>(dst_mask) + g);
-    }
-    if (first_group(first_tile))
-        for (size_t i = ngroups * CPL + threadIdx.x; i < n; i += kBlock) {
-            const int32_t zk = zone_id(ld_cell(zones + i));
-            const bool ok = zone_in_range(zk, n_zones);
-            st_cell<W>(ok ? tab[ok ? zk : 0] : W(0), dst + i);
-            if constexpr (MASKOUT) st_cell<uint8_t>(ok ? 1 : 0, dst_mask + i);
-        }
+    zonal_gather<W, ZT, MASKOUT, U>(zones, tab, n_zones, dst, dst_mask, n, first_tile);
 }
 
 template <typename W, typename ZT, bool MASKOUT>
@@ -401,13 +460,7 @@ __global__ __launch_bounds__(kBlock) void k_zonal_broadcast_cellwise(const ZT* _
     __shared__ W tab[ecz::kMaxZones];
     for (int z = threadIdx.x; z < n_zones; z += kBlock) tab[z] = ld_cell(table + z);
     __syncthreads();
-    const size_t stride = size_t(gridDim.x) * kBlock;
-    for (size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
-        const int32_t zk = zone_id(ld_cell(zones + i));
-        const bool ok = zone_in_range(zk, n_zones);
-        st_cell<W>(ok ? tab[ok ? zk : 0] : W(0), dst + i);
-        if constexpr (MASKOUT) st_cell<uint8_t>(ok ? 1 : 0, dst_mask + i);
-    }
+    zonal_gather_cellwise<W, ZT, MASKOUT>(zones, tab, n_zones, dst, dst_mask, n);
 }
 
 }  // namespace ecd

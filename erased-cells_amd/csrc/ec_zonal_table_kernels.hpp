@@ -11,15 +11,17 @@
 //   k_ztable_pass_b     kind 1 only: the zone's maximum read back, k and k2 derived (cached in the lane while its id stays), t and
 //                       the truncated w added into T1 and T2 (ec_zonal_table_cell.hpp)
 //   k_ztable_finalize   one lane per zone: the record, with the 128-bit -> f64 conversion, rounded once
-// Passes A and B run in the reductions' frame as k_zonal_partials does (ec_zonal_kernels.hpp): reduce_plan()'s grid-stride tiles,
-// 16-byte value loads with the ids and mask bytes of the same cells beside them, every load nt, the peeled head and the ragged
-// tail by workgroup 0, a cell-wise kernel for "unaligned_vector" off.
+// Passes A and B run in the reductions' frame as k_zonal_partials does (ec_zonal_kernels.hpp), ZtLane the visitor: the cell-wise
+// pass is zonal_walk_cellwise; the tiled pass KEEPS A TILE LOOP OF ITS OWN in front of the shared zonal_walk_edges.  Under the shared
+// zonal_walk, with the group's scan as a member of the lane, its masked pass A kernels for 1-byte values parked SGPRs in VGPR lanes
+// and one timed row fell behind the parent (profiles/zonal/frame.md).
 //
-// Aggregation before the atomic.  A lane keeps ONE running entry for ONE zone and flushes it when its id changes: a zone that
-// fills a lane's groups costs that lane one flush a launch.  Before a 16-byte group in which any lane leaves its zone, and at the
-// end of the kernel, the wave flushes together: a wave whose lanes hold at most kFewIds zones between them serves them a round
-// each — the first family's ballot loop: the zone's lanes fold by shuffles, one lane issues one set of atomics (the giant zone,
-// a wave inside a coherent zone, a wave across the edges of a few) — and a wave of many ids flushes lane by lane.
+// Aggregation before the atomic (ZtLane).  A lane keeps ONE running entry for ONE zone and flushes it when its id changes: a zone
+// that fills a lane's groups costs that lane one flush a launch.  Before a 16-byte group in which any lane leaves its zone, and at
+// the end of the kernel, the wave flushes together: a wave whose lanes hold at most kFewIds zones between them serves them a round
+// each (wave_rounds, as the first family does): the zone's lanes fold by shuffles, one lane issues one set of atomics (the giant
+// zone, a wave inside a coherent zone, a wave across the edges of a few) — and a wave of many ids flushes lane by lane.
+// What an entry holds is the pass's: ZtLaneA, ZtLaneB.
 #pragma once
 
 #include "ec_zonal_kernels.hpp"
@@ -65,15 +67,13 @@ __device__ __forceinline__ bool zt_few_ids(bool has, int32_t cur) {
     return rest == 0;
 }
 
-// Pass A's lane: the running entry of zone `cur`.  Bounds: a lane's share of n <= 2^32 cells; every word is a partial sum of the
-// zone's total, which the plan header bounds within its word.
+// Pass A's entry.  Bounds: a lane's share of n <= 2^32 cells; every word is a partial sum of the zone's total, which the plan
+// header bounds within its word.
 template <typename T>
 struct ZtLaneA {
+    using cell_type = T;
     static constexpr int KIND = StatsKind<T>::value;
     static constexpr int W = ezt::words(KIND);
-    ztword* table;
-    double pivot;
-    int32_t cur;
     uint64_t cnt;
     int64_t not_min, max;
     uint64_t a, b, c;  // kind 0: sum, squares lo, squares hi; kind 1: max |d| bits, flags, unused
@@ -84,13 +84,9 @@ struct ZtLaneA {
         max = zt_max_identity<T>();
         a = b = c = 0;
     }
-    __device__ __forceinline__ void init(ztword* t, double pv) {
-        table = t;
-        pivot = pv;
-        cur = -1;
-        reset();
-    }
-    __device__ __forceinline__ void add(T x) {
+    __device__ __forceinline__ bool has() const { return cnt != 0; }
+    __device__ __forceinline__ void enter(const ztword*, int32_t) {}
+    __device__ __forceinline__ void add(T x, double pivot) {
         const int64_t key = order_key<T>(x);
         ++cnt;
         not_min = ~key > not_min ? ~key : not_min;
@@ -108,7 +104,7 @@ struct ZtLaneA {
             b |= ezt::inf_flag(d);
         }
     }
-    __device__ __forceinline__ void atomics(int32_t z) const {
+    __device__ __forceinline__ void atomics(ztword* table, int32_t z) const {
         ztword* e = table + size_t(z) * W;
         zt_add(e + ezt::kCount, cnt);
         zt_smax(e + ezt::kNotMin, not_min);
@@ -121,24 +117,6 @@ struct ZtLaneA {
             zt_umax(e + ezt::kDmax, a);
             zt_or(e + ezt::kFlags, b);
         }
-    }
-    __device__ __forceinline__ void flush() {
-        if (cnt) atomics(cur);
-        reset();
-    }
-    // one cell; `valid`: it belongs to zone z (in range, shown)
-    __device__ __forceinline__ void cell(bool valid, T x, int32_t z) {
-        if (!valid) return;
-        if (z != cur) {
-            flush();
-            cur = z;
-        }
-        add(x);
-    }
-    // the whole wave, converged, before a group: `leaving` — this lane's next cell belongs to another zone than the one it holds.
-    // Where any lane leaves, the wave flushes together, so that a wave that crosses a zone's edge as one adds one folded entry.
-    __device__ __forceinline__ void before_group(bool leaving) {
-        if (__builtin_amdgcn_ballot_w64(leaving && cnt != 0) != 0) finish();
     }
     // the whole wave, converged: every lane's entry folded with the other lanes' by shuffles (same bits in every lane)
     __device__ __forceinline__ void fold() {
@@ -159,39 +137,15 @@ struct ZtLaneA {
             }
         }
     }
-    // The whole wave, converged: at the end of the kernel, and wherever a lane leaves its zone.  A wave of few zones (one: the giant
-    // zone, a wave inside a coherent zone; two to kFewIds: a wave across zones' edges) serves them a round each — the lanes of the
-    // zone fold, every other lane SELECTED to the identity, and one lane issues the atomics; a wave of many flushes lane by lane.
-    __device__ __forceinline__ void finish() {
-        const bool has = cnt != 0;
-        if (!zt_few_ids(has, cur)) {
-            flush();
-            return;
-        }
-        uint64_t rest = __builtin_amdgcn_ballot_w64(has);
-        while (rest) {  // wave-uniform: at most kFewIds rounds
-            const int first = __builtin_ctzll(rest);
-            const int32_t zid = __builtin_amdgcn_readlane(cur, first);
-            const bool member = has && cur == zid;
-            rest &= ~__builtin_amdgcn_ballot_w64(member);
-            ZtLaneA e = *this;
-            if (!member) e.reset();
-            e.fold();
-            if (static_cast<int>(threadIdx.x & (kWave - 1)) == first) e.atomics(zid);
-        }
-        reset();
-    }
 };
 
-// Pass B's lane (kind 1): the running T1 and T2 of zone `cur`, whose units are cached while the id stays.
+// Pass B's entry (kind 1): the running T1 and T2 of the lane's zone, whose units are cached while the id stays.
 template <typename T>
 struct ZtLaneB {
+    using cell_type = T;
     static constexpr int W = ezt::words(1);
-    ztword* table;
-    double pivot;
-    int32_t cur;
     bool any;
-    ezt::ZoneUnits u;
+    ezt::ZoneUnits u{false, false, 0, 0};
     ezt::Limbs t1, t2;
 
     __device__ __forceinline__ void reset() {
@@ -199,39 +153,23 @@ struct ZtLaneB {
         t1 = ezt::Limbs{0, 0};
         t2 = ezt::Limbs{0, 0};
     }
-    __device__ __forceinline__ void init(ztword* t, double pv) {
-        table = t;
-        pivot = pv;
-        cur = -1;
-        u = ezt::ZoneUnits{false, false, 0, 0};
-        reset();
+    __device__ __forceinline__ bool has() const { return any; }
+    __device__ __forceinline__ void enter(const ztword* table, int32_t z) {
+        u = ezt::zone_units(table[size_t(z) * W + ezt::kDmax]);  // written by pass A, a launch ago; nothing writes it now
     }
-    __device__ __forceinline__ void atomics(int32_t z) const {
-        ztword* e = table + size_t(z) * W;
-        zt_add(e + ezt::kT1Lo, t1.lo);
-        zt_add(e + ezt::kT1Hi, static_cast<uint64_t>(t1.hi));
-        zt_add(e + ezt::kT2Lo, t2.lo);
-        zt_add(e + ezt::kT2Hi, static_cast<uint64_t>(t2.hi));
-    }
-    __device__ __forceinline__ void flush() {
-        if (any) atomics(cur);
-        reset();
-    }
-    __device__ __forceinline__ void cell(bool valid, T x, int32_t z) {
-        if (!valid) return;
-        if (z != cur) {
-            flush();
-            cur = z;
-            u = ezt::zone_units(table[size_t(z) * W + ezt::kDmax]);  // written by pass A, a launch ago; nothing writes it now
-        }
+    __device__ __forceinline__ void add(T x, double pivot) {
         if (!u.sum1) return;  // a zone of NaN or infinities: the flags decide
         const double d = static_cast<double>(x) - pivot;
         any = true;
         ezt::limbs_add(t1, ezt::trunc_units(d, u.k1));
         if (u.sum2) ezt::limbs_add(t2, ezt::trunc_units(d * d, u.k2));
     }
-    __device__ __forceinline__ void before_group(bool leaving) {
-        if (__builtin_amdgcn_ballot_w64(leaving && any) != 0) finish();
+    __device__ __forceinline__ void atomics(ztword* table, int32_t z) const {
+        ztword* e = table + size_t(z) * W;
+        zt_add(e + ezt::kT1Lo, t1.lo);
+        zt_add(e + ezt::kT1Hi, static_cast<uint64_t>(t1.hi));
+        zt_add(e + ezt::kT2Lo, t2.lo);
+        zt_add(e + ezt::kT2Hi, static_cast<uint64_t>(t2.hi));
     }
     __device__ __forceinline__ void fold() {
 #pragma unroll
@@ -242,35 +180,73 @@ struct ZtLaneB {
             t2.hi += zt_xor_i64(t2.hi, off);
         }
     }
-    // as ZtLaneA::finish
+};
+
+// A lane of a pass, the visitor of zonal_walk_edges and zonal_walk_cellwise: the running entry `e` (ENTRY: ZtLaneA<T> or ZtLaneB<T>) of zone `cur`.
+template <typename ENTRY>
+struct ZtLane {
+    using T = typename ENTRY::cell_type;
+    ztword* table;
+    double pivot;
+    int32_t n_zones;
+    int32_t cur;
+    ENTRY e;
+
+    __device__ __forceinline__ void init(ztword* t, double pv, int32_t nz) {
+        table = t;
+        pivot = pv;
+        n_zones = nz;
+        cur = -1;
+        e.reset();
+    }
+    __device__ __forceinline__ void flush() {
+        if (e.has()) e.atomics(table, cur);
+        e.reset();
+    }
+    // one cell; `valid`: it belongs to zone z (in range, shown)
+    __device__ __forceinline__ void cell(bool valid, T x, int32_t z) {
+        if (!valid) return;
+        if (z != cur) {
+            flush();
+            cur = z;
+            e.enter(table, z);
+        }
+        e.add(x, pivot);
+    }
+    // the walk's cell: `in`: the lane has one; `m`: its mask byte, 1 without a mask
+    __device__ __forceinline__ void cell(bool in, T x, uint8_t m, int32_t z) { cell(in && m != 0 && zone_in_range(z, n_zones), x, z); }
+    // the whole wave, converged, before a group: `leaving` — this lane's next cell belongs to another zone than the one it holds.
+    // Where any lane leaves, the wave flushes together, so that a wave that crosses a zone's edge as one adds one folded entry.
+    __device__ __forceinline__ void before_group(bool leaving) {
+        if (__builtin_amdgcn_ballot_w64(leaving && e.has()) != 0) finish();
+    }
+    // The whole wave, converged: at the end of the kernel, and wherever a lane leaves its zone.  A wave of few zones (one: the giant
+    // zone, a wave inside a coherent zone; two to kFewIds: a wave across zones' edges) serves them a round each — the lanes of the
+    // zone fold, every other lane SELECTED to the identity, and lane `first` issues the atomics; a wave of many flushes lane by lane.
     __device__ __forceinline__ void finish() {
-        const bool has = any;
+        const bool has = e.has();
         if (!zt_few_ids(has, cur)) {
             flush();
             return;
         }
-        uint64_t rest = __builtin_amdgcn_ballot_w64(has);
-        while (rest) {
-            const int first = __builtin_ctzll(rest);
-            const int32_t zid = __builtin_amdgcn_readlane(cur, first);
-            const bool member = has && cur == zid;
-            rest &= ~__builtin_amdgcn_ballot_w64(member);
-            ZtLaneB e = *this;
-            if (!member) e.reset();
-            e.fold();
-            if (static_cast<int>(threadIdx.x & (kWave - 1)) == first) e.atomics(zid);
-        }
-        reset();
+        wave_rounds(has, cur, [&](int32_t zid, bool member, int first) {  // wave-uniform: at most kFewIds rounds
+            ENTRY f = e;
+            if (!member) f.reset();
+            f.fold();
+            if (static_cast<int>(threadIdx.x & (kWave - 1)) == first) f.atomics(table, zid);
+        });
+        e.reset();
     }
 };
 
 // One pass over the cells in k_zonal_partials' frame; LANE is ZtLaneA<T> or ZtLaneB<T>.  `head`: the cells peeled so that the value
-// loads start 16-byte aligned; the bits above bit 7 are not looked at: every load is nt.
+// loads start 16-byte aligned; the bits above bit 7 are not looked at: every load is nt.  The tile loop is zonal_walk's, written out, with
+// the lane's part of a group in it: the first-valid-id scan, before_group, the cells.
 template <typename T, typename ZT, bool MASKED, int U, typename LANE>
 __global__ __launch_bounds__(ezt::kBlock) void k_ztable_pass(const T* __restrict__ p, const uint8_t* __restrict__ mask, const ZT* __restrict__ zones,
                                                              size_t n, int32_t n_zones, ztword* table, unsigned head) {
-    LANE lane;
-    lane.init(table, stats_pivot<T>(p));  // the FIRST cell of the buffer, before the peel moves p
+    ZtLane<LANE> lane;
+    lane.init(table, stats_pivot<T>(p), n_zones);  // the FIRST cell of the buffer, before the peel moves p
     head &= 0xffu;
     p += head;
     zones += head;
@@ -318,31 +294,17 @@ __global__ __launch_bounds__(ezt::kBlock) void k_ztable_pass(const T* __restrict
             }
         }
     }
-    if (blockIdx.x == 0) {  // the ragged tail and the peeled head, a cell per lane
-        for (size_t i = ngroups * CPL + threadIdx.x; i < n; i += ezt::kBlock) {
-            const int32_t zk = zone_id(ld_cell(zones + i));
-            lane.cell((!MASKED || ld_cell(mask + i) != 0) && zone_in_range(zk, n_zones), ld_cell(p + i), zk);
-        }
-        for (unsigned h = threadIdx.x; h < head; h += ezt::kBlock) {
-            const ptrdiff_t at = -static_cast<ptrdiff_t>(h) - 1;
-            const int32_t zk = zone_id(ld_cell(zones + at));
-            lane.cell((!MASKED || ld_cell(mask + at) != 0) && zone_in_range(zk, n_zones), ld_cell(p + at), zk);
-        }
-    }
-    lane.finish();  // reconverged: every lane of every wave arrives
+    zonal_walk_edges<T, ZT, MASKED>(p, mask, zones, ngroups * CPL, n, head, lane);
+    lane.finish();  // every lane of every wave arrives
 }
 
 // Same pass, cell-wise loads: any alignment (the plan's other outcome, "unaligned_vector" off).
 template <typename T, typename ZT, bool MASKED, typename LANE>
 __global__ __launch_bounds__(ezt::kBlock) void k_ztable_pass_cellwise(const T* __restrict__ p, const uint8_t* __restrict__ mask,
                                                                       const ZT* __restrict__ zones, size_t n, int32_t n_zones, ztword* table) {
-    LANE lane;
-    lane.init(table, stats_pivot<T>(p));
-    const size_t stride = size_t(gridDim.x) * ezt::kBlock;
-    for (size_t i = size_t(blockIdx.x) * ezt::kBlock + threadIdx.x; i < n; i += stride) {
-        const int32_t zk = zone_id(zones[i]);
-        lane.cell((!MASKED || mask[i] != 0) && zone_in_range(zk, n_zones), p[i], zk);
-    }
+    ZtLane<LANE> lane;
+    lane.init(table, stats_pivot<T>(p), n_zones);
+    zonal_walk_cellwise<T, ZT, MASKED>(p, mask, zones, n, lane);
     lane.finish();
 }
 
@@ -389,58 +351,18 @@ __global__ __launch_bounds__(ezt::kBlock) void k_ztable_finalize(const ztword* _
     out->reserved = 0;
 }
 
-// ---- ec_zonal_lookup: k_zonal_broadcast's frame (ec_zonal_kernels.hpp) without the LDS staging: the table is read where it
+// ---- ec_zonal_lookup: zonal_gather (ec_zonal_kernels.hpp) without ec_zonal_broadcast's staging: the table is read where it
 // lies, with plain (cacheable) loads — a table of 2^24 cells does not fit a workgroup, and the L2 serves the re-reads.
 template <typename W, typename ZT, bool MASKOUT, int U>
 __global__ __launch_bounds__(kBlock) void k_zonal_lookup(const ZT* __restrict__ zones, const W* __restrict__ table, int32_t n_zones,
                                                          W* __restrict__ dst, uint8_t* __restrict__ dst_mask, size_t n, size_t first_tile) {
-    constexpr int CPL = 16 / max_of<sizeof(W), sizeof(ZT)>::value;
-    using DV = vec<W, CPL>;
-    using MV = vec<uint8_t, CPL>;
-    const size_t ngroups = n / CPL;
-    constexpr size_t TILE = size_t(kBlock) * U;
-    const size_t base = two_front_tile(first_tile) * TILE + threadIdx.x;
-    cells<ZT, CPL> z[U] = {};
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        const size_t g = base + size_t(j) * kBlock;
-        if (g < ngroups) z[j] = load_cells<true, ZT, CPL>(zones + g * CPL);
-    }
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        const size_t g = base + size_t(j) * kBlock;
-        if (g >= ngroups) continue;
-        DV o;
-        MV m;
-#pragma unroll
-        for (int k = 0; k < CPL; ++k) {
-            const int32_t zk = zone_id(z[j][k]);
-            const bool ok = zone_in_range(zk, n_zones);
-            o[k] = ok ? table[ok ? zk : 0] : W(0);
-            m[k] = ok ? 1 : 0;
-        }
-        nt_store(o, reinterpret_cast<DV*>(dst) + g);
-        if constexpr (MASKOUT) mask_store(m, reinterpret_cast<MV*>(dst_mask) + g);
-    }
-    if (first_group(first_tile))
-        for (size_t i = ngroups * CPL + threadIdx.x; i < n; i += kBlock) {
-            const int32_t zk = zone_id(ld_cell(zones + i));
-            const bool ok = zone_in_range(zk, n_zones);
-            st_cell<W>(ok ? table[ok ? zk : 0] : W(0), dst + i);
-            if constexpr (MASKOUT) st_cell<uint8_t>(ok ? 1 : 0, dst_mask + i);
-        }
+    zonal_gather<W, ZT, MASKOUT, U>(zones, table, n_zones, dst, dst_mask, n, first_tile);
 }
 
 template <typename W, typename ZT, bool MASKOUT>
 __global__ __launch_bounds__(kBlock) void k_zonal_lookup_cellwise(const ZT* __restrict__ zones, const W* __restrict__ table, int32_t n_zones,
                                                                   W* __restrict__ dst, uint8_t* __restrict__ dst_mask, size_t n) {
-    const size_t stride = size_t(gridDim.x) * kBlock;
-    for (size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
-        const int32_t zk = zone_id(ld_cell(zones + i));
-        const bool ok = zone_in_range(zk, n_zones);
-        st_cell<W>(ok ? table[ok ? zk : 0] : W(0), dst + i);
-        if constexpr (MASKOUT) st_cell<uint8_t>(ok ? 1 : 0, dst_mask + i);
-    }
+    zonal_gather_cellwise<W, ZT, MASKOUT>(zones, table, n_zones, dst, dst_mask, n);
 }
 
 }  // namespace ecd

@@ -2,7 +2,8 @@
 // ec_zonal_table_device, ec_zonal_table_compute, ec_zonal_lookup) share, in plain C++: the cap, the launch constants, the layout
 // of the per-zone table in the caller's workspace, the refusals and their order.
 //
-// Self-contained like ec_zonal_plan.hpp, whose zone types, overlap test and broadcast tiling it reuses: no HIP include.
+// Self-contained like ec_zonal_plan.hpp, whose zone types, broadcast tiling and the refusals' shared head and overlap tail it
+// reuses: no HIP include.
 #pragma once
 
 #include <stddef.h>
@@ -44,50 +45,29 @@ constexpr size_t workspace_bytes(int kind, int32_t n_zones) {
 
 inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
-// Why ec_zonal_table_device refuses a call, or null; ec_zonal_stats_device's order (ecz::stats_refusal) with the alignment of
-// the records and the workspace beside their overlaps.  max_cells: the kind's bound on n.  caller_workspace false (the forms that
-// take workspace and records from the library's pool): `workspace` is not looked at and `out` is host memory of any alignment.
+// Why ec_zonal_table_device refuses a call, or null; ec_zonal_stats_device's order and shared pieces (ecz::stats_refusal) with this
+// family's cap, the kind's bound on n (max_cells) and the alignment of the records and the workspace before their overlaps.
+// caller_workspace false (the forms that take workspace and records from the library's pool): `workspace` is not looked at and
+// `out` is host memory of any alignment.
 inline const char* table_refusal(int32_t n_zones, size_t cell_size, int kind, int zt, const void* p, const void* mask, const void* zones, size_t n,
                                  uint64_t max_cells, const void* out, const void* workspace, bool caller_workspace, bool* bad_type) {
-    *bad_type = false;
-    if (!valid_zones(n_zones)) return "n_zones is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES (16777216)";
-    if (cell_size == 0) { *bad_type = true; return "bad dtype"; }
-    if (!ecz::valid_zone_type(zt)) { *bad_type = true; return "the zone raster's type is not EC_U8, EC_U16 or EC_I32"; }
-    if (!out || (caller_workspace && !workspace) || (n > 0 && (!p || !zones))) return "null pointer";
+    const bool null_pointer = !out || (caller_workspace && !workspace) || (n > 0 && (!p || !zones));
+    if (const char* why = ecz::refusal_head(valid_zones(n_zones), "n_zones is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES (16777216)", cell_size, zt,
+                                            null_pointer, bad_type))
+        return why;
     if (n > max_cells) return kind == 0 ? "more cells than one exact record covers: shard it (ec_stats_fold merges the records)"
                                          : "more than 2^32 cells: the truncated sums are bounded for 2^32 (shard it)";
     if (!caller_workspace) return nullptr;
     if (!aligned16(out)) return "the records are not 16-byte aligned";
     if (!aligned16(workspace)) return "the workspace is not 16-byte aligned";
-    const size_t ws = workspace_bytes(kind, n_zones), out_bytes = size_t(n_zones) * ecz::kRecordBytes;
-    const void* in[3] = {p, mask, zones};
-    const size_t in_bytes[3] = {n * cell_size, n, n * ecz::zone_size(zt)};
-    for (int k = 0; k < 3; ++k) {
-        if (ecz::overlap(out, out_bytes, in[k], in_bytes[k])) return "the records overlap an input";
-        if (ecz::overlap(workspace, ws, in[k], in_bytes[k])) return "the workspace overlaps an input";
-    }
-    if (ecz::overlap(out, out_bytes, workspace, ws)) return "the records overlap the workspace";
-    return nullptr;
+    return ecz::stats_overlap_refusal(out, size_t(n_zones) * ecz::kRecordBytes, workspace, workspace_bytes(kind, n_zones), p, mask, zones, n, cell_size, zt);
 }
 
 // Why ec_zonal_lookup refuses a call, or null: ecz::broadcast_refusal with this family's cap.
 inline const char* lookup_refusal(int32_t n_zones, size_t cell_size, int zt, const void* zones, const void* table, size_t n, const void* dst,
                                   const void* dst_mask, bool* bad_type) {
-    *bad_type = false;
-    if (!valid_zones(n_zones)) return "n_zones is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES (16777216)";
-    if (cell_size == 0) { *bad_type = true; return "bad dtype"; }
-    if (!ecz::valid_zone_type(zt)) { *bad_type = true; return "the zone raster's type is not EC_U8, EC_U16 or EC_I32"; }
-    if (n == 0) return nullptr;
-    if (!zones || !table || !dst) return "null pointer";
-    if (ecz::broadcast_tiles(n, ecz::broadcast_cpl(cell_size, ecz::zone_size(zt))) > ecz::kMaxTiles) return "more than 2^31 - 1 tiles";
-    const void* in[2] = {zones, table};
-    const size_t in_bytes[2] = {n * ecz::zone_size(zt), size_t(n_zones) * cell_size};
-    for (int k = 0; k < 2; ++k) {
-        if (ecz::overlap(dst, n * cell_size, in[k], in_bytes[k])) return "dst overlaps an input (the operation is not in-place)";
-        if (ecz::overlap(dst_mask, n, in[k], in_bytes[k])) return "dst_mask overlaps an input";
-    }
-    if (ecz::overlap(dst, n * cell_size, dst_mask, n)) return "dst_mask overlaps dst";
-    return nullptr;
+    return ecz::gather_refusal(valid_zones(n_zones), "n_zones is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES (16777216)", n_zones, cell_size, zt, zones,
+                               table, n, dst, dst_mask, bad_type);
 }
 
 }  // namespace ezt

@@ -351,6 +351,10 @@ inline void focal_rank_call(ec_dtype t, const void* src, const uint8_t* src_mask
     if (q) check(ec_focal_rank(t, src, src_mask, cols, n / cols, radius.first, radius.second, q->first, q->second, method, flags, dst, dst_mask, current_stream()));
     else check(ec_focal_majority(t, src, src_mask, cols, n / cols, radius.first, radius.second, flags, dst, dst_mask, current_stream()));
 }
+// what both zonal families refuse of n_zones before the library is asked: `cap` is the family's, named `cap_name`
+inline void check_n_zones(const char* who, int32_t n_zones, int32_t cap, const char* cap_name, const char* advice = "") {
+    if (n_zones < 1 || n_zones > cap) throw Error(EC_ERR_ARG, std::string(who) + ": n_zones is not within 1 .. " + cap_name + advice);
+}
 }  // namespace detail
 
 class CellBuffer {
@@ -359,6 +363,20 @@ class CellBuffer {
     std::shared_ptr<DeviceMem> mem_;
 
     static CellBuffer empty_u8() { return CellBuffer(CellType::UInt8, 0); }  // buffer.rs:233-234
+    // the n_zones ec_stats of `values` per zone by `compute` (ec_zonal_stats_compute, ec_zonal_table_compute)
+    template <typename F>
+    static std::vector<ec_stats> zonal_of(F compute, const char* who, int32_t cap, const char* cap_name, const char* advice, const CellBuffer& values,
+                                          const uint8_t* mask_or_null, const CellBuffer& zones, int32_t n_zones) {
+        if (zones.n_ != values.n_) throw Error(EC_ERR_LENGTH, std::string(who) + ": the zone raster and the values differ in length");
+        detail::check_n_zones(who, n_zones, cap, cap_name, advice);
+        std::vector<ec_stats> out(static_cast<size_t>(n_zones));
+        check(compute(static_cast<ec_dtype>(values.ct_), values.ptr(), mask_or_null, static_cast<ec_dtype>(zones.ct_), zones.ptr(), values.n_, n_zones, out.data(),
+                      current_stream()));
+        return out;
+    }
+    // table[id] for each id of this buffer by `gather` (ec_zonal_broadcast, ec_zonal_lookup).  Defined below MaskedCellBuffer.
+    template <typename F>
+    MaskedCellBuffer gather(F fn, const char* who, size_t cap, const char* cap_name, const CellBuffer& table) const;
 
 public:
     CellBuffer() = default;
@@ -549,20 +567,12 @@ public:
     // Breaks of any cell type; Defined below ReclassTable.
     template <typename BT> CellBuffer classify(const std::vector<BT>& breaks, bool right = false) const;
     static std::vector<Stats> zonal_stats_of(const CellBuffer& values, const uint8_t* mask_or_null, const CellBuffer& zones, int32_t n_zones) {
-        if (zones.n_ != values.n_) throw Error(EC_ERR_LENGTH, "zonal_stats: the zone raster and the values differ in length");
-        if (n_zones < 1 || n_zones > EC_ZONAL_MAX_ZONES) throw Error(EC_ERR_ARG, "zonal_stats: n_zones is not within 1 .. EC_ZONAL_MAX_ZONES; relabel in chunks");
-        std::vector<ec_stats> out(static_cast<size_t>(n_zones));
-        check(ec_zonal_stats_compute(static_cast<ec_dtype>(values.ct_), values.ptr(), mask_or_null, static_cast<ec_dtype>(zones.ct_), zones.ptr(), values.n_,
-                                     n_zones, out.data(), current_stream()));
+        const std::vector<ec_stats> out = zonal_of(ec_zonal_stats_compute, "zonal_stats", EC_ZONAL_MAX_ZONES, "EC_ZONAL_MAX_ZONES", "; relabel in chunks", values,
+                                                   mask_or_null, zones, n_zones);
         return std::vector<Stats>(out.begin(), out.end());
     }
     static std::vector<ec_stats> zonal_table_of(const CellBuffer& values, const uint8_t* mask_or_null, const CellBuffer& zones, int32_t n_zones) {
-        if (zones.n_ != values.n_) throw Error(EC_ERR_LENGTH, "zonal_table: the zone raster and the values differ in length");
-        if (n_zones < 1 || n_zones > EC_ZONAL_TABLE_MAX_ZONES) throw Error(EC_ERR_ARG, "zonal_table: n_zones is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES");
-        std::vector<ec_stats> out(static_cast<size_t>(n_zones));
-        check(ec_zonal_table_compute(static_cast<ec_dtype>(values.ct_), values.ptr(), mask_or_null, static_cast<ec_dtype>(zones.ct_), zones.ptr(), values.n_,
-                                     n_zones, out.data(), current_stream()));
-        return out;
+        return zonal_of(ec_zonal_table_compute, "zonal_table", EC_ZONAL_TABLE_MAX_ZONES, "EC_ZONAL_TABLE_MAX_ZONES", "", values, mask_or_null, zones, n_zones);
     }
     template <typename T> std::vector<T> to_vec() const {  // buffer.rs:175-185
         CellBuffer r = convert(CellEncoding<T>::cell_type());
@@ -1268,22 +1278,22 @@ inline MaskedCellBuffer MaskedCellBuffer::reclassify(const ReclassTable& table) 
     return MaskedCellBuffer(std::move(out), std::move(m));
 }
 
-inline MaskedCellBuffer CellBuffer::broadcast(const CellBuffer& table) const {
-    if (table.n_ < 1 || table.n_ > size_t(EC_ZONAL_MAX_ZONES)) throw Error(EC_ERR_ARG, "broadcast: the table is not of 1 .. EC_ZONAL_MAX_ZONES cells");
+template <typename F>
+MaskedCellBuffer CellBuffer::gather(F fn, const char* who, size_t cap, const char* cap_name, const CellBuffer& table) const {
+    if (table.n_ < 1 || table.n_ > cap) throw Error(EC_ERR_ARG, std::string(who) + ": the table is not of 1 .. " + cap_name + " cells");
     CellBuffer out(table.ct_, n_);
     Mask m(n_);
-    check(ec_zonal_broadcast(static_cast<ec_dtype>(ct_), ptr(), n_, static_cast<int32_t>(table.n_), static_cast<ec_dtype>(table.ct_), table.ptr(), out.ptr(),
-                             m.ptr(), current_stream()));
+    check(fn(static_cast<ec_dtype>(ct_), ptr(), n_, static_cast<int32_t>(table.n_), static_cast<ec_dtype>(table.ct_), table.ptr(), out.ptr(), m.ptr(),
+             current_stream()));
     return MaskedCellBuffer(std::move(out), std::move(m));
 }
 
+inline MaskedCellBuffer CellBuffer::broadcast(const CellBuffer& table) const {
+    return gather(ec_zonal_broadcast, "broadcast", EC_ZONAL_MAX_ZONES, "EC_ZONAL_MAX_ZONES", table);
+}
+
 inline MaskedCellBuffer CellBuffer::lookup(const CellBuffer& table) const {
-    if (table.n_ < 1 || table.n_ > size_t(EC_ZONAL_TABLE_MAX_ZONES)) throw Error(EC_ERR_ARG, "lookup: the table is not of 1 .. EC_ZONAL_TABLE_MAX_ZONES cells");
-    CellBuffer out(table.ct_, n_);
-    Mask m(n_);
-    check(ec_zonal_lookup(static_cast<ec_dtype>(ct_), ptr(), n_, static_cast<int32_t>(table.n_), static_cast<ec_dtype>(table.ct_), table.ptr(), out.ptr(),
-                          m.ptr(), current_stream()));
-    return MaskedCellBuffer(std::move(out), std::move(m));
+    return gather(ec_zonal_lookup, "lookup", EC_ZONAL_TABLE_MAX_ZONES, "EC_ZONAL_TABLE_MAX_ZONES", table);
 }
 
 // no layer is masked: every cell is valid and the result is a CellBuffer
@@ -1701,6 +1711,21 @@ class ShardedCellBuffer {
         for (size_t l : lens_) bytes.push_back(l * size_of(ct));
         check(ec_sharded_alloc(grp_->raw(), bytes.data(), ptrs_.data()));
     }
+    // the n_zones ec_stats of the whole raster by `sharded` (ec_sharded_zonal_stats, ec_sharded_zonal_table)
+    template <typename F>
+    std::vector<ec_stats> zonal_of(F sharded, const char* who, int32_t cap, const char* cap_name, const ShardedCellBuffer& zones, int32_t n_zones,
+                                   const ShardedCellBuffer* mask) const {
+        if (zones.lens_ != lens_) throw Error(EC_ERR_LENGTH, "the zone raster must be sharded identically");
+        if (mask && (mask->ct_ != CellType::UInt8 || mask->lens_ != lens_)) throw Error(EC_ERR_LENGTH, "the mask must be UInt8 and sharded identically");
+        detail::check_n_zones(who, n_zones, cap, cap_name);
+        std::vector<ec_stats> out(static_cast<size_t>(n_zones));
+        std::vector<const void*> p(ptrs_.begin(), ptrs_.end()), z(zones.ptrs_.begin(), zones.ptrs_.end());
+        std::vector<const uint8_t*> m;
+        if (mask) for (void* q : mask->ptrs_) m.push_back(static_cast<const uint8_t*>(q));
+        check(sharded(grp_->raw(), static_cast<ec_dtype>(ct_), p.data(), mask ? m.data() : nullptr, static_cast<ec_dtype>(zones.ct_), z.data(), lens_.data(),
+                      n_zones, out.data()));
+        return out;
+    }
 
 public:
     ShardedCellBuffer(ShardedCellBuffer&& o) noexcept : grp_(o.grp_), ct_(o.ct_), ptrs_(std::move(o.ptrs_)), lens_(std::move(o.lens_)) { o.ptrs_.clear(); }
@@ -1856,29 +1881,12 @@ public:
     // CellBuffer::zonal_stats of the whole raster: every shard's n_zones records, zone by zone folded on the host in shard order
     // (`zones`: the zone raster cut the same way; `mask` as for stats())
     std::vector<Stats> zonal_stats(const ShardedCellBuffer& zones, int32_t n_zones, const ShardedCellBuffer* mask = nullptr) const {
-        if (zones.lens_ != lens_) throw Error(EC_ERR_LENGTH, "the zone raster must be sharded identically");
-        if (mask && (mask->ct_ != CellType::UInt8 || mask->lens_ != lens_)) throw Error(EC_ERR_LENGTH, "the mask must be UInt8 and sharded identically");
-        if (n_zones < 1 || n_zones > EC_ZONAL_MAX_ZONES) throw Error(EC_ERR_ARG, "zonal_stats: n_zones is not within 1 .. EC_ZONAL_MAX_ZONES");
-        std::vector<ec_stats> out(static_cast<size_t>(n_zones));
-        std::vector<const void*> p(ptrs_.begin(), ptrs_.end()), z(zones.ptrs_.begin(), zones.ptrs_.end());
-        std::vector<const uint8_t*> m;
-        if (mask) for (void* q : mask->ptrs_) m.push_back(static_cast<const uint8_t*>(q));
-        check(ec_sharded_zonal_stats(grp_->raw(), static_cast<ec_dtype>(ct_), p.data(), mask ? m.data() : nullptr, static_cast<ec_dtype>(zones.ct_), z.data(),
-                                     lens_.data(), n_zones, out.data()));
+        const std::vector<ec_stats> out = zonal_of(ec_sharded_zonal_stats, "zonal_stats", EC_ZONAL_MAX_ZONES, "EC_ZONAL_MAX_ZONES", zones, n_zones, mask);
         return std::vector<Stats>(out.begin(), out.end());
     }
     // CellBuffer::zonal_table of the whole raster (ec_sharded_zonal_table): up to EC_ZONAL_TABLE_MAX_ZONES zones, the fold unchanged
     std::vector<ec_stats> zonal_table(const ShardedCellBuffer& zones, int32_t n_zones, const ShardedCellBuffer* mask = nullptr) const {
-        if (zones.lens_ != lens_) throw Error(EC_ERR_LENGTH, "the zone raster must be sharded identically");
-        if (mask && (mask->ct_ != CellType::UInt8 || mask->lens_ != lens_)) throw Error(EC_ERR_LENGTH, "the mask must be UInt8 and sharded identically");
-        if (n_zones < 1 || n_zones > EC_ZONAL_TABLE_MAX_ZONES) throw Error(EC_ERR_ARG, "zonal_table: n_zones is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES");
-        std::vector<ec_stats> out(static_cast<size_t>(n_zones));
-        std::vector<const void*> p(ptrs_.begin(), ptrs_.end()), z(zones.ptrs_.begin(), zones.ptrs_.end());
-        std::vector<const uint8_t*> m;
-        if (mask) for (void* q : mask->ptrs_) m.push_back(static_cast<const uint8_t*>(q));
-        check(ec_sharded_zonal_table(grp_->raw(), static_cast<ec_dtype>(ct_), p.data(), mask ? m.data() : nullptr, static_cast<ec_dtype>(zones.ct_), z.data(),
-                                     lens_.data(), n_zones, out.data()));
-        return out;
+        return zonal_of(ec_sharded_zonal_table, "zonal_table", EC_ZONAL_TABLE_MAX_ZONES, "EC_ZONAL_TABLE_MAX_ZONES", zones, n_zones, mask);
     }
     template <typename T> std::vector<T> to_vec() const {  // gather; T must be the buffer's own cell type
         if (CellEncoding<T>::cell_type() != ct_) throw NarrowingError(ct_, CellEncoding<T>::cell_type());

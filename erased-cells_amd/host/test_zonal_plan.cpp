@@ -1,4 +1,5 @@
-// test_zonal_plan.cpp — csrc/ec_zonal_plan.hpp alone, under a plain C++17 compiler (and, as test_zonal_plan_san, under the address and
+// test_zonal_plan.cpp — csrc/ec_zonal_plan.hpp and the refusals of csrc/ec_zonal_table_plan.hpp alone, under a plain C++17
+// compiler (and, as test_zonal_plan_san, under the address and
 // undefined-behaviour sanitizers): the LDS layout of a workgroup's tables for every n_zones (no two slots overlap, everything
 // inside `bytes`, 8-byte slots 8-byte aligned), the workspace size against the most workgroups a reduction launches, where a
 // partial goes, and the refusals in the order include/erased_cells.h states.  Needs no GPU and nothing from the library.
@@ -9,6 +10,7 @@
 #include <vector>
 
 #include "ec_zonal_plan.hpp"
+#include "ec_zonal_table_plan.hpp"
 
 static int g_checks = 0;
 #define CHECK(cond)                                                                    \
@@ -145,6 +147,69 @@ int main() {
     CHECK(std::strstr(bwhy(4, 2, 0, Z, P, 100, OUT, far + 199), "dst_mask overlaps dst") && !*bwhy(4, 2, 0, Z, P, 100, OUT, far + 200));
     CHECK(broadcast_cpl(1, 1) == 16 && broadcast_cpl(1, 4) == 4 && broadcast_cpl(8, 1) == 2 && broadcast_cpl(2, 2) == 8);
     CHECK(broadcast_tiles(0, 16) == 0 && broadcast_tiles(16 * kBlock * kBroadcastU, 16) == 1 && broadcast_tiles(16 * kBlock * kBroadcastU + 16, 16) == 2);
+
+    // the table family: the same head and tail with its own cap and cap text, the kind's bound and text, the two alignments
+    auto twhy = [&](int32_t nz, size_t cell, int kind, int zt, const void* p, const void* m, const void* z, size_t n, uint64_t max_cells, const void* out,
+                    const void* ws, bool caller_ws = true) {
+        const char* w = ezt::table_refusal(nz, cell, kind, zt, p, m, z, n, max_cells, out, ws, caller_ws, &bad);
+        return w ? w : "";
+    };
+    static_assert(ezt::kMaxZones == 1 << 24, "the cap");
+    CHECK(!*twhy(4, 2, 0, 0, P, M, Z, 100, 100, OUT, WS) && !bad);
+    CHECK(!*twhy(257, 8, 1, 6, P, nullptr, Z, 100, 100, OUT, WS) && !*twhy(ezt::kMaxZones, 1, 0, 1, P, M, Z, 100, 100, OUT, far + (size_t(2) << 30)));
+    CHECK(std::strstr(why(257, 2, 0, P, M, Z, 100, 0, OUT, WS), "EC_ZONAL_MAX_ZONES (256)"));  // the first family's cap and text stay its own
+    CHECK(std::strstr(twhy(0, 0, 1, 3, nullptr, nullptr, nullptr, 100, 1, mem + 1, mem + 2), "EC_ZONAL_TABLE_MAX_ZONES (16777216)") && !bad);
+    CHECK(std::strstr(twhy(ezt::kMaxZones + 1, 0, 1, 3, nullptr, nullptr, nullptr, 100, 1, nullptr, nullptr), "EC_ZONAL_TABLE_MAX_ZONES (16777216)") && !bad);
+    CHECK(std::strstr(twhy(-5, 2, 0, 0, P, M, Z, 100, 100, OUT, WS), "n_zones"));
+    CHECK(std::strstr(twhy(4, 0, 1, 3, nullptr, nullptr, nullptr, 100, 1, nullptr, nullptr), "bad dtype") && bad);
+    CHECK(std::strstr(twhy(4, 2, 1, 3, nullptr, nullptr, nullptr, 100, 1, nullptr, nullptr), "zone raster's type") && bad);
+    CHECK(std::strstr(twhy(4, 2, 1, 0, nullptr, M, Z, 100, 1, mem + 1, mem + 2), "null pointer") && !bad);
+    CHECK(std::strstr(twhy(4, 2, 1, 0, P, M, nullptr, 100, 1, mem + 1, mem + 2), "null pointer"));
+    CHECK(std::strstr(twhy(4, 2, 1, 0, P, M, Z, 100, 1, nullptr, mem + 2), "null pointer"));
+    CHECK(std::strstr(twhy(4, 2, 1, 0, P, M, Z, 100, 1, mem + 1, nullptr), "null pointer"));
+    CHECK(!*twhy(4, 2, 0, 0, nullptr, nullptr, nullptr, 0, 0, OUT, WS));  // n == 0: no cells, no cell pointers; a bound of 0 is a bound here
+    CHECK(std::strstr(twhy(4, 2, 0, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, WS), "null pointer"));
+    CHECK(std::strstr(twhy(4, 2, 0, 0, P, M, Z, 100, 99, mem + 1, mem + 2), "more cells than one exact record covers"));  // the bound before the alignments
+    CHECK(std::strstr(twhy(4, 4, 1, 0, P, M, Z, 100, 99, mem + 1, mem + 2), "more than 2^32 cells"));
+    CHECK(std::strstr(twhy(4, 2, 0, 0, P, M, Z, 100, 0, OUT, WS), "more cells"));  // no "0 = none" in this family
+    CHECK(!*twhy(4, 2, 0, 0, P, M, Z, 100, 100, mem + 1, nullptr, false));         // the pool's forms: host records of any alignment, no workspace to give
+    CHECK(std::strstr(twhy(4, 2, 0, 0, P, M, Z, 100, 99, mem + 1, nullptr, false), "more cells"));
+    char* base = mem + (16 - reinterpret_cast<uintptr_t>(mem) % 16) % 16;  // 16-byte aligned, inside the values
+    CHECK(std::strstr(twhy(4, 2, 0, 0, P, M, Z, 100, 100, base + 1, base + 2), "records are not 16-byte aligned"));  // the alignments before the overlaps
+    CHECK(std::strstr(twhy(4, 2, 0, 0, P, M, Z, 100, 100, base, base + 2), "workspace is not 16-byte aligned"));
+    CHECK(std::strstr(twhy(4, 2, 0, 0, P, M, Z, 100, 100, base, base), "records overlap an input"));
+    CHECK(std::strstr(twhy(4, 2, 0, 0, P, M, Z, 100, 100, OUT, base), "workspace overlaps an input"));
+    CHECK(std::strstr(twhy(4, 2, 0, 0, P, M, Z, 100, 100, OUT, base + 1024), "workspace overlaps an input"));  // the mask
+    CHECK(!*twhy(4, 2, 0, 0, P, nullptr, Z, 100, 100, OUT, base + 1024));                                       // ... which is no input without one
+    CHECK(std::strstr(twhy(4, 2, 0, 0, P, M, Z, 100, 100, base + 2048, WS), "records overlap an input"));      // the zone ids
+    CHECK(!*twhy(4, 2, 0, 0, P, M, Z, 100, 100, OUT, static_cast<const char*>(OUT) + 256));                     // 4 records of 64 bytes
+    CHECK(std::strstr(twhy(4, 2, 0, 0, P, M, Z, 100, 100, OUT, static_cast<const char*>(OUT) + 240), "records overlap the workspace"));
+    CHECK(ezt::workspace_bytes(0, 4) == 192 && ezt::workspace_bytes(1, 4) == 320);
+    CHECK(!*twhy(4, 2, 0, 0, P, M, Z, 100, 100, OUT, static_cast<const char*>(OUT) - 192));                     // kind 0: 4 entries of 6 words
+    CHECK(std::strstr(twhy(4, 4, 1, 0, P, M, Z, 100, 100, OUT, static_cast<const char*>(OUT) - 192), "records overlap the workspace"));  // kind 1: 10 words
+    CHECK(!*twhy(4, 4, 1, 0, P, M, Z, 100, 100, OUT, static_cast<const char*>(OUT) - 320));
+
+    // the lookup: the broadcast's refusals under the table family's cap
+    auto lwhy = [&](int32_t nz, size_t cell, int zt, const void* z, const void* t, size_t n, const void* dst, const void* dm) {
+        const char* w = ezt::lookup_refusal(nz, cell, zt, z, t, n, dst, dm, &bad);
+        return w ? w : "";
+    };
+    CHECK(!*lwhy(4, 2, 0, Z, P, 100, OUT, nullptr) && !*lwhy(257, 2, 0, Z, P, 100, OUT, WS) && !*lwhy(ezt::kMaxZones, 1, 6, Z, P, 100, OUT, WS));
+    CHECK(std::strstr(bwhy(257, 2, 0, Z, P, 100, OUT, WS), "EC_ZONAL_MAX_ZONES (256)"));
+    CHECK(std::strstr(lwhy(0, 0, 3, nullptr, nullptr, 100, nullptr, nullptr), "EC_ZONAL_TABLE_MAX_ZONES (16777216)") && !bad);
+    CHECK(std::strstr(lwhy(ezt::kMaxZones + 1, 0, 3, nullptr, nullptr, 100, nullptr, nullptr), "EC_ZONAL_TABLE_MAX_ZONES (16777216)"));
+    CHECK(std::strstr(lwhy(4, 0, 3, nullptr, nullptr, 100, nullptr, nullptr), "bad dtype") && bad);
+    CHECK(std::strstr(lwhy(4, 2, 3, nullptr, nullptr, 100, nullptr, nullptr), "zone raster's type") && bad);
+    CHECK(!*lwhy(4, 2, 0, nullptr, nullptr, 0, nullptr, nullptr) && !bad);  // nothing to do
+    CHECK(std::strstr(lwhy(4, 2, 0, nullptr, P, 100, OUT, nullptr), "null pointer") && std::strstr(lwhy(4, 2, 0, Z, nullptr, 100, OUT, nullptr), "null pointer") &&
+          std::strstr(lwhy(4, 2, 0, Z, P, 100, nullptr, nullptr), "null pointer"));
+    CHECK(std::strstr(lwhy(4, 1, 0, Z, P, (size_t(kMaxTiles) + 1) * kBlock * kBroadcastU * 16, Z, Z), "tiles"));  // the tiles before the overlaps
+    CHECK(std::strstr(lwhy(4, 2, 0, Z, P, 100, mem + 2048 + 99, mem + 2048), "dst overlaps"));
+    CHECK(std::strstr(lwhy(4, 2, 0, Z, P, 100, mem + 7, nullptr), "dst overlaps"));  // the table: 4 cells of 2 bytes
+    CHECK(!*lwhy(4, 2, 0, Z, P, 100, mem + 8, nullptr));
+    CHECK(std::strstr(lwhy(300, 2, 0, Z, P, 100, mem + 599, nullptr), "dst overlaps") && !*lwhy(300, 2, 0, Z, P, 100, mem + 600, nullptr));  // 300 cells
+    CHECK(std::strstr(lwhy(4, 2, 0, Z, P, 100, OUT, mem + 2048), "dst_mask overlaps an input"));
+    CHECK(std::strstr(lwhy(4, 2, 0, Z, P, 100, OUT, far + 199), "dst_mask overlaps dst") && !*lwhy(4, 2, 0, Z, P, 100, OUT, far + 200));
 
     std::printf("%d checks passed\n", g_checks);
     return 0;

@@ -775,16 +775,7 @@ class CellBuffer:
         """This buffer as a zone raster, each cell replaced by `table[id]`: the way back from per-zone figures into the raster
         (ec_zonal_broadcast).  `table`: a CellBuffer of n_zones cells, or a sequence / array that `cell_type` (default: its own
         numpy type) is stored as.  A cell whose id is outside 0 .. len(table) - 1 is zero and not valid in the result."""
-        if not isinstance(table, CellBuffer):
-            a = np.asarray(table)
-            table = CellBuffer.from_vec(a.astype(NP_DTYPES[cell_type]) if cell_type is not None else a)
-        elif cell_type is not None and table.ct != cell_type:
-            raise EcError(EC_ERR_ARG, f"broadcast: the table is {CT_NAMES[table.ct]}, not {CT_NAMES[cell_type]}")
-        if not 1 <= table.n <= EC_ZONAL_MAX_ZONES:
-            raise EcError(EC_ERR_ARG, f"broadcast: a table of {table.n} cells, not within 1 .. EC_ZONAL_MAX_ZONES ({EC_ZONAL_MAX_ZONES})")
-        out, om = CellBuffer.empty(self.n, table.ct), DeviceMem(self.n)
-        check(lib().ec_zonal_broadcast(self.ct, self.mem.ptr, self.n, table.n, table.ct, table.mem.ptr, out.mem.ptr, om.ptr, _stream))
-        return MaskedCellBuffer(out, Mask(self.n, om))
+        return _table_gather("broadcast", "EC_ZONAL_MAX_ZONES", EC_ZONAL_MAX_ZONES, "ec_zonal_broadcast", self, table, cell_type)
 
     def zonal_table(self, zones: "CellBuffer", n_zones: int) -> np.ndarray:
         """`zonal_stats` for up to EC_ZONAL_TABLE_MAX_ZONES (2^24) zones — the K + 1 labels of `regions`, a UInt16 parcel raster — as
@@ -797,16 +788,7 @@ class CellBuffer:
         """`broadcast` for a table of up to EC_ZONAL_TABLE_MAX_ZONES cells, read from device memory (ec_zonal_lookup): each cell
         replaced by `table[id]`; a cell whose id is outside 0 .. len(table) - 1 is zero and not valid in the result.
         `anomaly = ndvi - labels.lookup(per_patch["mean"])`."""
-        if not isinstance(table, CellBuffer):
-            a = np.asarray(table)
-            table = CellBuffer.from_vec(a.astype(NP_DTYPES[cell_type]) if cell_type is not None else a)
-        elif cell_type is not None and table.ct != cell_type:
-            raise EcError(EC_ERR_ARG, f"lookup: the table is {CT_NAMES[table.ct]}, not {CT_NAMES[cell_type]}")
-        if not 1 <= table.n <= EC_ZONAL_TABLE_MAX_ZONES:
-            raise EcError(EC_ERR_ARG, f"lookup: a table of {table.n} cells, not within 1 .. EC_ZONAL_TABLE_MAX_ZONES ({EC_ZONAL_TABLE_MAX_ZONES})")
-        out, om = CellBuffer.empty(self.n, table.ct), DeviceMem(self.n)
-        check(lib().ec_zonal_lookup(self.ct, self.mem.ptr, self.n, table.n, table.ct, table.mem.ptr, out.mem.ptr, om.ptr, _stream))
-        return MaskedCellBuffer(out, Mask(self.n, om))
+        return _table_gather("lookup", "EC_ZONAL_TABLE_MAX_ZONES", EC_ZONAL_TABLE_MAX_ZONES, "ec_zonal_lookup", self, table, cell_type)
 
     def reclassify(self, table_or_breaks, values=None, right: bool = False, dtype: Optional[int] = None, valid=None, breaks_dtype: Optional[int] = None):
         """Each cell replaced by the value of its class among the breaks, in one pass (ec_reclass; the rule is in
@@ -1402,18 +1384,50 @@ def select(mask: Mask, a, b):
     return MaskedCellBuffer(out, om)
 
 
+def _table_gather(what: str, cap_name: str, cap: int, fn: str, zones: "CellBuffer", table, cell_type: Optional[int]) -> "MaskedCellBuffer":
+    """`table[id]` for each id of `zones` by the library's `fn` (ec_zonal_broadcast, ec_zonal_lookup), whose cap on the table is `cap`."""
+    if not isinstance(table, CellBuffer):
+        a = np.asarray(table)
+        table = CellBuffer.from_vec(a.astype(NP_DTYPES[cell_type]) if cell_type is not None else a)
+    elif cell_type is not None and table.ct != cell_type:
+        raise EcError(EC_ERR_ARG, f"{what}: the table is {CT_NAMES[table.ct]}, not {CT_NAMES[cell_type]}")
+    if not 1 <= table.n <= cap:
+        raise EcError(EC_ERR_ARG, f"{what}: a table of {table.n} cells, not within 1 .. {cap_name} ({cap})")
+    out, om = CellBuffer.empty(zones.n, table.ct), DeviceMem(zones.n)
+    check(getattr(lib(), fn)(zones.ct, zones.mem.ptr, zones.n, table.n, table.ct, table.mem.ptr, out.mem.ptr, om.ptr, _stream))
+    return MaskedCellBuffer(out, Mask(zones.n, om))
+
+
+def _check_n_zones(what: str, cap_name: str, cap: int, n_zones, advice: str = "") -> int:
+    """`n_zones` as an int, refused unless it is an integer within 1 .. `cap` (the family's cap, named `cap_name`)."""
+    if isinstance(n_zones, bool) or not isinstance(n_zones, (int, np.integer)) or not 1 <= n_zones <= cap:
+        raise EcError(EC_ERR_ARG, f"{what}: n_zones {n_zones!r} is not within 1 .. {cap_name} ({cap}){advice}")
+    return int(n_zones)
+
+
+def _zonal_raw(what: str, cap_name: str, cap: int, advice: str, fn: str, buf: "CellBuffer", mask, zones, n_zones) -> np.ndarray:
+    """The `n_zones` ec_stats of `buf` under `mask` (or None) per zone of the CellBuffer `zones`, as the library's `fn`
+    (ec_zonal_stats_compute, ec_zonal_table_compute) leaves them."""
+    if isinstance(zones, MaskedCellBuffer) or not isinstance(zones, CellBuffer):
+        raise EcError(EC_ERR_ARG, f"{what}: the zone raster is a {type(zones).__name__}, not a CellBuffer")
+    n_zones = _check_n_zones(what, cap_name, cap, n_zones, advice)
+    if zones.n != buf.n:
+        raise EcError(EC_ERR_ARG, f"{what}: the zone raster has {zones.n} cells, the values {buf.n}")
+    raw = np.empty(n_zones, dtype=_EC_STATS_DTYPE)
+    check(getattr(lib(), fn)(buf.ct, buf.mem.ptr, mask.mem.ptr if mask is not None else None, zones.ct, zones.mem.ptr, buf.n, n_zones, raw.ctypes.data,
+                             _stream))
+    return raw
+
+
+def _stats_list(raw: np.ndarray) -> list:
+    """An array of ec_stats as a list of Stats."""
+    return [Stats.from_ec(s) for s in (EcStats * raw.size).from_buffer(raw)]
+
+
 def _zonal_stats(buf: "CellBuffer", mask, zones, n_zones: int) -> list:
     """`n_zones` Stats of `buf` under `mask` (or None) per zone of the CellBuffer `zones` (ec_zonal_stats_compute)."""
-    if isinstance(zones, MaskedCellBuffer) or not isinstance(zones, CellBuffer):
-        raise EcError(EC_ERR_ARG, f"zonal_stats: the zone raster is a {type(zones).__name__}, not a CellBuffer")
-    if isinstance(n_zones, bool) or not isinstance(n_zones, (int, np.integer)) or not 1 <= n_zones <= EC_ZONAL_MAX_ZONES:
-        raise EcError(EC_ERR_ARG, f"zonal_stats: n_zones {n_zones!r} is not within 1 .. EC_ZONAL_MAX_ZONES ({EC_ZONAL_MAX_ZONES}); relabel in chunks")
-    if zones.n != buf.n:
-        raise EcError(EC_ERR_ARG, f"zonal_stats: the zone raster has {zones.n} cells, the values {buf.n}")
-    out = (EcStats * int(n_zones))()
-    check(lib().ec_zonal_stats_compute(buf.ct, buf.mem.ptr, mask.mem.ptr if mask is not None else None, zones.ct, zones.mem.ptr, buf.n,
-                                       int(n_zones), out, _stream))
-    return [Stats.from_ec(s) for s in out]
+    return _stats_list(_zonal_raw("zonal_stats", "EC_ZONAL_MAX_ZONES", EC_ZONAL_MAX_ZONES, "; relabel in chunks", "ec_zonal_stats_compute", buf, mask, zones,
+                                 n_zones))
 
 
 # ec_stats as numpy sees it: the u64, two 16-byte ec_value (a type byte, padding, the payload in 8 bytes), three doubles
@@ -1436,22 +1450,10 @@ def stats_table(raw, ct: int) -> np.ndarray:
     return out
 
 
-def _check_table_call(what: str, buf: "CellBuffer", zones, n_zones) -> None:
-    if isinstance(zones, MaskedCellBuffer) or not isinstance(zones, CellBuffer):
-        raise EcError(EC_ERR_ARG, f"{what}: the zone raster is a {type(zones).__name__}, not a CellBuffer")
-    if isinstance(n_zones, bool) or not isinstance(n_zones, (int, np.integer)) or not 1 <= n_zones <= EC_ZONAL_TABLE_MAX_ZONES:
-        raise EcError(EC_ERR_ARG, f"{what}: n_zones {n_zones!r} is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES ({EC_ZONAL_TABLE_MAX_ZONES})")
-    if zones.n != buf.n:
-        raise EcError(EC_ERR_ARG, f"{what}: the zone raster has {zones.n} cells, the values {buf.n}")
-
-
 def _zonal_table(buf: "CellBuffer", mask, zones, n_zones: int) -> np.ndarray:
     """`n_zones` rows of statistics of `buf` under `mask` (or None) per zone of the CellBuffer `zones` (ec_zonal_table_compute)."""
-    _check_table_call("zonal_table", buf, zones, n_zones)
-    raw = np.empty(int(n_zones), dtype=_EC_STATS_DTYPE)
-    check(lib().ec_zonal_table_compute(buf.ct, buf.mem.ptr, mask.mem.ptr if mask is not None else None, zones.ct, zones.mem.ptr, buf.n,
-                                       int(n_zones), raw.ctypes.data, _stream))
-    return stats_table(raw, buf.ct)
+    return stats_table(_zonal_raw("zonal_table", "EC_ZONAL_TABLE_MAX_ZONES", EC_ZONAL_TABLE_MAX_ZONES, "", "ec_zonal_table_compute", buf, mask, zones,
+                                  n_zones), buf.ct)
 
 
 def _typed_array(what: str, xs, ct: Optional[int], default_for_numbers) -> np.ndarray:

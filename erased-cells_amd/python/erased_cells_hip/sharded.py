@@ -386,33 +386,28 @@ class ShardGroup:
                                      (C.c_size_t * self.n)(*sb.lens), C.byref(out)))
         return B.Stats.from_ec(out)
 
+    def _zonal_raw(self, what: str, cap_name: str, fn: str, sb: ShardedBuffer, zones: ShardedBuffer, n_zones, mask: ShardedBuffer):
+        """The `n_zones` ec_stats of the whole sharded raster as the library's `fn` (ec_sharded_zonal_stats, ec_sharded_zonal_table)
+        leaves them; `cap_name`: the family's cap on n_zones."""
+        import numpy as np
+        from . import _ffi
+        if list(zones.lens) != list(sb.lens) or (mask is not None and list(mask.lens) != list(sb.lens)):
+            raise _ffi.EcError(_ffi.EC_ERR_ARG, f"{what}: the zone raster or the mask is not sharded like the values")
+        n_zones = B._check_n_zones(what, cap_name, getattr(_ffi, cap_name), n_zones)  # a numpy K (of `regions`) as CellBuffer's forms take it
+        raw = np.empty(n_zones, dtype=B._EC_STATS_DTYPE)
+        check(getattr(lib(), fn)(self.handle, sb.ct, sb.ptrs, mask.ptrs if mask is not None else None, zones.ct, zones.ptrs,
+                                 (C.c_size_t * self.n)(*sb.lens), n_zones, raw.ctypes.data))
+        return raw
+
     def zonal_stats(self, sb: ShardedBuffer, zones: ShardedBuffer, n_zones: int, mask: ShardedBuffer = None) -> list:
         """`CellBuffer.zonal_stats` of the whole sharded raster: every shard's `n_zones` records, zone by zone folded on the host in
         shard order (no collective).  `zones`: the zone raster (UInt8, UInt16 or Int32), sharded like `sb`."""
-        from ._ffi import EC_ERR_ARG, EC_ZONAL_MAX_ZONES, EcError
-        if list(zones.lens) != list(sb.lens) or (mask is not None and list(mask.lens) != list(sb.lens)):
-            raise EcError(EC_ERR_ARG, "zonal_stats: the zone raster or the mask is not sharded like the values")
-        if isinstance(n_zones, bool) or not isinstance(n_zones, int) or not 1 <= n_zones <= EC_ZONAL_MAX_ZONES:
-            raise EcError(EC_ERR_ARG, f"zonal_stats: n_zones {n_zones!r} is not within 1 .. EC_ZONAL_MAX_ZONES ({EC_ZONAL_MAX_ZONES})")
-        out = (EcStats * n_zones)()
-        check(lib().ec_sharded_zonal_stats(self.handle, sb.ct, sb.ptrs, mask.ptrs if mask is not None else None, zones.ct, zones.ptrs,
-                                           (C.c_size_t * self.n)(*sb.lens), n_zones, out))
-        return [B.Stats.from_ec(s) for s in out]
+        return B._stats_list(self._zonal_raw("zonal_stats", "EC_ZONAL_MAX_ZONES", "ec_sharded_zonal_stats", sb, zones, n_zones, mask))
 
     def zonal_table(self, sb: ShardedBuffer, zones: ShardedBuffer, n_zones: int, mask: ShardedBuffer = None):
         """`CellBuffer.zonal_table` of the whole sharded raster (ec_sharded_zonal_table): up to EC_ZONAL_TABLE_MAX_ZONES zones, every
         shard's records folded zone by zone on the host in shard order; one numpy structured array of `n_zones` rows."""
-        import numpy as np
-        from ._ffi import EC_ERR_ARG, EC_ZONAL_TABLE_MAX_ZONES, EcError
-        if list(zones.lens) != list(sb.lens) or (mask is not None and list(mask.lens) != list(sb.lens)):
-            raise EcError(EC_ERR_ARG, "zonal_table: the zone raster or the mask is not sharded like the values")
-        if isinstance(n_zones, bool) or not isinstance(n_zones, (int, np.integer)) or not 1 <= n_zones <= EC_ZONAL_TABLE_MAX_ZONES:
-            raise EcError(EC_ERR_ARG, f"zonal_table: n_zones {n_zones!r} is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES ({EC_ZONAL_TABLE_MAX_ZONES})")
-        n_zones = int(n_zones)   # the K of `regions`, a numpy maximum: as CellBuffer.zonal_table takes them
-        raw = np.empty(n_zones, dtype=B._EC_STATS_DTYPE)
-        check(lib().ec_sharded_zonal_table(self.handle, sb.ct, sb.ptrs, mask.ptrs if mask is not None else None, zones.ct, zones.ptrs,
-                                           (C.c_size_t * self.n)(*sb.lens), n_zones, raw.ctypes.data))
-        return B.stats_table(raw, sb.ct)
+        return B.stats_table(self._zonal_raw("zonal_table", "EC_ZONAL_TABLE_MAX_ZONES", "ec_sharded_zonal_table", sb, zones, n_zones, mask), sb.ct)
 
     def counts(self, mask: ShardedBuffer) -> tuple[int, int]:
         t, f = C.c_uint64(), C.c_uint64()

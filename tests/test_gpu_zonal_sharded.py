@@ -94,5 +94,7 @@ def test_a_refused_call_launches_nothing(ec):
         got = g.zonal_stats(sb, sz, nz)                       # the group is unharmed: the next call works
         want = Z.stats(ct, cells.tolist(), zones.tolist(), nz)
         assert [s.count for s in got] == [w["count"] for w in want] and [s.sum for s in got] == [w["sum"] for w in want]
+        again = g.zonal_stats(sb, sz, np.int64(nz))           # a numpy K is taken as CellBuffer.zonal_stats and ShardGroup.zonal_table take it
+        assert [(s.count, s.sum) for s in again] == [(s.count, s.sum) for s in got]
         sb.free()
         sz.free()

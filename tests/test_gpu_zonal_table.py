@@ -113,15 +113,17 @@ def test_planted_and_hand_worked_zones(ec, space, zt):
 
 
 # ---------------------------------------------------------------- 3. every place a cell can be lost
-@pytest.mark.parametrize("ct", [R.U16, R.F64, R.F32], ids=lambda t: NAMES[t])
+@pytest.mark.parametrize("ct", [R.U16, R.F64, R.F32, R.U8], ids=lambda t: NAMES[t])
 def test_sizes_and_offsets(ec, space, ct):
     T = ZT.tile(ct)
-    sizes = [0, 1, T - 1, T, T + 1, 2 * T + 5]
+    sizes, offsets = [0, 1, T - 1, T, T + 1, 2 * T + 5], (0, 1, 3)
+    if ct == R.U8:   # the longest peel: 16 cells a group, a head of up to 15 cells, which whole waves walk with the ragged tail
+        sizes, offsets = [0, 1, 15, 16, 17, T + 1], (0, 1, 15)
     zt, nz = Z.ZONE_TYPES[ct % 3], 257
-    cells, mask, zones = K.arrays(ct, zt, nz, "runs37", max(sizes), 3, 0x512E + ct)
+    cells, mask, zones = K.arrays(ct, zt, nz, "runs37", max(sizes), max(offsets), 0x512E + ct)
     r = Raster(ec, ct, zt, cells, mask, zones)
     for n in sizes:
-        for off in (0, 1, 3):
+        for off in offsets:
             for masked in (False, True):
                 r.check(ec, space, nz, off, n, masked, (NAMES[ct], "n", n, "offset", off, "masked", masked))
 
