@@ -16,7 +16,7 @@
 //           is private to the wave, so no workgroup barrier is needed.
 // One workgroup per tile of U = 2 chunks per wave (1,024 cells), straight-line code,
 // grid = number of tiles (≫ 256 CUs: 262,144 workgroups at 16384²), dealt from both
-// ends of the buffer at once (two_front_tile).  Stores always stream (nt_store,
+// ends of the buffer at once (two_front_tile, ec_tile.hpp).  Stores always stream (nt_store,
 // ec_device.hpp): the f64 output (2.1 GB) dwarfs the 256 MiB Infinity Cache.  Loads are
 // non-temporal (+6 % on the divide, tune_binop_v2.log: 6270 -> 6666 GB/s) except a full
 // tile's loads of an operand stream that the host marks cacheable for the launch (policy
@@ -26,32 +26,11 @@
 // no L2 locality to win (measured: −4 %).
 #pragma once
 
-#include "ec_device.hpp"
+#include "ec_tile.hpp"
 
 namespace ecd {
 
-constexpr int kBlock = 256;          // 4 waves
-constexpr int kWave = 64;
 constexpr int kWavesPerBlock = kBlock / kWave;
-
-// a vector load in one arm of its launch's load policy (policy_arms, ec_device.hpp): NT = the stream is not kept cacheable
-template <bool NT, typename V>
-__device__ __forceinline__ V load_vec(const V* p) {
-    if constexpr (NT) return nt_load(p);
-    else return plain_load(p);
-}
-
-// Workgroup -> tile map: even workgroups walk the buffer from the front, odd ones from the back, so
-// two streaming fronts are live at once (measured +1…5 % over a single front, tune_binop_v4/v5.log).
-// A bijection on [0, gridDim.x) for any grid size.
-__device__ __forceinline__ size_t two_front_tile() {
-    const size_t b = blockIdx.x;
-    return (b & 1) ? size_t(gridDim.x) - 1 - (b >> 1) : (b >> 1);
-}
-// The same map inside one launch of a job cut into several (split_launch, ec_runtime.hpp): this launch covers the tiles
-// [first, first + gridDim.x).  `first_group(first)` names the workgroup that does a job's once-only work (ragged tails).
-__device__ __forceinline__ size_t two_front_tile(size_t first) { return first + two_front_tile(); }
-__device__ __forceinline__ bool first_group(size_t first) { return first == 0 && blockIdx.x == 0; }
 
 // ---------------------------------------------------------------------------
 // DIRECT variant: one block tile of kBlock*U pairs (2 cells each).  Pointers may sit
@@ -247,8 +226,6 @@ struct Staged {
     using Load = vec<uint32_t, int(sizeof(T))>;                        // 4*sizeof(T) bytes per lane
     static constexpr int kSlabBytes = value ? int(kLdsWaveCells * sizeof(T)) : 16;
 };
-
-using u32x4 = vec<uint32_t, 4>;
 
 template <typename L, typename R, int OP>
 __device__ __forceinline__ void binop_lds_body(const L* __restrict__ l, const R* __restrict__ r,

@@ -35,7 +35,7 @@
 #pragma once
 
 #include "ec_focal_plan.hpp"
-#include "ec_window_kernels.hpp"
+#include "ec_tile.hpp"
 
 namespace ecd {
 
@@ -119,30 +119,24 @@ __device__ __forceinline__ ecf::Tile focal_this_tile(const FocalArgs& a) {
 }
 
 // What a lane does with the CPL results of one output slot: `bits[k]` and `valid[k]` of the `cells` cells from column j0 of tile row oy.
+// The mask word and the store pair of a whole slot are the ones k_window_resample uses (SlotMask, slot_store_pair: ec_tile.hpp).  The
+// two branches stay here, reading `a` where they need it: behind one more call that takes the mask pointer and the cell-wise flag by
+// value the 1-byte rank kernels held 42 VGPRs in place of 34 (profiles/window/frame.md).
 template <int OW, int CPL>
 __device__ __forceinline__ void focal_store_slot(const FocalArgs& a, const ecf::Tile& t, uint32_t oy, uint32_t j0, uint32_t cells,
                                                  const uint64_t (&bits)[CPL], const bool (&valid)[CPL]) {
     using C = typename width_cell<OW>::type;
-    using M = typename byte_words<CPL>::type;
     const uint64_t at = (t.y0 + oy) * a.cols + t.x0 + j0;
     C* dst = static_cast<C*>(a.dst) + at;
     if (cells == uint32_t(CPL) && !a.cellwise_stores) {
         u32x4 v{0, 0, 0, 0};
-        uint64_t mlo = 0, mhi = 0;
+        SlotMask m;
 #pragma unroll
         for (int k = 0; k < CPL; ++k) {
             slot_put<OW>(v, k, C(valid[k] ? bits[k] : 0));
-            if (k < 8) mlo |= uint64_t(valid[k]) << (8 * (k & 7));
-            else mhi |= uint64_t(valid[k]) << (8 * (k & 7));
+            m.put(k, valid[k]);
         }
-        nt_store(v, reinterpret_cast<u32x4*>(dst));
-        if (a.dst_mask) {
-            M m;
-            if constexpr (CPL == 16) m = M{uint32_t(mlo), uint32_t(mlo >> 32), uint32_t(mhi), uint32_t(mhi >> 32)};
-            else if constexpr (CPL == 8) m = M{uint32_t(mlo), uint32_t(mlo >> 32)};
-            else m = static_cast<M>(mlo);
-            mask_store(m, reinterpret_cast<M*>(a.dst_mask + at));
-        }
+        slot_store_pair<CPL>(v, m, static_cast<C*>(a.dst), a.dst_mask, at);
     } else {
 #pragma unroll
         for (int k = 0; k < CPL; ++k) {
@@ -176,13 +170,6 @@ struct focal_key {
         }
     }
 };
-
-// byte k of the CPL count bytes a lane read as one word
-template <int CPL>
-__device__ __forceinline__ uint32_t focal_count_byte(const typename byte_words<CPL>::type& m, int k) {
-    if constexpr (CPL <= 4) return (uint32_t(m) >> (8 * k)) & 0xffu;
-    else return (m[k >> 2] >> (8 * (k & 3))) & 0xffu;
-}
 
 // ---- sum / mean (KIND = ecf::kSeparableSum, f64 results) and min / max (ecf::kSeparableMinMax, results of type T)
 template <typename T, bool MASKED, int KIND>
@@ -267,7 +254,7 @@ __global__ __launch_bounds__(kBlock) void k_focal(FocalArgs a) {
             if constexpr (MASKED) cm = *reinterpret_cast<const M*>(rcnt + at);
 #pragma unroll
             for (int k = 0; k < CPL; ++k) {  // columns past t.ow hold nothing written; their results are never stored
-                const uint32_t c = MASKED ? focal_count_byte<CPL>(cm, k) : in_row[k];
+                const uint32_t c = MASKED ? mask_word_byte<CPL>(cm, k) : in_row[k];
                 if constexpr (SUM) {
                     const double next = acc[k] + bits_f64(slot_get<8>(r, k));
                     acc[k] = in ? next : acc[k];

@@ -108,7 +108,7 @@ __global__ __launch_bounds__(kBlock) void k_focal_rank(FocalArgs a, RankTable ra
 #pragma unroll
         for (int k = 0; k < CPL; ++k) {  // columns past t.ow hold nothing written; their results are never stored
             bits[k] = uint64_t(slot_get<W>(r, k));
-            valid[k] = focal_count_byte<CPL>(vm, k) != 0;
+            valid[k] = mask_word_byte<CPL>(vm, k) != 0;
         }
         focal_store_slot<W, CPL>(a, t, oy, j0, cells, bits, valid);
     }

@@ -8,7 +8,7 @@
 // more than kMaxGroups workgroups to one launch:
 //   * the one-workgroup-per-tile families whose documented limit is 2^31 - 1 tiles (focal, focal_rank, composite, composite_rank,
 //     reclass, zonal broadcast, resample) issue several launches on the same stream, launch k covering the tiles
-//     [first, first + count) of part(tiles, k); the kernels take `first` as an argument (two_front_tile(first), ec_binop_kernels.hpp);
+//     [first, first + count) of part(tiles, k); the kernels take `first` as an argument (two_front_tile(first), ec_tile.hpp);
 //   * the streaming families (binops, maps, one-pass trees) refuse such a call on the host (check_groups, ec_runtime.hpp): they
 //     reach the limit only at 64 GiB or more of one stream.
 #pragma once

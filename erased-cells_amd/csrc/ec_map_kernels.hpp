@@ -13,7 +13,7 @@
 // when the "unaligned_vector" knob is off and a pointer is not 16-B aligned.
 #pragma once
 
-#include "ec_binop_kernels.hpp"
+#include "ec_tile.hpp"
 
 namespace ecd {
 

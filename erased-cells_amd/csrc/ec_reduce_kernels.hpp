@@ -25,7 +25,7 @@
 
 #include <type_traits>
 
-#include "ec_binop_kernels.hpp"
+#include "ec_tile.hpp"
 
 namespace ecd {
 

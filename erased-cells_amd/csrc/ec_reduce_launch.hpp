@@ -8,7 +8,7 @@
 #include <mutex>
 #include <type_traits>
 
-#include "ec_binop_kernels.hpp"  // kBlock, the cell-wise kernels' workgroup
+#include "ec_tile.hpp"  // kBlock, the cell-wise kernels' workgroup
 #include "ec_runtime.hpp"
 
 namespace ecd {

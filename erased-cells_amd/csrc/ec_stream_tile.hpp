@@ -8,7 +8,7 @@
 //   * the nt stores of the value pairs, the peeled head cell and the odd tail cell, and the mask phase.
 #pragma once
 
-#include "ec_binop_kernels.hpp"
+#include "ec_tile.hpp"
 #include "ec_runtime.hpp"
 
 namespace ecd {

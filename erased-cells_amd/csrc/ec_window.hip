@@ -42,9 +42,9 @@ static ec_status launch_window(int kind, const WindowArgs& args, const WindowAxi
         else k_window_cellwise<W, MASKED, false><<<grid_capped(chunks, 8), kBlock, 0, s>>>(a, ax ? *ax : id_x, ay ? *ay : id_y);
         return check_launch("window(cell-wise)");
     }
-    const uint64_t slots = (a.g.n + (16 / W) - 1) / (16 / W), per_tile = uint64_t(kBlock) * kWindowU;
-    if (const ec_status st = check_groups("window", (slots + per_tile - 1) / per_tile)) return st;  // a window of 256 GiB
-    const unsigned grid = grid_for((slots + per_tile - 1) / per_tile);
+    const uint64_t tiles = window_tiles(a.g.n, W, kWindowTileSlots);
+    if (const ec_status st = check_groups("window", tiles)) return st;  // a window of 256 GiB
+    const unsigned grid = grid_for(tiles);
     if (ax) k_window_nearest<W, MASKED><<<grid, kBlock, 0, s>>>(a, *ax, *ay);
     else if (kind == kWinPut) k_window_put<W, MASKED><<<grid, kBlock, 0, s>>>(a);
     else k_window_copy<W, MASKED><<<grid, kBlock, 0, s>>>(a);

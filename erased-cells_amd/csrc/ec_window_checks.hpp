@@ -11,6 +11,13 @@ namespace ecd {
 
 inline bool mul_overflows(uint64_t a, uint64_t b) { return a != 0 && b > UINT64_MAX / a; }
 
+// workgroups of a tiled launch over n cells of `cell` bytes on the contiguous side: one per tile of `tile_slots` 16-byte slots
+// (kWindowTileSlots, ec_window_kernels.hpp).  No sum that could overflow: n may be any 64-bit count.
+inline uint64_t window_tiles(uint64_t n, size_t cell, uint64_t tile_slots) {
+    const uint64_t per_slot = 16 / cell, slots = n / per_slot + (n % per_slot != 0);
+    return slots / tile_slots + (slots % tile_slots != 0);
+}
+
 // the raster, the window in it and the pair of masks: what the three entry points check alike
 inline ec_status check_window(const char* what, ec_dtype t, uint64_t cols, uint64_t rows, uint64_t x0, uint64_t y0, uint64_t w, uint64_t h,
                               const void* mask_a, const void* mask_b) {

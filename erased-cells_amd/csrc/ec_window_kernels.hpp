@@ -13,19 +13,20 @@
 // Where a lane's slot sits in the window: the workgroup divides the first cell of its tile by the window width ONCE (wave-uniform);
 // a lane adds its offset inside the tile and steps to its row by one compare-and-subtract when the window is at least a tile wide,
 // by a 32-bit division when it is narrower (the sum then fits 32 bits).  No lane divides 64-bit numbers on the copy and paste paths.
+//
+// ONE TILE FRAME.  The three kernels are one body (window_move) over two SIDES, each written once: the contiguous side and the raster
+// side say where a slot is one 16-byte access and walk its cells where it is not; a cut loads from the raster side and stores to the
+// contiguous one, a paste the other way round, a cut at another size gathers its source through two axes instead of loading it.
+// The walk over a row end (RowCursor) is the one k_window_resample uses too (ec_window_resample_kernels.hpp).  The slot itself and
+// the workgroup -> tile map are every tiled kernel's: ec_tile.hpp.  Registers and first timings: profiles/window/frame.md.
 #pragma once
 
-#include "ec_binop_kernels.hpp"
+#include "ec_tile.hpp"
 
 namespace ecd {
 
 constexpr int kWindowU = 4;  // 16-byte slots per lane per tile
-
-template <int W> struct width_cell;
-template <> struct width_cell<1> { using type = uint8_t; };
-template <> struct width_cell<2> { using type = uint16_t; };
-template <> struct width_cell<4> { using type = uint32_t; };
-template <> struct width_cell<8> { using type = uint64_t; };
+constexpr int kWindowTileSlots = kBlock * kWindowU;  // value slots per tile; the host counts a launch's tiles by it (window_tiles, ec_window_checks.hpp)
 
 // A window of a row-major raster and the contiguous side that faces it, in cells.
 struct WindowGeom {
@@ -59,33 +60,6 @@ __device__ __forceinline__ void axis_step(const WindowAxis& a, AxisPos& p) {
     }
 }
 
-// cell k of a slot's four dwords (k is a constant after unrolling)
-template <int W>
-__device__ __forceinline__ void slot_put(u32x4& v, int k, typename width_cell<W>::type c) {
-    if constexpr (W == 1) v[k >> 2] |= uint32_t(c) << (8 * (k & 3));
-    else if constexpr (W == 2) v[k >> 1] |= uint32_t(c) << (16 * (k & 1));
-    else if constexpr (W == 4) v[k] = c;
-    else {
-        v[2 * k] = uint32_t(c);
-        v[2 * k + 1] = uint32_t(c >> 32);
-    }
-}
-template <int W>
-__device__ __forceinline__ typename width_cell<W>::type slot_get(const u32x4& v, int k) {
-    using C = typename width_cell<W>::type;
-    if constexpr (W == 1) return C((v[k >> 2] >> (8 * (k & 3))) & 0xffu);
-    else if constexpr (W == 2) return C((v[k >> 1] >> (16 * (k & 1))) & 0xffffu);
-    else if constexpr (W == 4) return v[k];
-    else return uint64_t(v[2 * k]) | (uint64_t(v[2 * k + 1]) << 32);
-}
-
-// the 16-byte store of a value stream (write-through) or of a mask stream (nt_store / mask_store, ec_device.hpp)
-template <bool MASK_ST>
-__device__ __forceinline__ void slot_store(u32x4 v, void* p) {
-    if constexpr (MASK_ST) mask_store(v, static_cast<u32x4*>(p));
-    else nt_store(v, static_cast<u32x4*>(p));
-}
-
 struct RowCol {
     uint64_t row, col;
 };
@@ -101,7 +75,7 @@ __device__ __forceinline__ RowCol lane_row_col(uint64_t row0, uint64_t col0, uin
     return RowCol{row0 + q, uint64_t(x - q * w32)};
 }
 
-// What the three tile bodies share.  A tile is TILE_SLOTS slots of the contiguous side starting at cell `first`, which lies at
+// The lane map of a tile, which its two sides share.  A tile is TILE_SLOTS slots of the contiguous side starting at cell `first`, which lies at
 // (row0, col0) of the window; lane t owns slots t, t + 256, ... (NJ of them; the mask stream of a launch over wide cells has fewer
 // slots than lanes).
 template <int W, int TILE_SLOTS>
@@ -128,152 +102,134 @@ struct TileLanes {
     }
 };
 
-// ---- cut: contiguous[c] = raster[window cell c].  `cacheable`: the raster stream's load-policy bit (cache_plan, ec_runtime.hpp).
-template <int W, int TILE_SLOTS, bool MASK_ST>
-__device__ __forceinline__ void window_copy_tile(const typename width_cell<W>::type* __restrict__ src,
-                                                 typename width_cell<W>::type* __restrict__ dst, const WindowGeom& g, uint64_t first,
-                                                 uint64_t row0, uint64_t col0, unsigned cacheable) {
-    using C = typename width_cell<W>::type;
-    using L = TileLanes<W, TILE_SLOTS>;
-    constexpr int CPL = L::CPL, NJ = L::NJ;
-    const L t(g, first, row0, col0);
-    const C* __restrict__ win = src + g.origin;
-    u32x4 v[NJ];
-    policy_arms<1>(cacheable, [&](auto bits) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            v[j] = u32x4{0, 0, 0, 0};
-            if (t.one_row[j]) v[j] = load_vec<!(decltype(bits)::value & 1u)>(reinterpret_cast<const u32x4*>(win + t.rc[j].row * g.pitch + t.rc[j].col));
-        }
-    });
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        if (t.live[j] && !t.one_row[j]) {  // over a row end, or the last cells of the window: cell by cell
-            uint64_t col = t.rc[j].col;
-            const C* p = win + t.rc[j].row * g.pitch + col;
-#pragma unroll
-            for (int k = 0; k < CPL; ++k) {
-                if (t.c0[j] + k < g.n) {
-                    slot_put<W>(v[j], k, ld_cell(p));
-                    ++p;
-                    if (++col == g.w) {
-                        col = 0;
-                        p += g.pitch - g.w;
-                    }
-                }
-            }
+// The row-end cursor: a walk over cells in the order of the contiguous side.  It owns the column; where the walk stands on the raster
+// side is the caller's (a cell pointer for the copy and the paste, a pair of axis positions for the resampling kernels), and so is
+// `row_end`, which takes that position from the last cell of a row of the window to the first cell of the next.
+struct RowCursor {
+    uint64_t col, w;
+    template <typename E>
+    __device__ __forceinline__ void next(E&& row_end) {
+        if (++col == w) {
+            col = 0;
+            row_end();
         }
     }
+};
+// cell(k) for the cells of a slot that exist — cell k is cell c0 + k of the n the contiguous side has — each followed by the cursor's step
+template <int CPL, typename F, typename E>
+__device__ __forceinline__ void walk_slot(uint64_t c0, uint64_t n, RowCursor at, F&& cell, E&& row_end) {
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        if (t.whole[j]) {
-            slot_store<MASK_ST>(v[j], dst + t.c0[j]);
-        } else if (t.live[j]) {
-#pragma unroll
-            for (int k = 0; k < CPL; ++k)
-                if (t.c0[j] + k < g.n) st_cell(slot_get<W>(v[j], k), dst + t.c0[j] + k);
+    for (int k = 0; k < CPL; ++k) {
+        if (c0 + k < n) {
+            cell(k);
+            at.next(row_end);
         }
     }
 }
 
-// ---- paste: raster[window cell c] = contiguous[c].  Vector stores only inside one row of the window; nothing outside it is written.
-template <int W, int TILE_SLOTS, bool MASK_ST>
-__device__ __forceinline__ void window_put_tile(const typename width_cell<W>::type* __restrict__ tile,
-                                                typename width_cell<W>::type* __restrict__ dst, const WindowGeom& g, uint64_t first,
-                                                uint64_t row0, uint64_t col0, unsigned cacheable) {
+// The two sides of a tile as its body sees them (P: a pointer to cells, const on the side that is read).  Slot j is ONE 16-byte access
+// at at(j) where vector(j) holds; else cells(j, f) calls f(k, p) for each of its cells that exists, p where cell k lies.
+// The contiguous side: a slot's cells follow one another; it is whole unless it holds the last cells of the tile.
+template <typename P, typename L>
+struct ContiguousSide {
+    P base;
+    const L& t;
+    uint64_t n;
+    __device__ __forceinline__ bool vector(int j) const { return t.whole[j]; }
+    __device__ __forceinline__ P at(int j) const { return base + t.c0[j]; }
+    template <typename F>
+    __device__ __forceinline__ void cells(int j, F&& f) const {
+#pragma unroll
+        for (int k = 0; k < L::CPL; ++k)
+            if (t.c0[j] + k < n) f(k, base + t.c0[j] + k);
+    }
+};
+// The raster side (`win`: the window's first cell): a whole slot inside one row of the window is one under-aligned access; over a
+// row end the cursor takes it cell by cell, so that a paste writes nothing outside its window.
+template <typename P, typename L>
+struct RasterSide {
+    P win;
+    const L& t;
+    const WindowGeom& g;
+    __device__ __forceinline__ bool vector(int j) const { return t.one_row[j]; }
+    __device__ __forceinline__ P at(int j) const { return win + t.rc[j].row * g.pitch + t.rc[j].col; }
+    template <typename F>
+    __device__ __forceinline__ void cells(int j, F&& f) const {
+        P p = at(j);
+        walk_slot<L::CPL>(t.c0[j], g.n, RowCursor{t.rc[j].col, g.w}, [&](int k) { f(k, p++); }, [&] { p += g.pitch - g.w; });
+    }
+};
+
+// One slot of a cut at another size: contiguous[(i, j)] = raster[window cell (rows(i), cols(j))], gathered cell by cell.  The source
+// row is found once per slot and stepped at a row end of the output, not per cell.  NT: the arm of the load policy.
+template <int W, bool NT>
+__device__ __forceinline__ void nearest_slot(u32x4& v, const typename width_cell<W>::type* win, const WindowGeom& g, uint64_t c0, RowCol rc,
+                                             const WindowAxis& ax, const WindowAxis& ay) {
     using C = typename width_cell<W>::type;
-    using L = TileLanes<W, TILE_SLOTS>;
-    constexpr int CPL = L::CPL, NJ = L::NJ;
-    const L t(g, first, row0, col0);
-    C* __restrict__ win = dst + g.origin;
+    AxisPos y = axis_at(ay, rc.row), x = axis_at(ax, rc.col);
+    const C* row = win + y.src * g.pitch;
+    walk_slot<16 / W>(
+        c0, g.n, RowCursor{rc.col, g.w},
+        [&](int k) {
+            C c;
+            if constexpr (NT) c = ld_cell(row + x.src);
+            else c = row[x.src];
+            slot_put<W>(v, k, c);
+            axis_step(ax, x);
+        },
+        [&] {
+            x = axis_first(ax);
+            axis_step(ay, y);
+            row = win + y.src * g.pitch;
+        });
+}
+
+// The tile body: the lanes' slots, zeroed, are filled from one side and stored to the other.  All 16-byte loads of the tile are
+// issued in one arm of the load policy (`cacheable`: the loaded stream's bit, cache_plan, ec_runtime.hpp) before any cell-wise
+// access, and every load comes before the first store.  AXES: none for the copy and the paste; the two axes of a nearest-neighbour
+// cut, whose source side is gathered (nearest_slot) in the arm instead.
+template <int W, bool MASK_ST, typename L, typename FROM, typename TO, typename... AXES>
+__device__ __forceinline__ void window_move(const L& t, const FROM& from, const TO& to, unsigned cacheable, const AXES&... axes) {
+    constexpr int NJ = L::NJ;
+    constexpr bool GATHER = sizeof...(AXES) != 0;
     u32x4 v[NJ];
     policy_arms<1>(cacheable, [&](auto bits) {
+        constexpr bool NT = !(decltype(bits)::value & 1u);
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             v[j] = u32x4{0, 0, 0, 0};
-            if (t.whole[j]) v[j] = load_vec<!(decltype(bits)::value & 1u)>(reinterpret_cast<const u32x4*>(tile + t.c0[j]));
+            if constexpr (GATHER) {
+                if (t.live[j]) nearest_slot<W, NT>(v[j], from.win, from.g, t.c0[j], t.rc[j], axes...);
+            } else {
+                if (from.vector(j)) v[j] = load_vec<NT>(reinterpret_cast<const u32x4*>(from.at(j)));
+            }
         }
     });
+    if constexpr (!GATHER) {
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        if (t.live[j] && !t.whole[j]) {  // the last cells of the tile
-#pragma unroll
-            for (int k = 0; k < CPL; ++k)
-                if (t.c0[j] + k < g.n) slot_put<W>(v[j], k, ld_cell(tile + t.c0[j] + k));
-        }
+        for (int j = 0; j < NJ; ++j)
+            if (t.live[j] && !from.vector(j)) from.cells(j, [&](int k, auto p) { slot_put<W>(v[j], k, ld_cell(p)); });
     }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-        C* p = win + t.rc[j].row * g.pitch + t.rc[j].col;
-        if (t.one_row[j]) {
-            slot_store<MASK_ST>(v[j], p);
-        } else if (t.live[j]) {
-            uint64_t col = t.rc[j].col;
-#pragma unroll
-            for (int k = 0; k < CPL; ++k) {
-                if (t.c0[j] + k < g.n) {
-                    st_cell(slot_get<W>(v[j], k), p);
-                    ++p;
-                    if (++col == g.w) {
-                        col = 0;
-                        p += g.pitch - g.w;
-                    }
-                }
-            }
-        }
+        if (to.vector(j)) slot_store<MASK_ST>(v[j], to.at(j));
+        else if (t.live[j]) to.cells(j, [&](int k, auto p) { st_cell(slot_get<W>(v[j], k), p); });
     }
 }
 
-// ---- cut and resample: contiguous[(i, j)] = raster[window cell (rows(i), cols(j))], per-cell gathers, 16-byte stores.  The source row
-// is found once per slot and stepped at a row end of the output, not per cell.
-template <int W, int TILE_SLOTS, bool MASK_ST>
-__device__ __forceinline__ void window_nearest_tile(const typename width_cell<W>::type* __restrict__ src,
-                                                    typename width_cell<W>::type* __restrict__ dst, const WindowGeom& g,
-                                                    const WindowAxis& ax, const WindowAxis& ay, uint64_t first, uint64_t row0,
-                                                    uint64_t col0, unsigned cacheable) {
+enum { kWinCopy = 0, kWinPut = 1 };
+
+// One stream of a launch, values or mask bytes, over a tile of TILE_SLOTS slots that starts at cell `first` = (row0, col0) of the
+// window.  cut: contiguous[c] = raster[window cell c], at the window's size or (with axes) at another; paste: the other way round.
+template <int W, int TILE_SLOTS, bool MASK_ST, int KIND, typename... AXES>
+__device__ __forceinline__ void window_tile(const typename width_cell<W>::type* __restrict__ in, typename width_cell<W>::type* __restrict__ out,
+                                            const WindowGeom& g, uint64_t first, uint64_t row0, uint64_t col0, unsigned cacheable,
+                                            const AXES&... axes) {
     using C = typename width_cell<W>::type;
     using L = TileLanes<W, TILE_SLOTS>;
-    constexpr int CPL = L::CPL, NJ = L::NJ;
     const L t(g, first, row0, col0);
-    const C* __restrict__ win = src + g.origin;
-    u32x4 v[NJ];
-    policy_arms<1>(cacheable, [&](auto bits) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            v[j] = u32x4{0, 0, 0, 0};
-            if (t.live[j]) {
-                AxisPos y = axis_at(ay, t.rc[j].row), x = axis_at(ax, t.rc[j].col);
-                uint64_t col = t.rc[j].col;
-                const C* row = win + y.src * g.pitch;
-#pragma unroll
-                for (int k = 0; k < CPL; ++k) {
-                    if (t.c0[j] + k < g.n) {
-                        C c;
-                        if constexpr (decltype(bits)::value & 1u) c = row[x.src];
-                        else c = ld_cell(row + x.src);
-                        slot_put<W>(v[j], k, c);
-                        axis_step(ax, x);
-                        if (++col == g.w) {
-                            col = 0;
-                            x = axis_first(ax);
-                            axis_step(ay, y);
-                            row = win + y.src * g.pitch;
-                        }
-                    }
-                }
-            }
-        }
-    });
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        if (t.whole[j]) {
-            slot_store<MASK_ST>(v[j], dst + t.c0[j]);
-        } else if (t.live[j]) {
-#pragma unroll
-            for (int k = 0; k < CPL; ++k)
-                if (t.c0[j] + k < g.n) st_cell(slot_get<W>(v[j], k), dst + t.c0[j] + k);
-        }
-    }
+    if constexpr (KIND == kWinPut) window_move<W, MASK_ST>(t, ContiguousSide<const C*, L>{in, t, g.n}, RasterSide<C*, L>{out + g.origin, t, g}, cacheable);
+    else window_move<W, MASK_ST>(t, RasterSide<const C*, L>{in + g.origin, t, g}, ContiguousSide<C*, L>{out, t, g.n}, cacheable, axes...);
 }
 
 // Launch arguments: the value stream (raster side / contiguous side) and, for MASKED launches, the mask stream over the same cells.
@@ -287,35 +243,26 @@ struct WindowArgs {
     unsigned cacheable;
 };
 
-enum { kWinCopy = 0, kWinPut = 1 };
-
-// One workgroup per tile of kBlock * kWindowU value slots; the mask bytes of the SAME cells are 1 / W as many slots, with their own
-// lane map (16 mask bytes per lane, as mask_and_body has), so one division serves both streams.
-template <int W, bool MASKED, int KIND>
-__device__ __forceinline__ void window_body(const WindowArgs& a, const WindowAxis* ax, const WindowAxis* ay) {
+// One workgroup per tile of kWindowTileSlots value slots; the mask bytes of the SAME cells are 1 / W as many slots, with their own
+// lane map (16 mask bytes per lane, as the binop's mask_and_body has), so one division serves both streams.  The axes of a
+// nearest-neighbour cut come by reference to the kernel's own arguments: nothing takes their address, so they stay in registers.
+template <int W, bool MASKED, int KIND, typename... AXES>
+__device__ __forceinline__ void window_body(const WindowArgs& a, const AXES&... axes) {
     using C = typename width_cell<W>::type;
-    constexpr int SLOTS = kBlock * kWindowU, MSLOTS = SLOTS / W;
+    constexpr int SLOTS = kWindowTileSlots, MSLOTS = SLOTS / W;
     const uint64_t first = uint64_t(two_front_tile()) * (uint64_t(SLOTS) * (16 / W));
     const uint64_t row0 = first / a.g.w, col0 = first - row0 * a.g.w;  // wave-uniform, once per workgroup
     if (first >= a.g.n) return;
-    if (ax) {
-        window_nearest_tile<W, SLOTS, false>(static_cast<const C*>(a.in), static_cast<C*>(a.out), a.g, *ax, *ay, first, row0, col0, a.cacheable);
-        if constexpr (MASKED) window_nearest_tile<1, MSLOTS, true>(a.in_mask, a.out_mask, a.g, *ax, *ay, first, row0, col0, a.cacheable >> 1);
-    } else if constexpr (KIND == kWinCopy) {
-        window_copy_tile<W, SLOTS, false>(static_cast<const C*>(a.in), static_cast<C*>(a.out), a.g, first, row0, col0, a.cacheable);
-        if constexpr (MASKED) window_copy_tile<1, MSLOTS, true>(a.in_mask, a.out_mask, a.g, first, row0, col0, a.cacheable >> 1);
-    } else {
-        window_put_tile<W, SLOTS, false>(static_cast<const C*>(a.in), static_cast<C*>(a.out), a.g, first, row0, col0, a.cacheable);
-        if constexpr (MASKED) window_put_tile<1, MSLOTS, true>(a.in_mask, a.out_mask, a.g, first, row0, col0, a.cacheable >> 1);
-    }
+    window_tile<W, SLOTS, false, KIND>(static_cast<const C*>(a.in), static_cast<C*>(a.out), a.g, first, row0, col0, a.cacheable, axes...);
+    if constexpr (MASKED) window_tile<1, MSLOTS, true, KIND>(a.in_mask, a.out_mask, a.g, first, row0, col0, a.cacheable >> 1, axes...);
 }
 
 template <int W, bool MASKED>
-__global__ __launch_bounds__(kBlock) void k_window_copy(WindowArgs a) { window_body<W, MASKED, kWinCopy>(a, nullptr, nullptr); }
+__global__ __launch_bounds__(kBlock) void k_window_copy(WindowArgs a) { window_body<W, MASKED, kWinCopy>(a); }
 template <int W, bool MASKED>
-__global__ __launch_bounds__(kBlock) void k_window_put(WindowArgs a) { window_body<W, MASKED, kWinPut>(a, nullptr, nullptr); }
+__global__ __launch_bounds__(kBlock) void k_window_put(WindowArgs a) { window_body<W, MASKED, kWinPut>(a); }
 template <int W, bool MASKED>
-__global__ __launch_bounds__(kBlock) void k_window_nearest(WindowArgs a, WindowAxis ax, WindowAxis ay) { window_body<W, MASKED, kWinCopy>(a, &ax, &ay); }
+__global__ __launch_bounds__(kBlock) void k_window_nearest(WindowArgs a, WindowAxis ax, WindowAxis ay) { window_body<W, MASKED, kWinCopy>(a, ax, ay); }
 
 // ---- the comparison path ("unaligned_vector" = 0 and a row start that is not 16-byte aligned): one cell per lane, plain accesses.
 // A workgroup takes 256 cells of one row of the contiguous side at a time.  PUT = false serves the cut at either size (the copy is

@@ -38,19 +38,13 @@ static const char* make_resample_axis(int32_t alg, uint64_t win, uint64_t out, R
     return nullptr;
 }
 
-// workgroups of a launch over n output cells of `cell` bytes: one per tile of kBlock * kWindowU 16-byte slots
-static uint64_t resample_tiles(uint64_t n, size_t cell) {
-    const uint64_t per_slot = 16 / cell, slots = n / per_slot + (n % per_slot != 0), per_tile = uint64_t(kBlock) * kWindowU;
-    return slots / per_tile + (slots % per_tile != 0);
-}
-
 template <typename T, bool MASKED>
 static ec_status launch_resample(const ResampleArgs& args, uint64_t win_cells, hipStream_t s) {
     constexpr size_t W = sizeof(T);
     ResampleArgs a = args;
     const size_t bytes[2] = {win_cells * W, MASKED ? win_cells : 0};  // the streams that are loaded: the window's cells and mask bytes
     a.w.cacheable = cache_plan(bytes, 2);
-    return split_launch(resample_tiles(a.w.g.n, W), "window(resample)", [&](size_t first, unsigned grid) {  // at most 2^31 - 1 tiles: checked by the caller
+    return split_launch(window_tiles(a.w.g.n, W, kWindowTileSlots), "window(resample)", [&](size_t first, unsigned grid) {  // at most 2^31 - 1 tiles: checked by the caller
         a.first_tile = first;
         k_window_resample<T, MASKED><<<grid, kBlock, 0, s>>>(a);
     });
@@ -93,7 +87,7 @@ extern "C" ec_status ec_window_resample(int32_t alg, ec_dtype t, const void* src
     if (alg == EC_RESAMPLE_BILINEAR && (u128)4 * out_cols * out_rows > UINT64_MAX)  // out_cols * out_rows fits: checked above
         return set_error(EC_ERR_ARG, "ec_window_resample: the total weight 4 * %llu * %llu of a bilinear footprint overflows 64 bits",
                          (unsigned long long)out_cols, (unsigned long long)out_rows);
-    if (resample_tiles(out_cols * out_rows, ecl::size_of(t)) > 0x7fffffffu)
+    if (window_tiles(out_cols * out_rows, ecl::size_of(t), kWindowTileSlots) > 0x7fffffffu)
         return set_error(EC_ERR_ARG, "ec_window_resample: an output of %llu x %llu cells is more than 2^31 - 1 tiles", (unsigned long long)out_cols,
                          (unsigned long long)out_rows);
     st = ensure_ready();

@@ -12,16 +12,17 @@
 // host fills ResampleAxis; the kernel never learns which algorithm it runs.  From j to j + 1 the run start moves by `num` units = q cells
 // and r units, so a lane divides once per axis for its slot's first cell and steps the others (tap_at / tap_step, as axis_at / axis_step).
 //
-// OUTPUT SIDE: the shape of the other window kernels — 256-thread workgroups, one workgroup per tile of kBlock * kWindowU 16-byte
-// value slots, two fronts, nt_store for a whole value slot, cell-wise stores for the last partial slot.  The mask byte of an output cell
-// is a by-product of its value (wsum != 0), so the lane that owns a value slot also owns the 16 / W mask bytes of the same cells and
-// writes them as ONE mask_store of that width (16, 8, 4, 2 bytes: neighbouring lanes write neighbouring bytes); a lane map of its own
-// for the mask stream, as the copies have, would walk every footprint twice.
+// OUTPUT SIDE: the shape of the other window kernels — 256-thread workgroups, one workgroup per tile of kWindowTileSlots 16-byte
+// value slots, two fronts, the lane map and the row-end cursor of ec_window_kernels.hpp (lane_row_col, RowCursor), nt_store for a whole
+// value slot, cell-wise stores for the last partial slot.  The mask byte of an output cell is a by-product of its value (wsum != 0), so
+// the lane that owns a value slot also owns the 16 / W mask bytes of the same cells and writes them as ONE mask_store of that width
+// (16, 8, 4, 2 bytes: neighbouring lanes write neighbouring bytes) — SlotMask and slot_store_pair of ec_tile.hpp, which the focal
+// kernels end their slots with too; a lane map of its own for the mask stream, as the copies have, would walk every footprint twice.
 // SOURCE SIDE: cell loads under the launch's cache_plan bits.  A footprint row is a run of at most 65 cells and neighbouring lanes' runs
 // are neighbours or overlap, so a line is wanted several times within a workgroup; whether it stays cacheable is the host's call.
 // Slots and cells are walked by loops that are NOT unrolled, so that the code stays small (ten types x masked or not x the policy arms);
-// what that costs beside a cell's taps (up to 65 x 65 of them) is not measured: throughput is unmeasured as a whole, tools/window_bench.py
-// rows (f)-(h).
+// what that costs beside a cell's taps (up to 65 x 65 of them) is not measured.  First timings of tools/window_bench.py rows (f)-(h):
+// profiles/window/frame.md; what bounds the kernel is not looked into there.
 #pragma once
 
 #include "ec_cast_cell.hpp"
@@ -128,10 +129,9 @@ struct ResampleArgs {
 
 template <typename T, bool MASKED>
 __global__ __launch_bounds__(kBlock) void k_window_resample(ResampleArgs a) {
-    constexpr int W = sizeof(T), CPL = 16 / W, SLOTS = kBlock * kWindowU;
+    constexpr int W = sizeof(T), CPL = 16 / W, SLOTS = kWindowTileSlots;
     constexpr uint32_t SPAN = uint32_t(SLOTS) * CPL;
     using C = typename width_cell<W>::type;
-    using M = typename byte_words<CPL>::type;  // the mask bytes of one value slot
     const WindowGeom& g = a.w.g;
     const uint64_t first = uint64_t(two_front_tile(a.first_tile)) * SPAN;
     if (first >= g.n) return;
@@ -140,6 +140,7 @@ __global__ __launch_bounds__(kBlock) void k_window_resample(ResampleArgs a) {
     const uint8_t* __restrict__ mwin = MASKED ? a.w.in_mask + g.origin : nullptr;
     C* __restrict__ dst = static_cast<C*>(a.w.out);
     uint8_t* __restrict__ dmask = a.w.out_mask;
+    if constexpr (MASKED) __builtin_assume(dmask != nullptr);  // both masks or neither (check_window): slot_store_pair's test folds away
     policy_arms<MASKED ? 2 : 1>(a.w.cacheable, [&](auto bits) {
 #pragma unroll 1
         for (uint32_t s = threadIdx.x; s < uint32_t(SLOTS); s += kBlock) {
@@ -150,8 +151,9 @@ __global__ __launch_bounds__(kBlock) void k_window_resample(ResampleArgs a) {
             const uint32_t cells = g.n - c0 < uint64_t(CPL) ? uint32_t(g.n - c0) : uint32_t(CPL);
             const bool whole = cells == uint32_t(CPL) && !a.cellwise_stores;
             TapPos y = tap_at(a.ay, rc.row), x = tap_at(a.ax, rc.col);
-            uint64_t col = rc.col;
-            uint64_t lo = 0, hi = 0, mlo = 0, mhi = 0;  // the slot's 16 value bytes and up to 16 mask bytes
+            RowCursor at{rc.col, g.w};
+            uint64_t lo = 0, hi = 0;  // the slot's 16 value bytes, packed by shifts: k is a loop counter here, an array would go to scratch
+            SlotMask m;
 #pragma unroll 1
             for (uint32_t k = 0; k < cells; ++k) {
                 bool valid;
@@ -161,31 +163,18 @@ __global__ __launch_bounds__(kBlock) void k_window_resample(ResampleArgs a) {
                     const uint32_t sh = (k * 8 * W) & 63u;
                     if (k * W < 8) lo |= uint64_t(c) << sh;
                     else hi |= uint64_t(c) << sh;
-                    if constexpr (MASKED) {
-                        if (k < 8) mlo |= uint64_t(valid) << (8 * k);
-                        else mhi |= uint64_t(valid) << (8 * (k & 7u));
-                    }
+                    if constexpr (MASKED) m.put(k, valid);
                 } else {
                     st_cell(c, dst + c0 + k);
                     if constexpr (MASKED) st_cell(uint8_t(valid), dmask + c0 + k);
                 }
                 tap_step(a.ax, x);
-                if (++col == g.w) {
-                    col = 0;
+                at.next([&] {
                     x = tap_first(a.ax);
                     tap_step(a.ay, y);
-                }
+                });
             }
-            if (whole) {
-                nt_store(u32x4{uint32_t(lo), uint32_t(lo >> 32), uint32_t(hi), uint32_t(hi >> 32)}, reinterpret_cast<u32x4*>(dst + c0));
-                if constexpr (MASKED) {
-                    M m;
-                    if constexpr (CPL == 16) m = M{uint32_t(mlo), uint32_t(mlo >> 32), uint32_t(mhi), uint32_t(mhi >> 32)};
-                    else if constexpr (CPL == 8) m = M{uint32_t(mlo), uint32_t(mlo >> 32)};
-                    else m = static_cast<M>(mlo);
-                    mask_store(m, reinterpret_cast<M*>(dmask + c0));
-                }
-            }
+            if (whole) slot_store_pair<CPL>(u32x4{uint32_t(lo), uint32_t(lo >> 32), uint32_t(hi), uint32_t(hi >> 32)}, m, dst, MASKED ? dmask : nullptr, c0);
         }
     });
 }

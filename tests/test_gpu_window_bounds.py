@@ -83,11 +83,12 @@ def single_rows(W):
 
 def shapes(W):
     """(w, h) of the contiguous side: the single rows, odd-width blocks below a tile, above one and above two, narrow windows
-    whose slots span several rows, and one block whose rows all start on 16-byte boundaries at every width"""
+    whose slots span several rows, one block whose rows all start on 16-byte boundaries at every width, and three rows one cell
+    wider than a tile: the lane map's wide branch (the window at least a tile wide) with slots that wrap into the next row"""
     c, t = cpl(W), tile(W)
     multi = [_odd_rows(t - c, t), _odd_rows(t, t + c), _odd_rows(2 * t, 2 * t + 64)]
     narrow = [(1, c + 3), (3, c // 3 + 2)]
-    return [(n, 1) for n in single_rows(W)] + multi + narrow + [(48, 5)]
+    return [(n, 1) for n in single_rows(W)] + multi + narrow + [(t + 1, 3), (48, 5)]
 
 
 def put_x0s(W):

@@ -72,6 +72,7 @@ class Cut:
 def _store(arena, at, data, stray=False):
     """`data` at byte `at` of the payload (negative: in front of it; beyond its end: behind it)"""
     lo = arena.lo + at
+    data = data[:max(0, arena.mem.size - lo)]   # the image ends with the high guard: what a stray store writes behind it no arena sees
     arena.mem[lo:lo + data.size] = _differing(data, arena.mem[lo:lo + data.size]) if stray else data
 
 

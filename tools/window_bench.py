@@ -49,7 +49,7 @@ def main():
             fn(k % sets)
         torch.cuda.synchronize()
         rounds, total, calls = 1, 0.0, 0
-        while total < min_ms:
+        while calls == 0 or total < min_ms:  # at least one rotation: row (c) asks for no minimum
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(rounds):
