@@ -10,7 +10,8 @@
 // kernels (ec_distance_kernels.hpp) run a row tile by tile out of LDS — and get what one call over the whole line gives.  Every loop
 // is bounded by a count the caller passes or by the stack's depth: a corrupt stack gives wrong cells, never a spin.
 //
-// Also here, because the host and the tests need them without a device: the launch constants and the layout of the workspace.
+// Also here, because the host and the tests need them without a device: the launch constants, the layout of the workspace and the
+// call's refusals (over ec_refusal.hpp).
 //
 // Self-contained like ec_focal_rank_cell.hpp and ec_order_key.hpp: no HIP runtime include; host/test_distance_line.cpp runs these
 // very functions under a plain C++ compiler and the address and undefined-behaviour sanitizers.
@@ -20,6 +21,7 @@
 #include <stdint.h>
 
 #include "ec_order_key.hpp"  // EC_HD
+#include "ec_refusal.hpp"
 
 #if defined(__clang__)
 #define EC_DIST_UNROLL _Pragma("unroll")
@@ -56,6 +58,28 @@ constexpr DistWorkspace dist_workspace(uint64_t cols, uint64_t rows) {
 }
 constexpr size_t dist_workspace_bytes(uint64_t cols, uint64_t rows) {
     return dist_valid_side(cols) && dist_valid_side(rows) ? dist_workspace(cols, rows).bytes : 0;
+}
+
+// ---- the refusals ------------------------------------------------------------------------------------------------------------
+// Why ec_distance refuses a call, or nothing; the order is the header's, the overlaps output-major.  known_type: out_type is a
+// cell type's code; out_size: 4 for EC_U32, 8 for EC_F64, 0 for every other.  Pointers are compared, never dereferenced.
+inline ecv::Refusal distance_refusal(const void* mask, uint64_t cols, uint64_t rows, bool known_type, size_t out_size, const void* dst,
+                                     const void* dst_mask, const void* workspace) {
+    if (!dist_valid_side(cols) || !dist_valid_side(rows)) return {"cols and rows must be within 1 .. EC_DISTANCE_MAX_SIDE"};
+    if (!known_type) return {"bad out_type", true};
+    if (out_size == 0) return {"out_type is neither EC_U32 nor EC_F64"};
+    if (!mask) return {"null mask"};
+    if (!dst && !dst_mask) return {"dst and dst_mask are both NULL"};
+    if (ecv::misaligned(dst, out_size)) return {"dst is not aligned to its cell type"};
+    const size_t n = size_t(cols * rows);
+    const ecv::Span in{mask, n}, out{dst, n * out_size}, out_mask{dst_mask, n}, work{workspace, dist_workspace_bytes(cols, rows)};
+    const ecv::OverlapRow overlaps[] = {{out, in, "dst overlaps the mask"},
+                                        {out_mask, in, "dst_mask overlaps the mask"},
+                                        {work, in, "the workspace overlaps the mask"},
+                                        {out, out_mask, "dst_mask overlaps dst"},
+                                        {work, out, "the workspace overlaps dst"},
+                                        {work, out_mask, "the workspace overlaps dst_mask"}};
+    return {ecv::first_overlap(overlaps)};
 }
 
 // ---- columns -----------------------------------------------------------------------------------------------------------------

@@ -1,11 +1,12 @@
 // ec_reclass.hip — reclassification (include/erased_cells.h: ec_reclass_table_build, ec_reclass): the refusals and the record
-// (ec_reclass_plan.hpp; before any device work and before the library asks for a device) and the launches of the kernels of
+// (ec_reclass_checks.hpp; before any device work and before the library asks for a device) and the launches of the kernels of
 // ec_reclass_kernels.hpp, in a translation unit of their own so the build stays parallel.  The sharded form is ec_sharded.hip's.
 // The family launches at the default tile shape only (ecr::kU = the default "map_u"), as ec_compare and ec_cast do.
 #include <hip/hip_runtime.h>
 
 #include "ec_dispatch.hpp"
 #include "ec_lattice.hpp"
+#include "ec_reclass_checks.hpp"
 #include "ec_reclass_kernels.hpp"
 #include "ec_runtime.hpp"
 
@@ -43,19 +44,17 @@ using namespace ecd;
 extern "C" ec_status ec_reclass_table_build(ec_dtype t, ec_dtype bt, const void* breaks_host, int32_t n_breaks, int32_t right, ec_dtype dt,
                                             const ec_value* values, const uint8_t* valid_or_null, const ec_value* nodata_or_null,
                                             void* table_host_out) {
-    bool bad_type = false;
-    if (const char* why = ecr::build(t, bt, breaks_host, n_breaks, right, dt, values, valid_or_null, nodata_or_null,
-                                     static_cast<ec_reclass_table*>(table_host_out), &bad_type))
-        return set_error(bad_type ? EC_ERR_UNSUPPORTED_TYPE : EC_ERR_ARG, "ec_reclass_table_build: %s (dtype %d, breaks of dtype %d, output dtype %d, %d breaks, right %d)",
-                         why, int(t), int(bt), int(dt), int(n_breaks), int(right));
+    if (const ecv::Refusal r = ecr::build(t, bt, breaks_host, n_breaks, right, dt, values, valid_or_null, nodata_or_null,
+                                          static_cast<ec_reclass_table*>(table_host_out)))
+        return refused(r, "ec_reclass_table_build", "(dtype %d, breaks of dtype %d, output dtype %d, %d breaks, right %d)", int(t), int(bt), int(dt),
+                       int(n_breaks), int(right));
     return EC_OK;
 }
 
 extern "C" ec_status ec_reclass(ec_dtype t, const void* src, const uint8_t* mask_or_null, size_t n, ec_dtype dt, const void* table_dev, void* dst,
                                 uint8_t* dst_mask_or_null, ec_stream stream) {
-    bool bad_type = false;
-    if (const char* why = ecr::reclass_refusal(ecl::size_of(t), ecl::size_of(dt), src, mask_or_null, n, table_dev, dst, dst_mask_or_null, &bad_type))
-        return set_error(bad_type ? EC_ERR_UNSUPPORTED_TYPE : EC_ERR_ARG, "ec_reclass: %s (dtype %d, output dtype %d, %zu cells)", why, int(t), int(dt), n);
+    if (const ecv::Refusal r = ecr::reclass_refusal(ecl::size_of(t), ecl::size_of(dt), src, mask_or_null, n, table_dev, dst, dst_mask_or_null))
+        return refused(r, "ec_reclass", "(dtype %d, output dtype %d, %zu cells)", int(t), int(dt), n);
     if (n == 0) return EC_OK;
     const ec_status st = ensure_ready();
     if (st != EC_OK) return st;

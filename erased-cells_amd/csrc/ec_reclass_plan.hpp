@@ -1,5 +1,6 @@
 // ec_reclass_plan.hpp — the host side of the reclassification (include/erased_cells.h: ec_reclass_table_build, ec_reclass) in
-// plain C++: the refusals and their order, the thresholds and the record's layout, and what the launch and the kernels share.
+// plain C++: the thresholds and the record's layout, and what the launch and the kernels share.  The refusals and the builder:
+// ec_reclass_checks.hpp.
 //
 // The thresholds.  For every pair of the lattice the cast t -> UT = union(t, bt) is monotone non-decreasing in t's own order,
 // and a break is never a NaN, so NaN payloads decide nothing: "UT(x) >= b" (right: "UT(x) > b") over the cells of type t is
@@ -115,46 +116,6 @@ inline uint64_t low_bytes(const ec_value& v, size_t size) {
     return bits;
 }
 
-// ec_reclass_table_build: why it refuses, or null with *out written — every byte of it.  The order is the header's; *bad_type
-// set: EC_ERR_UNSUPPORTED_TYPE, every other refusal is EC_ERR_ARG.  A refusal writes nothing to *out.
-inline const char* build(int t, int bt, const void* breaks, int32_t n_breaks, int32_t right, int dt, const ec_value* values, const uint8_t* valid,
-                         const ec_value* nodata, ec_reclass_table* out, bool* bad_type) {
-    *bad_type = false;
-    if (n_breaks < 1 || n_breaks > kMaxBreaks) return "n_breaks is not within 1 .. EC_RECLASS_MAX_BREAKS (255)";
-    if (right != 0 && right != 1) return "right is not 0 or 1";
-    if (!ecl::valid(t) || !ecl::valid(bt) || !ecl::valid(dt)) { *bad_type = true; return "bad dtype"; }
-    if (!breaks || !values || !out) return "null pointer";
-    for (int32_t c = 0; c <= n_breaks; ++c)
-        if (values[c].dtype != dt) return "a class value is not of the output's dtype";
-    if (nodata && nodata->dtype != dt) return "the nodata value is not of the output's dtype";
-    ec_reclass_table tab;
-    memset(&tab, 0, sizeof tab);
-    const char* why = with_pair(t, bt, [&](auto tt, auto bb) -> const char* {
-        using T = decltype(tt);
-        using BT = decltype(bb);
-        BT b[kMaxBreaks];
-        memcpy(b, breaks, size_t(n_breaks) * sizeof(BT));
-        if (const char* w = breaks_refusal<T, BT>(b, n_breaks)) return w;
-        tab.n_reached = thresholds<T, BT>(b, n_breaks, right != 0, tab.thr);
-        return nullptr;
-    });
-    if (why) return why;
-    tab.t = t;
-    tab.dt = dt;
-    tab.n_breaks = n_breaks;
-    const size_t w = ecl::size_of(dt);
-    for (int32_t c = 0; c <= n_breaks; ++c) tab.value_bits[c] = low_bytes(values[c], w);
-    bool drops = false;
-    for (int32_t c = 0; c < kSlots; ++c) {
-        tab.valid[c] = c <= n_breaks ? (valid ? valid[c] != 0 : 1) : 0;
-        drops = drops || (c <= n_breaks && !tab.valid[c]);
-    }
-    tab.flags = (nodata ? uint32_t(EC_RECLASS_HAS_NODATA) : 0u) | (drops ? uint32_t(EC_RECLASS_DROPS) : 0u);
-    tab.nodata_bits = nodata ? low_bytes(*nodata, w) : 0;
-    memcpy(out, &tab, sizeof tab);
-    return nullptr;
-}
-
 // c = #{ j < n_reached : thr[j] <= key }: the class through the record, as the kernels compute it (a plain loop here)
 inline int32_t class_of(const ec_reclass_table& tab, int64_t key) {
     int32_t c = 0;
@@ -172,31 +133,5 @@ constexpr int search_steps(int32_t n_reached) {
 // The tiles of a launch: groups of cpl cells, kBlock * kU groups per workgroup, one workgroup per tile.
 constexpr size_t cpl(size_t cell_size, size_t out_size) { return 16 / (cell_size > out_size ? cell_size : out_size); }
 constexpr uint64_t tiles(uint64_t n, size_t cpl_) { return (n / cpl_ + uint64_t(kBlock) * kU - 1) / (uint64_t(kBlock) * kU); }
-
-inline bool overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
-    if (!a || !b || abytes == 0 || bbytes == 0) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + bbytes && y < x + abytes;
-}
-
-// Why ec_reclass refuses a call, or null; the header's order.  cell_size / out_size: bytes of a cell of t / dt, 0 for a bad code.
-// n == 0 passes whatever the pointers are.
-inline const char* reclass_refusal(size_t cell_size, size_t out_size, const void* src, const void* mask, size_t n, const void* table, const void* dst,
-                                   const void* dst_mask, bool* bad_type) {
-    *bad_type = false;
-    if (cell_size == 0 || out_size == 0) { *bad_type = true; return "bad dtype"; }
-    if (n == 0) return nullptr;
-    if (!src || !table || !dst) return "null pointer";
-    if (reinterpret_cast<uintptr_t>(table) % 16 != 0) return "table_dev is not 16-byte aligned";
-    if (tiles(n, cpl(cell_size, out_size)) > kMaxTiles) return "more than 2^31 - 1 tiles";
-    const void* in[3] = {src, mask, table};
-    const size_t in_bytes[3] = {n * cell_size, n, size_t(EC_RECLASS_TABLE_BYTES)};
-    for (int k = 0; k < 3; ++k) {
-        if (overlap(dst, n * out_size, in[k], in_bytes[k])) return "dst overlaps an input (the operation is not in-place)";
-        if (overlap(dst_mask, n, in[k], in_bytes[k])) return "dst_mask overlaps an input";
-    }
-    if (overlap(dst, n * out_size, dst_mask, n)) return "dst_mask overlaps dst";
-    return nullptr;
-}
 
 }  // namespace ecr

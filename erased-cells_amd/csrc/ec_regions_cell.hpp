@@ -16,7 +16,8 @@
 // host/test_regions_cell.cpp, on plain words and on std::atomic under threads.  Every loop counts its steps for that program; the
 // kernels drop the counts.
 //
-// Also here, because the host and the tests need them without a device: the launch constants and the layout of the workspace.
+// Also here, because the host and the tests need them without a device: the launch constants, the layout of the workspace and the
+// call's refusals (over ec_refusal.hpp).
 //
 // Self-contained like ec_distance_line.hpp: no HIP runtime include.
 #pragma once
@@ -25,6 +26,7 @@
 #include <stdint.h>
 
 #include "ec_order_key.hpp"  // EC_HD
+#include "ec_refusal.hpp"
 
 namespace ecd {
 
@@ -56,6 +58,41 @@ constexpr RegWorkspace reg_workspace(uint64_t cols, uint64_t rows) {
 }
 constexpr size_t reg_workspace_bytes(uint64_t cols, uint64_t rows) {
     return reg_valid_side(cols) && reg_valid_side(rows) ? reg_workspace(cols, rows).bytes : 0;
+}
+
+// ---- the refusals ---------------------------------------------------------------------------------------------------------------
+// Why ec_regions refuses a call, or nothing; the order is the header's, the overlaps output-major.  cell_size: bytes of a cell of
+// src's type, 0 for a bad code (looked at only with a src); known_numbering: it is one of the two.  Pointers are compared, never dereferenced.
+inline ecv::Refusal regions_refusal(size_t cell_size, const void* src, const void* src_mask, uint64_t cols, uint64_t rows, int32_t connectivity,
+                                    bool known_numbering, const void* dst, const void* dst_mask, const void* n_regions, const void* workspace) {
+    if (!reg_valid_side(cols) || !reg_valid_side(rows)) return {"cols and rows must be within 1 .. EC_REGIONS_MAX_SIDE"};
+    if (src && cell_size == 0) return {"bad cell type", true};
+    if (connectivity != 4 && connectivity != 8) return {"connectivity is neither 4 nor 8"};
+    if (!known_numbering) return {"numbering is neither EC_REGIONS_ROOT nor EC_REGIONS_DENSE"};
+    if (!src && !src_mask) return {"src and src_mask are both NULL"};
+    if (!dst && !dst_mask && !n_regions) return {"dst, dst_mask and n_regions are all NULL"};
+    if (ecv::misaligned(src, src ? cell_size : 1)) return {"src is not aligned to its cell type"};
+    if (ecv::misaligned(dst, 4)) return {"dst is not aligned to its cell type"};
+    if (ecv::misaligned(n_regions, 8)) return {"n_regions is not aligned to 8 bytes"};
+    if (ecv::misaligned(workspace, 16)) return {"the workspace is not aligned to 16 bytes"};
+    const size_t n = size_t(cols * rows);
+    const ecv::Span cells{src, n * cell_size}, valid{src_mask, n}, out{dst, n * 4}, out_mask{dst_mask, n}, count{n_regions, 8},
+        work{workspace, reg_workspace_bytes(cols, rows)};
+    const ecv::OverlapRow overlaps[] = {{out, cells, "dst overlaps src"},
+                                       {out, valid, "dst overlaps src_mask"},
+                                       {out_mask, cells, "dst_mask overlaps src"},
+                                       {out_mask, valid, "dst_mask overlaps src_mask"},
+                                       {count, cells, "n_regions overlaps src"},
+                                       {count, valid, "n_regions overlaps src_mask"},
+                                       {work, cells, "the workspace overlaps src"},
+                                       {work, valid, "the workspace overlaps src_mask"},
+                                       {out, out_mask, "dst_mask overlaps dst"},
+                                       {count, out, "n_regions overlaps dst"},
+                                       {count, out_mask, "n_regions overlaps dst_mask"},
+                                       {work, out, "the workspace overlaps dst"},
+                                       {work, out_mask, "the workspace overlaps dst_mask"},
+                                       {work, count, "the workspace overlaps n_regions"}};
+    return {ecv::first_overlap(overlaps)};
 }
 
 // ---- the raster -----------------------------------------------------------------------------------------------------------------

@@ -47,6 +47,15 @@ ec_status set_error_text(ec_status code, const std::string& text) {
 
 const std::string& last_error_text() { return t_err; }
 
+ec_status refused(const ecv::Refusal& r, const char* who, const char* about_fmt, ...) {
+    char about[384];
+    va_list ap;
+    va_start(ap, about_fmt);
+    vsnprintf(about, sizeof about, about_fmt, ap);
+    va_end(ap);
+    return set_error(r.bad_type ? EC_ERR_UNSUPPORTED_TYPE : EC_ERR_ARG, "%s: %s %s", who, r.why, about);
+}
+
 ec_status set_narrowing(int src, int dst) {
     static const char* names[EC_NTYPES] = {"UInt8", "UInt16", "UInt32", "UInt64", "Int8",
                                            "Int16", "Int32", "Int64", "Float32", "Float64"};

@@ -13,6 +13,7 @@
 
 #include "ec_launch_split.hpp"  // kMaxGroups, part
 #include "ec_reduce_plan.hpp"  // kReduceU, kMaxReduceBlocks
+#include "ec_refusal.hpp"
 #include "erased_cells.h"
 
 namespace ecd {
@@ -73,6 +74,9 @@ ec_status set_error_text(ec_status code, const std::string& text);
 const std::string& last_error_text();
 ec_status set_narrowing(int src, int dst);
 std::atomic<int64_t>& lds_rule_launches();  // binop launches that took the LDS-staged variant by rule (ec_stat_get "binop_lds_rule_launches")
+// The status and text of a call that `r` refuses (r.why not null): EC_ERR_UNSUPPORTED_TYPE for a bad type, else EC_ERR_ARG, and
+// "<who>: <r.why> <about>", `about` being the family's own words on the call's arguments, printf-style.
+ec_status refused(const ecv::Refusal& r, const char* who, const char* about_fmt, ...) __attribute__((format(printf, 3, 4)));
 ec_status check_launch(const char* what);
 ec_status check_hip(hipError_t e, const char* what);
 // `otherwise` of a dispatch (ec_dispatch.hpp) whose entry point refused a bad dtype with its own text before: never returned
@@ -231,6 +235,19 @@ inline unsigned grid_capped(size_t blocks, int bpc) {
     if (blocks < 1) blocks = 1;
     const size_t cap = size_t(device_cus()) * size_t(bpc > 0 ? bpc : 8);
     return static_cast<unsigned>(blocks < cap ? blocks : cap);
+}
+
+// f(workspace) on the caller's block `own`, or — own null — on `bytes` bytes of the library's stream-ordered pool that go back to
+// it behind f's launches on the same stream: the call stays asynchronous.  f's status first, then the hand-back's.
+template <typename F>
+inline ec_status with_workspace(void* own, size_t bytes, ec_stream stream, F&& f) {
+    if (own) return f(own);
+    void* block = nullptr;
+    ec_status st = ec_alloc_async(&block, bytes, stream);
+    if (st != EC_OK) return st;
+    st = f(block);
+    const ec_status freed = ec_free_async(block, stream);
+    return st != EC_OK ? st : freed;
 }
 
 // Per-(device, stream) scratch for reduction partials (device) and results (pinned host).  The stream orders the LAUNCHES

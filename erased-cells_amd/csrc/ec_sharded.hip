@@ -43,7 +43,7 @@
 #include "ec_collective.hpp"
 #include "ec_hostpipe.hpp"
 #include "ec_lattice.hpp"
-#include "ec_reclass_plan.hpp"
+#include "ec_reclass_checks.hpp"
 #include "ec_runtime.hpp"
 #include "ec_worker.hpp"
 #include "ec_zonal_host.hpp"
@@ -605,9 +605,8 @@ extern "C" ec_status ec_sharded_reclass(ec_shard_group* g, ec_dtype t, const voi
     auto omv = dst_masks_or_null ? take(g, what, "dst_masks", dst_masks_or_null, n, &st) : std::vector<uint8_t*>(g->n, nullptr);
     if (st != EC_OK) return st;
     for (int i = 0; i < g->n; ++i) {  // every shard's own refusals of ec_reclass, here: nothing is posted after one
-        bool bad_type = false;
-        if (const char* why = ecr::reclass_refusal(ecl::size_of(t), ecl::size_of(dt), sv[i], mv[i], n[i], tv[i], dv[i], omv[i], &bad_type))
-            return set_error(EC_ERR_ARG, "%s: shard %d: %s", what, i, why);
+        if (const ecv::Refusal r = ecr::reclass_refusal(ecl::size_of(t), ecl::size_of(dt), sv[i], mv[i], n[i], tv[i], dv[i], omv[i]))
+            return set_error(EC_ERR_ARG, "%s: shard %d: %s", what, i, r.why);
     }
     std::lock_guard<std::mutex> lk(g->call_mu);
     return post_each_shard(g, [g, t, dt, src = std::move(sv), m = std::move(mv), tab = std::move(tv), dst = std::move(dv), om = std::move(omv),

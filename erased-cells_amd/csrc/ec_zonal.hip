@@ -62,10 +62,8 @@ static ec_status dispatch_zonal(int t, const void* p, const uint8_t* mask, int z
 // What ec_zonal_stats_device refuses before any device work (the order: ec_zonal_plan.hpp stats_refusal).
 static ec_status check_zonal_args(const char* who, ec_dtype t, const void* p, const uint8_t* mask, ec_dtype zt, const void* zones, size_t n,
                                   int32_t n_zones, const void* out, size_t out_bytes, const void* workspace, bool caller_workspace) {
-    bool bad_type = false;
-    const char* why = ecz::stats_refusal(n_zones, ecl::size_of(t), zt, p, mask, zones, n, stats_max_cells(t), out, out_bytes, workspace,
-                                         caller_workspace, &bad_type);
-    return zonal_refused(who, why, bad_type, t, zt, n, n_zones);
+    const ecv::Refusal r = ecz::stats_refusal(n_zones, ecl::size_of(t), zt, p, mask, zones, n, stats_max_cells(t), out, out_bytes, workspace, caller_workspace);
+    return zonal_refused(who, r, t, zt, n, n_zones);
 }
 
 // The n_zones records of one launch at HOST address recs (records_host).  Arguments checked by the caller (check_zonal_args with
@@ -118,7 +116,6 @@ extern "C" ec_status ec_zonal_stats_compute(ec_dtype t, const void* p, const uin
 
 extern "C" ec_status ec_zonal_broadcast(ec_dtype zt, const void* zones, size_t n, int32_t n_zones, ec_dtype t, const void* table_dev, void* dst,
                                         uint8_t* dst_mask_or_null, ec_stream stream) {
-    bool bad_type = false;
-    const char* why = ecz::broadcast_refusal(n_zones, ecl::size_of(t), zt, zones, table_dev, n, dst, dst_mask_or_null, &bad_type);
-    return zonal_gather_call<BroadcastKernels>("ec_zonal_broadcast", why, bad_type, zt, zones, n, n_zones, t, table_dev, dst, dst_mask_or_null, stream);
+    const ecv::Refusal r = ecz::broadcast_refusal(n_zones, ecl::size_of(t), zt, zones, table_dev, n, dst, dst_mask_or_null);
+    return zonal_gather_call<BroadcastKernels>("ec_zonal_broadcast", r, zt, zones, n, n_zones, t, table_dev, dst, dst_mask_or_null, stream);
 }

@@ -26,11 +26,9 @@ static ec_status with_zone_type(int zt, F&& f) {
     return kTypeChecked;
 }
 
-// EC_OK for no refusal (`why` null), else the status and text of every zonal entry point's refusal.
-inline ec_status zonal_refused(const char* who, const char* why, bool bad_type, ec_dtype t, ec_dtype zt, size_t n, int32_t n_zones) {
-    if (!why) return EC_OK;
-    return set_error(bad_type ? EC_ERR_UNSUPPORTED_TYPE : EC_ERR_ARG, "%s: %s (dtype %d, zones of dtype %d, %zu cells, %d zones)", who, why, int(t), int(zt),
-                     n, int(n_zones));
+// EC_OK for no refusal, else the status and text of every zonal entry point's refusal.
+inline ec_status zonal_refused(const char* who, const ecv::Refusal& r, ec_dtype t, ec_dtype zt, size_t n, int32_t n_zones) {
+    return r ? refused(r, who, "(dtype %d, zones of dtype %d, %zu cells, %d zones)", int(t), int(zt), n, int(n_zones)) : EC_OK;
 }
 
 // The n_zones records of one call at HOST address recs: a workspace of `ws` bytes (a multiple of 64) and the records from the
@@ -92,11 +90,11 @@ static ec_status launch_gather(const void* zones, const void* table, size_t n, i
     return dst_mask ? launch(std::true_type{}) : launch(std::false_type{});
 }
 
-// The body of ec_zonal_broadcast and ec_zonal_lookup: `why` is the family's refusal of the call, K its kernels.
+// The body of ec_zonal_broadcast and ec_zonal_lookup: `r` is the family's refusal of the call, K its kernels.
 template <typename K>
-static ec_status zonal_gather_call(const char* who, const char* why, bool bad_type, ec_dtype zt, const void* zones, size_t n, int32_t n_zones, ec_dtype t,
-                              const void* table_dev, void* dst, uint8_t* dst_mask, ec_stream stream) {
-    ec_status st = zonal_refused(who, why, bad_type, t, zt, n, n_zones);
+static ec_status zonal_gather_call(const char* who, const ecv::Refusal& r, ec_dtype zt, const void* zones, size_t n, int32_t n_zones, ec_dtype t,
+                                   const void* table_dev, void* dst, uint8_t* dst_mask, ec_stream stream) {
+    ec_status st = zonal_refused(who, r, t, zt, n, n_zones);
     if (st != EC_OK || n == 0) return st;
     if ((st = ensure_ready()) != EC_OK) return st;
     return ecl::with_cell_width(ecl::size_of(t), [&](auto w) {

@@ -2,15 +2,16 @@
 // ec_zonal_broadcast) share, in plain C++: the launch constants, the refusals and their order, the size of the caller's
 // workspace and the layout of a workgroup's tables in LDS.
 //
-// Self-contained: no HIP include and nothing from this library but ec_reduce_plan.hpp (kMaxReduceBlocks), so that
-// host/test_zonal_plan.cpp runs these very functions under the address and undefined-behaviour sanitizers.  The functions the
-// kernels call are constexpr: hipcc compiles a constexpr function for both sides.
+// Self-contained: no HIP include and nothing from this library but ec_reduce_plan.hpp (kMaxReduceBlocks) and ec_refusal.hpp, so
+// that host/test_zonal_plan.cpp runs these very functions under the address and undefined-behaviour sanitizers.  The functions
+// the kernels call are constexpr: hipcc compiles a constexpr function for both sides.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
 
 #include "ec_reduce_plan.hpp"
+#include "ec_refusal.hpp"
 
 namespace ecz {
 
@@ -73,57 +74,39 @@ constexpr LdsLayout lds_layout(int32_t n_zones, int kind) {
     return l;
 }
 
-inline bool overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
-    if (!a || !b || abytes == 0 || bbytes == 0) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + bbytes && y < x + abytes;
-}
-
 constexpr bool valid_zone_type(int zt) { return zt == 0 /* EC_U8 */ || zt == 1 /* EC_U16 */ || zt == 6 /* EC_I32 */; }
 constexpr size_t zone_size(int zt) { return zt == 0 ? 1 : zt == 1 ? 2 : zt == 6 ? 4 : 0; }
 
 // The head of all four refusals of the two zonal families (this header, ec_zonal_table_plan.hpp), in the header's order: n_zones
-// against the family's cap (`zones_ok`, the cap's text passed in), the two types (*bad_type set: EC_ERR_UNSUPPORTED_TYPE, every
-// other refusal is EC_ERR_ARG), a null pointer (`null_pointer`: the caller's own test, it knows which pointers the call needs).
-// cell_size: bytes of a value cell, 0 for a bad t.
-inline const char* refusal_head(bool zones_ok, const char* cap_text, size_t cell_size, int zt, bool null_pointer, bool* bad_type) {
-    *bad_type = false;
-    if (!zones_ok) return cap_text;
-    if (cell_size == 0) { *bad_type = true; return "bad dtype"; }
-    if (!valid_zone_type(zt)) { *bad_type = true; return "the zone raster's type is not EC_U8, EC_U16 or EC_I32"; }
-    return null_pointer ? "null pointer" : nullptr;
+// against the family's cap (`zones_ok`, the cap's text passed in), the two types, a null pointer (`null_pointer`: the caller's own
+// test, it knows which pointers the call needs).  cell_size: bytes of a value cell, 0 for a bad t.
+inline ecv::Refusal refusal_head(bool zones_ok, const char* cap_text, size_t cell_size, int zt, bool null_pointer) {
+    if (!zones_ok) return {cap_text};
+    if (cell_size == 0) return {"bad dtype", true};
+    if (!valid_zone_type(zt)) return {"the zone raster's type is not EC_U8, EC_U16 or EC_I32", true};
+    if (null_pointer) return {"null pointer"};
+    return {};
 }
 
-// Their tail: two outputs a and b against each of the nin inputs, then against each other.  text: a on an input, b on an input,
-// a on b.
-inline const char* overlap_refusal(const void* a, size_t abytes, const void* b, size_t bbytes, const void* const* in, const size_t* in_bytes, int nin,
-                                   const char* const text[3]) {
-    for (int k = 0; k < nin; ++k) {
-        if (overlap(a, abytes, in[k], in_bytes[k])) return text[0];
-        if (overlap(b, bbytes, in[k], in_bytes[k])) return text[1];
-    }
-    return overlap(a, abytes, b, bbytes) ? text[2] : nullptr;
+// The tail of a statistics call: the records and the workspace against the values, the mask and the zone ids, then each other.
+inline ecv::Refusal stats_overlap_refusal(const void* out, size_t out_bytes, const void* workspace, size_t ws, const void* p, const void* mask,
+                                          const void* zones, size_t n, size_t cell_size, int zt) {
+    const ecv::Span rec{out, out_bytes}, work{workspace, ws}, values{p, n * cell_size}, valid{mask, n}, ids{zones, n * zone_size(zt)};
+    const ecv::OverlapRow rows[] = {{rec, values, "the records overlap an input"},  {work, values, "the workspace overlaps an input"},
+                                    {rec, valid, "the records overlap an input"},   {work, valid, "the workspace overlaps an input"},
+                                    {rec, ids, "the records overlap an input"},     {work, ids, "the workspace overlaps an input"},
+                                    {rec, work, "the records overlap the workspace"}};
+    return {ecv::first_overlap(rows)};
 }
 
-// The tail of a statistics call: the records and the workspace against the values, the mask and the zone ids.
-inline const char* stats_overlap_refusal(const void* out, size_t out_bytes, const void* workspace, size_t ws, const void* p, const void* mask,
-                                         const void* zones, size_t n, size_t cell_size, int zt) {
-    const void* in[3] = {p, mask, zones};
-    const size_t in_bytes[3] = {n * cell_size, n, n * zone_size(zt)};
-    const char* const text[3] = {"the records overlap an input", "the workspace overlaps an input", "the records overlap the workspace"};
-    return overlap_refusal(out, out_bytes, workspace, ws, in, in_bytes, 3, text);
-}
-
-// Why ec_zonal_stats_device refuses a call, or null.  The order is the header's: refusal_head, n above the bound of one exact
+// Why ec_zonal_stats_device refuses a call, or nothing.  The order is the header's: refusal_head, n above the bound of one exact
 // record (max_cells, 0 = none: stats_max_cells), an output overlapping an input.  caller_workspace false (the forms that take
 // their workspace from the library's pool): `workspace` is not looked at, and `out` is host memory (out_bytes 0).
-inline const char* stats_refusal(int32_t n_zones, size_t cell_size, int zt, const void* p, const void* mask, const void* zones, size_t n,
-                                 uint64_t max_cells, const void* out, size_t out_bytes, const void* workspace, bool caller_workspace,
-                                 bool* bad_type) {
+inline ecv::Refusal stats_refusal(int32_t n_zones, size_t cell_size, int zt, const void* p, const void* mask, const void* zones, size_t n,
+                                  uint64_t max_cells, const void* out, size_t out_bytes, const void* workspace, bool caller_workspace) {
     const bool null_pointer = !out || (caller_workspace && !workspace) || (n > 0 && (!p || !zones));
-    if (const char* why = refusal_head(valid_zones(n_zones), "n_zones is not within 1 .. EC_ZONAL_MAX_ZONES (256)", cell_size, zt, null_pointer, bad_type))
-        return why;
-    if (max_cells && n > max_cells) return "more cells than one exact record covers: shard it (ec_stats_fold merges the records)";
+    if (const ecv::Refusal r = refusal_head(valid_zones(n_zones), "n_zones is not within 1 .. EC_ZONAL_MAX_ZONES (256)", cell_size, zt, null_pointer)) return r;
+    if (max_cells && n > max_cells) return {"more cells than one exact record covers: shard it (ec_stats_fold merges the records)"};
     return stats_overlap_refusal(out, out_bytes, workspace, caller_workspace ? workspace_bytes(n_zones) : 0, p, mask, zones, n, cell_size, zt);
 }
 
@@ -135,22 +118,22 @@ constexpr uint64_t broadcast_tiles(uint64_t n, size_t cpl) {
     return (n / cpl + uint64_t(kBlock) * kBroadcastU - 1) / (uint64_t(kBlock) * kBroadcastU);
 }
 
-// Why a gather (ec_zonal_broadcast, ec_zonal_lookup) refuses a call, or null; same order.  n == 0 passes whatever the pointers are.
-inline const char* gather_refusal(bool zones_ok, const char* cap_text, int32_t n_zones, size_t cell_size, int zt, const void* zones,
-                                  const void* table, size_t n, const void* dst, const void* dst_mask, bool* bad_type) {
-    if (const char* why = refusal_head(zones_ok, cap_text, cell_size, zt, n > 0 && (!zones || !table || !dst), bad_type)) return why;
-    if (n == 0) return nullptr;
-    if (broadcast_tiles(n, broadcast_cpl(cell_size, zone_size(zt))) > kMaxTiles) return "more than 2^31 - 1 tiles";
-    const void* in[2] = {zones, table};
-    const size_t in_bytes[2] = {n * zone_size(zt), size_t(n_zones) * cell_size};
-    const char* const text[3] = {"dst overlaps an input (the operation is not in-place)", "dst_mask overlaps an input", "dst_mask overlaps dst"};
-    return overlap_refusal(dst, n * cell_size, dst_mask, n, in, in_bytes, 2, text);
+// Why a gather (ec_zonal_broadcast, ec_zonal_lookup) refuses a call, or nothing; same order.  n == 0 passes whatever the pointers are.
+inline ecv::Refusal gather_refusal(bool zones_ok, const char* cap_text, int32_t n_zones, size_t cell_size, int zt, const void* zones, const void* table,
+                                   size_t n, const void* dst, const void* dst_mask) {
+    if (const ecv::Refusal r = refusal_head(zones_ok, cap_text, cell_size, zt, n > 0 && (!zones || !table || !dst))) return r;
+    if (n == 0) return {};
+    if (broadcast_tiles(n, broadcast_cpl(cell_size, zone_size(zt))) > kMaxTiles) return {"more than 2^31 - 1 tiles"};
+    const ecv::Span out{dst, n * cell_size}, out_mask{dst_mask, n}, ids{zones, n * zone_size(zt)}, tab{table, size_t(n_zones) * cell_size};
+    const ecv::OverlapRow rows[] = {{out, ids, "dst overlaps an input (the operation is not in-place)"}, {out_mask, ids, "dst_mask overlaps an input"},
+                                    {out, tab, "dst overlaps an input (the operation is not in-place)"}, {out_mask, tab, "dst_mask overlaps an input"},
+                                    {out, out_mask, "dst_mask overlaps dst"}};
+    return {ecv::first_overlap(rows)};
 }
 
-inline const char* broadcast_refusal(int32_t n_zones, size_t cell_size, int zt, const void* zones, const void* table, size_t n, const void* dst,
-                                     const void* dst_mask, bool* bad_type) {
-    return gather_refusal(valid_zones(n_zones), "n_zones is not within 1 .. EC_ZONAL_MAX_ZONES (256)", n_zones, cell_size, zt, zones, table, n, dst,
-                          dst_mask, bad_type);
+inline ecv::Refusal broadcast_refusal(int32_t n_zones, size_t cell_size, int zt, const void* zones, const void* table, size_t n, const void* dst,
+                                      const void* dst_mask) {
+    return gather_refusal(valid_zones(n_zones), "n_zones is not within 1 .. EC_ZONAL_MAX_ZONES (256)", n_zones, cell_size, zt, zones, table, n, dst, dst_mask);
 }
 
 }  // namespace ecz

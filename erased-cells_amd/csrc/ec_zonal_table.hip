@@ -70,10 +70,8 @@ static uint64_t table_max_cells(ec_dtype t) { return stats_kind(t) == 0 ? stats_
 // What ec_zonal_table_device refuses before any device work (the order: ec_zonal_table_plan.hpp table_refusal).
 static ec_status check_table_args(const char* who, ec_dtype t, const void* p, const uint8_t* mask, ec_dtype zt, const void* zones, size_t n, int32_t n_zones,
                                   const void* out, const void* workspace, bool caller_workspace) {
-    bool bad_type = false;
-    const char* why = ezt::table_refusal(n_zones, ecl::size_of(t), stats_kind(t), zt, p, mask, zones, n, table_max_cells(t), out, workspace, caller_workspace,
-                                         &bad_type);
-    return zonal_refused(who, why, bad_type, t, zt, n, n_zones);
+    const ecv::Refusal r = ezt::table_refusal(n_zones, ecl::size_of(t), stats_kind(t), zt, p, mask, zones, n, table_max_cells(t), out, workspace, caller_workspace);
+    return zonal_refused(who, r, t, zt, n, n_zones);
 }
 
 // The n_zones records of one call at HOST address recs (records_host).  Arguments checked by the caller.
@@ -126,7 +124,6 @@ extern "C" ec_status ec_zonal_table_compute(ec_dtype t, const void* p, const uin
 
 extern "C" ec_status ec_zonal_lookup(ec_dtype zt, const void* zones, size_t n, int32_t n_zones, ec_dtype t, const void* table_dev, void* dst,
                                      uint8_t* dst_mask_or_null, ec_stream stream) {
-    bool bad_type = false;
-    const char* why = ezt::lookup_refusal(n_zones, ecl::size_of(t), zt, zones, table_dev, n, dst, dst_mask_or_null, &bad_type);
-    return zonal_gather_call<LookupKernels>("ec_zonal_lookup", why, bad_type, zt, zones, n, n_zones, t, table_dev, dst, dst_mask_or_null, stream);
+    const ecv::Refusal r = ezt::lookup_refusal(n_zones, ecl::size_of(t), zt, zones, table_dev, n, dst, dst_mask_or_null);
+    return zonal_gather_call<LookupKernels>("ec_zonal_lookup", r, zt, zones, n, n_zones, t, table_dev, dst, dst_mask_or_null, stream);
 }

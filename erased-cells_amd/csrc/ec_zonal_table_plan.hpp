@@ -43,31 +43,29 @@ constexpr size_t workspace_bytes(int kind, int32_t n_zones) {
     return valid_zones(n_zones) && (kind == 0 || kind == 1) ? size_t(n_zones) * size_t(words(kind)) * 8u : 0;
 }
 
-inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
-// Why ec_zonal_table_device refuses a call, or null; ec_zonal_stats_device's order and shared pieces (ecz::stats_refusal) with this
-// family's cap, the kind's bound on n (max_cells) and the alignment of the records and the workspace before their overlaps.
+// Why ec_zonal_table_device refuses a call, or nothing; ec_zonal_stats_device's order and shared pieces (ecz::stats_refusal) with
+// this family's cap, the kind's bound on n (max_cells) and the alignment of the records and the workspace before their overlaps.
 // caller_workspace false (the forms that take workspace and records from the library's pool): `workspace` is not looked at and
 // `out` is host memory of any alignment.
-inline const char* table_refusal(int32_t n_zones, size_t cell_size, int kind, int zt, const void* p, const void* mask, const void* zones, size_t n,
-                                 uint64_t max_cells, const void* out, const void* workspace, bool caller_workspace, bool* bad_type) {
+inline ecv::Refusal table_refusal(int32_t n_zones, size_t cell_size, int kind, int zt, const void* p, const void* mask, const void* zones, size_t n,
+                                  uint64_t max_cells, const void* out, const void* workspace, bool caller_workspace) {
     const bool null_pointer = !out || (caller_workspace && !workspace) || (n > 0 && (!p || !zones));
-    if (const char* why = ecz::refusal_head(valid_zones(n_zones), "n_zones is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES (16777216)", cell_size, zt,
-                                            null_pointer, bad_type))
-        return why;
-    if (n > max_cells) return kind == 0 ? "more cells than one exact record covers: shard it (ec_stats_fold merges the records)"
-                                         : "more than 2^32 cells: the truncated sums are bounded for 2^32 (shard it)";
-    if (!caller_workspace) return nullptr;
-    if (!aligned16(out)) return "the records are not 16-byte aligned";
-    if (!aligned16(workspace)) return "the workspace is not 16-byte aligned";
+    if (const ecv::Refusal r = ecz::refusal_head(valid_zones(n_zones), "n_zones is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES (16777216)", cell_size, zt,
+                                                 null_pointer))
+        return r;
+    if (n > max_cells) return {kind == 0 ? "more cells than one exact record covers: shard it (ec_stats_fold merges the records)"
+                                          : "more than 2^32 cells: the truncated sums are bounded for 2^32 (shard it)"};
+    if (!caller_workspace) return {};
+    if (ecv::misaligned(out, 16)) return {"the records are not 16-byte aligned"};
+    if (ecv::misaligned(workspace, 16)) return {"the workspace is not 16-byte aligned"};
     return ecz::stats_overlap_refusal(out, size_t(n_zones) * ecz::kRecordBytes, workspace, workspace_bytes(kind, n_zones), p, mask, zones, n, cell_size, zt);
 }
 
-// Why ec_zonal_lookup refuses a call, or null: ecz::broadcast_refusal with this family's cap.
-inline const char* lookup_refusal(int32_t n_zones, size_t cell_size, int zt, const void* zones, const void* table, size_t n, const void* dst,
-                                  const void* dst_mask, bool* bad_type) {
+// Why ec_zonal_lookup refuses a call, or nothing: ecz::broadcast_refusal with this family's cap.
+inline ecv::Refusal lookup_refusal(int32_t n_zones, size_t cell_size, int zt, const void* zones, const void* table, size_t n, const void* dst,
+                                   const void* dst_mask) {
     return ecz::gather_refusal(valid_zones(n_zones), "n_zones is not within 1 .. EC_ZONAL_TABLE_MAX_ZONES (16777216)", n_zones, cell_size, zt, zones,
-                               table, n, dst, dst_mask, bad_type);
+                               table, n, dst, dst_mask);
 }
 
 }  // namespace ezt

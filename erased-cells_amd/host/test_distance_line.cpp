@@ -1,11 +1,13 @@
 // test_distance_line.cpp — csrc/ec_distance_line.hpp alone, under a plain C++ compiler: the column sweeps and the row scans that the
 // kernels of ec_distance run, against brute force (the minimum over all targets, in integers) over EVERY mask of every shape up to
 // 4 x 4 and random masks up to 40 x 40.  The rows are scanned the way the kernel scans them: in pieces of a tile's width, with the
-// stacks of several rows interleaved in one block, and g read through a stride.  Also the workspace's layout.  Built plainly and
-// with -fsanitize=address,undefined (every stack and g plane is an exactly sized heap block, so a step outside one is reported).
+// stacks of several rows interleaved in one block, and g read through a stride.  Also the workspace's layout, and ec_distance's
+// refusals in the order include/erased_cells.h states.  Built plainly and with -fsanitize=address,undefined (every stack and g plane
+// is an exactly sized heap block, so a step outside one is reported).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <string_view>
 #include <vector>
 
 #include "ec_distance_line.hpp"
@@ -83,7 +85,65 @@ static void one(const std::vector<uint8_t>& m, uint32_t cols, uint32_t rows) {
     }
 }
 
+// ec_distance's refusals.  Addresses are plain integers, never dereferenced.
+static const void* at(uint64_t a) { return reinterpret_cast<const void*>(uintptr_t(a)); }
+static bool says(const ecv::Refusal& r, const char* text, bool bad_type = false) {
+    return r.why && std::string_view(r.why) == text && r.bad_type == bad_type;
+}
+
+static void refusals() {
+    const uint64_t M = 0x10000, D = 0x20000, E = D + 400, FAR = uint64_t(1) << 40, W = dist_workspace_bytes(10, 10);  // 10 x 10 cells of 4 bytes
+    const void* far = at(FAR);
+    CHECK(W > 0 && W % 16 == 0);
+    CHECK(!distance_refusal(at(M), 10, 10, true, 4, at(D), at(E), far) && !distance_refusal(at(M), 10, 10, true, 8, at(D), nullptr, nullptr));
+    CHECK(!distance_refusal(at(M), 10, 10, true, 4, nullptr, at(E), nullptr));
+    // the order: each call is wrong in everything that comes later as well
+    CHECK(says(distance_refusal(nullptr, 0, 10, false, 0, nullptr, nullptr, nullptr), "cols and rows must be within 1 .. EC_DISTANCE_MAX_SIDE"));
+    CHECK(says(distance_refusal(nullptr, 10, 0, false, 0, nullptr, nullptr, nullptr), "cols and rows must be within 1 .. EC_DISTANCE_MAX_SIDE"));
+    CHECK(says(distance_refusal(nullptr, 10, 10, false, 0, nullptr, nullptr, nullptr), "bad out_type", true));
+    CHECK(says(distance_refusal(nullptr, 10, 10, true, 0, nullptr, nullptr, nullptr), "out_type is neither EC_U32 nor EC_F64"));
+    CHECK(says(distance_refusal(nullptr, 10, 10, true, 4, nullptr, nullptr, nullptr), "null mask"));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, nullptr, nullptr, at(M)), "dst and dst_mask are both NULL"));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(M + 2), at(M), at(M)), "dst is not aligned to its cell type"));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 8, at(M + 4), at(M), at(M)), "dst is not aligned to its cell type"));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(M), at(M), at(M)), "dst overlaps the mask"));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(D), at(M), at(M)), "dst_mask overlaps the mask"));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(D), at(D), at(M)), "the workspace overlaps the mask"));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(D), at(D), at(D)), "dst_mask overlaps dst"));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(D), at(E), at(E - 1)), "the workspace overlaps dst"));  // its second byte on dst_mask
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(D), at(E), at(E + 99)), "the workspace overlaps dst_mask"));
+    // each overlap by one byte, and the same two blocks touching
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(M + 96), nullptr, far), "dst overlaps the mask") &&
+          !distance_refusal(at(M), 10, 10, true, 4, at(M + 100), nullptr, far));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(M - 396), nullptr, far), "dst overlaps the mask") &&
+          !distance_refusal(at(M), 10, 10, true, 4, at(M - 400), nullptr, far));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(D), at(M + 99), far), "dst_mask overlaps the mask") &&
+          !distance_refusal(at(M), 10, 10, true, 4, at(D), at(M + 100), far));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(D), at(E), at(M - W + 1)), "the workspace overlaps the mask") &&
+          !distance_refusal(at(M), 10, 10, true, 4, at(D), at(E), at(M - W)));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(D), at(E - 1), far), "dst_mask overlaps dst") &&
+          !distance_refusal(at(M), 10, 10, true, 4, at(D), at(E), far));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(D), nullptr, at(D + 399)), "the workspace overlaps dst") &&
+          !distance_refusal(at(M), 10, 10, true, 4, at(D), nullptr, at(D + 400)));
+    CHECK(says(distance_refusal(at(M), 10, 10, true, 4, at(D), at(E), at(E - W + 1)), "the workspace overlaps dst") &&  // ends on dst's last byte
+          says(distance_refusal(at(M), 10, 10, true, 4, nullptr, at(E), at(E - W + 1)), "the workspace overlaps dst_mask") &&
+          !distance_refusal(at(M), 10, 10, true, 4, nullptr, at(E), at(E - W)) && !distance_refusal(at(M), 10, 10, true, 4, nullptr, at(E), at(E + 100)));
+    // the largest shape, and one past it: 2^30 cells, every product in 64 bits
+    const uint64_t S = kDistMaxSide, N = S * S, WS = dist_workspace_bytes(S, S);
+    CHECK(WS >= 6 * N && WS > (uint64_t(1) << 32));
+    CHECK(!distance_refusal(far, S, S, true, 8, at(FAR + N), at(FAR + 9 * N), at(FAR + 10 * N)));
+    CHECK(says(distance_refusal(far, S, S, true, 8, at(FAR + N - 8), nullptr, nullptr), "dst overlaps the mask"));
+    CHECK(says(distance_refusal(far, S, S, true, 8, at(FAR + N), at(FAR + 9 * N - 1), nullptr), "dst_mask overlaps dst"));
+    CHECK(says(distance_refusal(far, S, S, true, 8, at(FAR + N), at(FAR + 9 * N), at(FAR - WS + 1)), "the workspace overlaps the mask") &&
+          !distance_refusal(far, S, S, true, 8, at(FAR + N), at(FAR + 9 * N), at(FAR - WS)));
+    CHECK(says(distance_refusal(far, S, S, true, 8, at(FAR + N), at(FAR + 9 * N), at(FAR + 10 * N - 1)), "the workspace overlaps dst_mask"));
+    CHECK(says(distance_refusal(far, S + 1, S, true, 8, far, far, far), "cols and rows must be within 1 .. EC_DISTANCE_MAX_SIDE") &&
+          says(distance_refusal(far, S, S + 1, true, 8, far, far, far), "cols and rows must be within 1 .. EC_DISTANCE_MAX_SIDE") &&
+          says(distance_refusal(far, 1, uint64_t(1) << 63, true, 8, far, far, far), "cols and rows must be within 1 .. EC_DISTANCE_MAX_SIDE"));
+}
+
 int main() {
+    refusals();
     // every mask of every shape up to 4 x 4
     for (uint32_t rows = 1; rows <= 4; ++rows)
         for (uint32_t cols = 1; cols <= 4; ++cols) {

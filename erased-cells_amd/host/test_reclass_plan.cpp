@@ -1,4 +1,4 @@
-// test_reclass_plan.cpp — csrc/ec_reclass_plan.hpp alone, under a plain C++17 compiler (and, as test_reclass_plan_san, under the
+// test_reclass_plan.cpp — csrc/ec_reclass_plan.hpp and csrc/ec_reclass_checks.hpp alone, under a plain C++17 compiler (and, as test_reclass_plan_san, under the
 // address and undefined-behaviour sanitizers): the thresholds against the union-order predicate itself for EVERY cell of the 1-
 // and 2-byte types and for planted cells of the wider ones, the key ranges, unreachable suffixes, the refusals in the order
 // include/erased_cells.h states, that a refused build writes nothing and a build defines every byte, and the kernels'
@@ -10,7 +10,7 @@
 #include <limits>
 #include <vector>
 
-#include "ec_reclass_plan.hpp"
+#include "ec_reclass_checks.hpp"
 
 static int g_checks = 0;
 #define CHECK(cond)                                                                    \
@@ -23,6 +23,12 @@ static int g_checks = 0;
     } while (0)
 
 using namespace ecr;
+
+// a refusal as these checks read it: its text (null: none), the type flag left in *bad
+static const char* told(const ecv::Refusal& r, bool* bad) {
+    *bad = r.bad_type;
+    return r.why;
+}
 
 static uint64_t g_rng = 0x9E3779B97F4A7C15ull;
 static uint64_t rnd() {
@@ -92,7 +98,7 @@ static void exhaustive() {
                 for (size_t c = 0; c <= b.size(); ++c) vals.push_back(value_of<uint8_t>(EC_U8, uint8_t(c)));
                 ec_reclass_table tab;
                 bool bad = false;
-                const char* why = build(t, bt, b.data(), int32_t(b.size()), right, EC_U8, vals.data(), nullptr, nullptr, &tab, &bad);
+                const char* why = told(build(t, bt, b.data(), int32_t(b.size()), right, EC_U8, vals.data(), nullptr, nullptr, &tab), &bad);
                 CHECK(why == nullptr && !bad);
                 CHECK(tab.n_reached >= 0 && tab.n_reached <= tab.n_breaks && tab.n_breaks == int32_t(b.size()));
                 for (int32_t j = 1; j < tab.n_reached; ++j) CHECK(tab.thr[j - 1] <= tab.thr[j]);
@@ -121,7 +127,7 @@ static void planted(const std::vector<BT>& b) {
     for (int right = 0; right < 2; ++right) {
         ec_reclass_table tab;
         bool bad = false;
-        CHECK(build(t, bt, b.data(), int32_t(b.size()), right, EC_U8, vals.data(), nullptr, nullptr, &tab, &bad) == nullptr);
+        CHECK(told(build(t, bt, b.data(), int32_t(b.size()), right, EC_U8, vals.data(), nullptr, nullptr, &tab), &bad) == nullptr);
         std::vector<int64_t> keys = {key_min<T>(), key_min<T>() + 1, key_max<T>() - 1, key_max<T>(), 0, -1, 1};
         for (int32_t j = 0; j < tab.n_reached; ++j)
             for (int64_t d = -2; d <= 2; ++d) {
@@ -191,13 +197,13 @@ int main() {
         for (int c = 0; c < 6; ++c) vals[c] = value_of<uint8_t>(EC_U8, uint8_t(10 + c));
         ec_reclass_table tab;
         bool bad = false;
-        CHECK(build(EC_U8, EC_F64, b, 5, 0, EC_U8, vals, nullptr, nullptr, &tab, &bad) == nullptr);
+        CHECK(told(build(EC_U8, EC_F64, b, 5, 0, EC_U8, vals, nullptr, nullptr, &tab), &bad) == nullptr);
         CHECK(tab.n_reached == 4 && tab.thr[0] == 0 && tab.thr[1] == 1 && tab.thr[2] == 1 && tab.thr[3] == 255);
         CHECK(class_of(tab, 0) == 1 && class_of(tab, 1) == 3 && class_of(tab, 254) == 3 && class_of(tab, 255) == 4);
-        CHECK(build(EC_U8, EC_F64, b, 5, 1, EC_U8, vals, nullptr, nullptr, &tab, &bad) == nullptr);
+        CHECK(told(build(EC_U8, EC_F64, b, 5, 1, EC_U8, vals, nullptr, nullptr, &tab), &bad) == nullptr);
         CHECK(tab.n_reached == 3 && tab.thr[0] == 0 && tab.thr[1] == 1 && tab.thr[2] == 1);  // no u8 cell is > 255.0
         const double far[2] = {1e9, 2e9};
-        CHECK(build(EC_U8, EC_F64, far, 2, 0, EC_U8, vals, nullptr, nullptr, &tab, &bad) == nullptr);
+        CHECK(told(build(EC_U8, EC_F64, far, 2, 0, EC_U8, vals, nullptr, nullptr, &tab), &bad) == nullptr);
         CHECK(tab.n_reached == 0 && tab.n_breaks == 2);
     }
     // the refusals, in order; a refused build writes nothing
@@ -221,28 +227,28 @@ int main() {
             return why;
         };
         // everything wrong at once: n_breaks speaks first
-        CHECK(std::strstr(refused(build(99, 99, nullptr, 0, 7, 99, nullptr, nullptr, nullptr, out, &bad), false), "n_breaks"));
-        CHECK(std::strstr(refused(build(99, 99, nullptr, 256, 7, 99, nullptr, nullptr, nullptr, out, &bad), false), "n_breaks"));
-        CHECK(std::strstr(refused(build(99, 99, nullptr, 3, 7, 99, nullptr, nullptr, nullptr, out, &bad), false), "right"));
-        CHECK(std::strstr(refused(build(99, EC_F64, nullptr, 3, 0, EC_U16, nullptr, nullptr, nullptr, out, &bad), true), "dtype"));
-        CHECK(std::strstr(refused(build(EC_F32, 10, nullptr, 3, 0, EC_U16, nullptr, nullptr, nullptr, out, &bad), true), "dtype"));
-        CHECK(std::strstr(refused(build(EC_F32, EC_F64, nullptr, 3, 0, 200, nullptr, nullptr, nullptr, out, &bad), true), "dtype"));
-        CHECK(std::strstr(refused(build(EC_F32, EC_F64, nullptr, 3, 0, EC_U16, bad_vals, nullptr, &bad_nd, out, &bad), false), "null"));
-        CHECK(std::strstr(refused(build(EC_F32, EC_F64, nan_b, 3, 0, EC_U16, nullptr, nullptr, &bad_nd, out, &bad), false), "null"));
-        CHECK(std::strstr(build(EC_F32, EC_F64, nan_b, 3, 0, EC_U16, bad_vals, nullptr, &bad_nd, nullptr, &bad), "null"));
-        CHECK(std::strstr(refused(build(EC_F32, EC_F64, nan_b, 3, 0, EC_U16, bad_vals, nullptr, &bad_nd, out, &bad), false), "class value"));
-        CHECK(std::strstr(refused(build(EC_F32, EC_F64, nan_b, 3, 0, EC_U16, vals, nullptr, &bad_nd, out, &bad), false), "nodata"));
-        CHECK(std::strstr(refused(build(EC_F32, EC_F64, nan_b, 3, 0, EC_U16, vals, nullptr, &nd, out, &bad), false), "NaN"));
-        CHECK(std::strstr(refused(build(EC_F32, EC_F64, flat, 3, 0, EC_U16, vals, nullptr, &nd, out, &bad), false), "ascending"));
-        CHECK(std::strstr(refused(build(EC_F32, EC_I64, same_in_f64, 2, 0, EC_U16, vals, nullptr, &nd, out, &bad), false), "ascending"));
-        CHECK(build(EC_I64, EC_I64, same_in_f64, 2, 0, EC_U16, vals, nullptr, &nd, out, &bad) == nullptr);  // exact in Int64
+        CHECK(std::strstr(refused(told(build(99, 99, nullptr, 0, 7, 99, nullptr, nullptr, nullptr, out), &bad), false), "n_breaks"));
+        CHECK(std::strstr(refused(told(build(99, 99, nullptr, 256, 7, 99, nullptr, nullptr, nullptr, out), &bad), false), "n_breaks"));
+        CHECK(std::strstr(refused(told(build(99, 99, nullptr, 3, 7, 99, nullptr, nullptr, nullptr, out), &bad), false), "right"));
+        CHECK(std::strstr(refused(told(build(99, EC_F64, nullptr, 3, 0, EC_U16, nullptr, nullptr, nullptr, out), &bad), true), "dtype"));
+        CHECK(std::strstr(refused(told(build(EC_F32, 10, nullptr, 3, 0, EC_U16, nullptr, nullptr, nullptr, out), &bad), true), "dtype"));
+        CHECK(std::strstr(refused(told(build(EC_F32, EC_F64, nullptr, 3, 0, 200, nullptr, nullptr, nullptr, out), &bad), true), "dtype"));
+        CHECK(std::strstr(refused(told(build(EC_F32, EC_F64, nullptr, 3, 0, EC_U16, bad_vals, nullptr, &bad_nd, out), &bad), false), "null"));
+        CHECK(std::strstr(refused(told(build(EC_F32, EC_F64, nan_b, 3, 0, EC_U16, nullptr, nullptr, &bad_nd, out), &bad), false), "null"));
+        CHECK(std::strstr(told(build(EC_F32, EC_F64, nan_b, 3, 0, EC_U16, bad_vals, nullptr, &bad_nd, nullptr), &bad), "null"));
+        CHECK(std::strstr(refused(told(build(EC_F32, EC_F64, nan_b, 3, 0, EC_U16, bad_vals, nullptr, &bad_nd, out), &bad), false), "class value"));
+        CHECK(std::strstr(refused(told(build(EC_F32, EC_F64, nan_b, 3, 0, EC_U16, vals, nullptr, &bad_nd, out), &bad), false), "nodata"));
+        CHECK(std::strstr(refused(told(build(EC_F32, EC_F64, nan_b, 3, 0, EC_U16, vals, nullptr, &nd, out), &bad), false), "NaN"));
+        CHECK(std::strstr(refused(told(build(EC_F32, EC_F64, flat, 3, 0, EC_U16, vals, nullptr, &nd, out), &bad), false), "ascending"));
+        CHECK(std::strstr(refused(told(build(EC_F32, EC_I64, same_in_f64, 2, 0, EC_U16, vals, nullptr, &nd, out), &bad), false), "ascending"));
+        CHECK(told(build(EC_I64, EC_I64, same_in_f64, 2, 0, EC_U16, vals, nullptr, &nd, out), &bad) == nullptr);  // exact in Int64
         // every byte defined: two builds into differently poisoned memory agree
         unsigned char a[sizeof(ec_reclass_table)], c[sizeof(ec_reclass_table)];
         std::memset(a, 0x00, sizeof a);
         std::memset(c, 0xFF, sizeof c);
         const uint8_t valid[4] = {1, 0, 7, 1};
-        CHECK(build(EC_F32, EC_F64, b, 3, 1, EC_U16, vals, valid, &nd, reinterpret_cast<ec_reclass_table*>(a), &bad) == nullptr);
-        CHECK(build(EC_F32, EC_F64, b, 3, 1, EC_U16, vals, valid, &nd, reinterpret_cast<ec_reclass_table*>(c), &bad) == nullptr);
+        CHECK(told(build(EC_F32, EC_F64, b, 3, 1, EC_U16, vals, valid, &nd, reinterpret_cast<ec_reclass_table*>(a)), &bad) == nullptr);
+        CHECK(told(build(EC_F32, EC_F64, b, 3, 1, EC_U16, vals, valid, &nd, reinterpret_cast<ec_reclass_table*>(c)), &bad) == nullptr);
         CHECK(std::memcmp(a, c, sizeof a) == 0);
         ec_reclass_table tab;
         std::memcpy(&tab, a, sizeof tab);
@@ -250,28 +256,28 @@ int main() {
         CHECK(tab.nodata_bits == 65535 && tab.reserved0 == 0 && tab.reserved1 == 0);
         CHECK(tab.valid[0] == 1 && tab.valid[1] == 0 && tab.valid[2] == 1 && tab.valid[3] == 1 && tab.valid[4] == 0 && tab.valid[255] == 0);
         CHECK(tab.value_bits[3] == 3 && tab.value_bits[4] == 0);
-        CHECK(build(EC_F32, EC_F64, b, 3, 1, EC_U16, vals, nullptr, nullptr, &tab, &bad) == nullptr && tab.flags == 0 && tab.valid[3] == 1 && tab.valid[4] == 0);
+        CHECK(told(build(EC_F32, EC_F64, b, 3, 1, EC_U16, vals, nullptr, nullptr, &tab), &bad) == nullptr && tab.flags == 0 && tab.valid[3] == 1 && tab.valid[4] == 0);
     }
     // ec_reclass's refusals, in order
     {
         alignas(16) static unsigned char mem[8192 + EC_RECLASS_TABLE_BYTES];
         unsigned char* src = mem; unsigned char* dst = mem + 1024; unsigned char* dm = mem + 3072; unsigned char* tab = mem + 8192;
         bool bad = false;
-        CHECK(std::strstr(reclass_refusal(0, 1, nullptr, nullptr, 5, nullptr, nullptr, nullptr, &bad), "dtype") && bad);
-        CHECK(std::strstr(reclass_refusal(1, 0, nullptr, nullptr, 5, nullptr, nullptr, nullptr, &bad), "dtype") && bad);
-        CHECK(reclass_refusal(1, 2, nullptr, nullptr, 0, nullptr, nullptr, nullptr, &bad) == nullptr && !bad);
-        CHECK(std::strstr(reclass_refusal(1, 2, nullptr, nullptr, 5, tab + 1, dst, nullptr, &bad), "null") && !bad);
-        CHECK(std::strstr(reclass_refusal(1, 2, src, nullptr, 5, nullptr, dst, nullptr, &bad), "null"));
-        CHECK(std::strstr(reclass_refusal(1, 2, src, nullptr, 5, tab + 1, nullptr, nullptr, &bad), "null"));
-        CHECK(std::strstr(reclass_refusal(1, 2, src, nullptr, 5, tab + 8, src, nullptr, &bad), "16-byte"));
-        CHECK(std::strstr(reclass_refusal(8, 8, src, nullptr, size_t(1) << 42, tab, src, nullptr, &bad), "tiles"));
-        CHECK(std::strstr(reclass_refusal(1, 2, src, nullptr, 100, tab, src + 99, nullptr, &bad), "dst overlaps"));
-        CHECK(std::strstr(reclass_refusal(1, 2, src, dst + 199, 100, tab, dst, nullptr, &bad), "dst overlaps"));
-        CHECK(std::strstr(reclass_refusal(1, 2, src, nullptr, 100, dst + 16, dst, nullptr, &bad), "dst overlaps"));
-        CHECK(std::strstr(reclass_refusal(1, 2, src, nullptr, 100, tab, dst, src + 50, &bad), "dst_mask overlaps an input"));
-        CHECK(std::strstr(reclass_refusal(1, 2, src, nullptr, 100, tab, dst, tab + 4000, &bad), "dst_mask overlaps an input"));
-        CHECK(std::strstr(reclass_refusal(1, 2, src, nullptr, 100, tab, dst, dst + 199, &bad), "dst_mask overlaps dst"));
-        CHECK(reclass_refusal(1, 2, src, src + 100, 100, tab, dst, dm, &bad) == nullptr);
+        CHECK(std::strstr(told(reclass_refusal(0, 1, nullptr, nullptr, 5, nullptr, nullptr, nullptr), &bad), "dtype") && bad);
+        CHECK(std::strstr(told(reclass_refusal(1, 0, nullptr, nullptr, 5, nullptr, nullptr, nullptr), &bad), "dtype") && bad);
+        CHECK(told(reclass_refusal(1, 2, nullptr, nullptr, 0, nullptr, nullptr, nullptr), &bad) == nullptr && !bad);
+        CHECK(std::strstr(told(reclass_refusal(1, 2, nullptr, nullptr, 5, tab + 1, dst, nullptr), &bad), "null") && !bad);
+        CHECK(std::strstr(told(reclass_refusal(1, 2, src, nullptr, 5, nullptr, dst, nullptr), &bad), "null"));
+        CHECK(std::strstr(told(reclass_refusal(1, 2, src, nullptr, 5, tab + 1, nullptr, nullptr), &bad), "null"));
+        CHECK(std::strstr(told(reclass_refusal(1, 2, src, nullptr, 5, tab + 8, src, nullptr), &bad), "16-byte"));
+        CHECK(std::strstr(told(reclass_refusal(8, 8, src, nullptr, size_t(1) << 42, tab, src, nullptr), &bad), "tiles"));
+        CHECK(std::strstr(told(reclass_refusal(1, 2, src, nullptr, 100, tab, src + 99, nullptr), &bad), "dst overlaps"));
+        CHECK(std::strstr(told(reclass_refusal(1, 2, src, dst + 199, 100, tab, dst, nullptr), &bad), "dst overlaps"));
+        CHECK(std::strstr(told(reclass_refusal(1, 2, src, nullptr, 100, dst + 16, dst, nullptr), &bad), "dst overlaps"));
+        CHECK(std::strstr(told(reclass_refusal(1, 2, src, nullptr, 100, tab, dst, src + 50), &bad), "dst_mask overlaps an input"));
+        CHECK(std::strstr(told(reclass_refusal(1, 2, src, nullptr, 100, tab, dst, tab + 4000), &bad), "dst_mask overlaps an input"));
+        CHECK(std::strstr(told(reclass_refusal(1, 2, src, nullptr, 100, tab, dst, dst + 199), &bad), "dst_mask overlaps dst"));
+        CHECK(told(reclass_refusal(1, 2, src, src + 100, 100, tab, dst, dm), &bad) == nullptr);
     }
     std::printf("test_reclass_plan: %d checks passed\n", g_checks);
     return 0;

@@ -3,7 +3,8 @@
 // flood fill in raster order.
 //   (a) sequentially, on plain words: EVERY mask of every shape up to 4 x 4, and random class rasters up to 40 x 40 with masks, both
 //       connectivities, both numberings, several sieves and tile shapes.  Also with loads that are STALE on purpose — a load returns
-//       any value the word has held — which may cost rounds and must not cost an answer.  And the workspace's layout.
+//       any value the word has held — which may cost rounds and must not cost an answer.  And the workspace's layout, and ec_regions'
+//       refusals in the order include/erased_cells.h states.
 //   (b) the seam unions on std::atomic words from up to 16 std::threads in shuffled order: the same answers, and every loop's step
 //       count under the bound the header states.
 // Built plainly, with -fsanitize=address,undefined, and with -fsanitize=thread for (b).
@@ -294,10 +295,90 @@ static void layout() {
     CHECK(reg_tiles(1, kRegTileW) == 1 && reg_tiles(kRegTileW + 1, kRegTileW) == 2 && reg_scan_blocks(kRegScanCells + 1) == 2);
 }
 
+// ec_regions' refusals.  Addresses are plain integers, never dereferenced.
+static const void* at(uint64_t a) { return reinterpret_cast<const void*>(uintptr_t(a)); }
+static bool says(const ecv::Refusal& r, const char* text, bool bad_type = false) {
+    return r.why && std::string_view(r.why) == text && r.bad_type == bad_type;
+}
+
+static void refusals() {
+    // 10 x 10 cells of 2 bytes: src 200 bytes at S, src_mask 100 at V, dst 400 at D, dst_mask 100 at E, n_regions 8 at C, the workspace W at K
+    const uint64_t S = 0x10000, V = 0x11000, D = 0x20000, E = D + 400, C = 0x30000, K = 0x40000, FAR = uint64_t(1) << 40, W = reg_workspace_bytes(10, 10);
+    const void* far = at(FAR);
+    auto call = [](const void* src, const void* mask, const void* dst, const void* dm, const void* count, const void* ws) {
+        return regions_refusal(2, src, mask, 10, 10, 8, true, dst, dm, count, ws);
+    };
+    CHECK(W == 816);
+    CHECK(!call(at(S), at(V), at(D), at(E), at(C), at(K)) && !call(at(S), nullptr, at(D), nullptr, nullptr, nullptr));
+    CHECK(!call(at(S), at(V), nullptr, at(E), nullptr, nullptr) && !call(at(S), at(V), nullptr, nullptr, at(C), nullptr));
+    CHECK(!regions_refusal(0, nullptr, at(V), 10, 10, 4, true, at(D), at(E), at(C), at(K)));  // the mask form: no src, no cell type
+    // the order: each call is wrong in everything that comes later as well
+    const char* const side = "cols and rows must be within 1 .. EC_REGIONS_MAX_SIDE";
+    CHECK(says(regions_refusal(0, at(S + 1), nullptr, 0, 10, 5, false, nullptr, nullptr, nullptr, at(K + 1)), side));
+    CHECK(says(regions_refusal(0, at(S + 1), nullptr, 10, 0, 5, false, nullptr, nullptr, nullptr, at(K + 1)), side));
+    CHECK(says(regions_refusal(0, at(S + 1), nullptr, 10, 10, 5, false, nullptr, nullptr, nullptr, at(K + 1)), "bad cell type", true));
+    CHECK(says(regions_refusal(0, nullptr, nullptr, 10, 10, 5, false, nullptr, nullptr, nullptr, at(K + 1)), "connectivity is neither 4 nor 8"));
+    CHECK(says(regions_refusal(0, nullptr, nullptr, 10, 10, 6, false, nullptr, nullptr, nullptr, at(K + 1)), "connectivity is neither 4 nor 8"));
+    CHECK(says(regions_refusal(0, nullptr, nullptr, 10, 10, 4, false, nullptr, nullptr, nullptr, at(K + 1)), "numbering is neither EC_REGIONS_ROOT nor EC_REGIONS_DENSE"));
+    CHECK(says(regions_refusal(0, nullptr, nullptr, 10, 10, 8, false, nullptr, nullptr, nullptr, at(K + 1)), "numbering is neither EC_REGIONS_ROOT nor EC_REGIONS_DENSE"));
+    CHECK(says(call(nullptr, nullptr, nullptr, nullptr, nullptr, at(K + 1)), "src and src_mask are both NULL"));
+    CHECK(says(call(at(S + 1), nullptr, nullptr, nullptr, nullptr, at(K + 1)), "dst, dst_mask and n_regions are all NULL"));
+    CHECK(says(call(at(S + 1), nullptr, at(S + 2), at(S), at(S + 4), at(S + 8)), "src is not aligned to its cell type"));
+    CHECK(says(call(at(S), nullptr, at(S + 2), at(S), at(S + 4), at(S + 8)), "dst is not aligned to its cell type"));
+    CHECK(says(call(at(S), nullptr, at(S), at(S), at(S + 4), at(S + 8)), "n_regions is not aligned to 8 bytes"));
+    CHECK(says(call(at(S), nullptr, at(S), at(S), at(S), at(S + 8)), "the workspace is not aligned to 16 bytes"));
+    CHECK(says(call(at(S), at(S), at(S), at(S), at(S), at(S)), "dst overlaps src"));
+    CHECK(says(call(far, at(V), at(V), at(V), at(V), at(V)), "dst overlaps src_mask"));
+    CHECK(says(call(at(S), at(S), at(D), at(S), at(S), at(S)), "dst_mask overlaps src"));
+    CHECK(says(call(far, at(V), at(D), at(V), at(V), at(V)), "dst_mask overlaps src_mask"));
+    CHECK(says(call(at(S), at(S), at(D), at(D), at(S), at(S)), "n_regions overlaps src"));
+    CHECK(says(call(far, at(V), at(D), at(D), at(V), at(V)), "n_regions overlaps src_mask"));
+    CHECK(says(call(at(S), at(S), at(D), at(D), at(D), at(S)), "the workspace overlaps src"));
+    CHECK(says(call(far, at(V), at(D), at(D), at(D), at(V)), "the workspace overlaps src_mask"));
+    CHECK(says(call(at(S), at(V), at(D), at(D), at(D), at(D)), "dst_mask overlaps dst"));
+    CHECK(says(call(at(S), at(V), at(D), at(E), at(D), at(D)), "n_regions overlaps dst"));
+    CHECK(says(call(at(S), at(V), at(D), at(E), at(E), at(E - 16)), "n_regions overlaps dst_mask"));  // the workspace on dst, dst_mask and n_regions
+    CHECK(says(call(at(S), at(V), at(D), at(E), at(C), at(E - 16)), "the workspace overlaps dst"));
+    CHECK(says(call(at(S), at(V), at(D), at(C), at(C), at(C)), "n_regions overlaps dst_mask"));
+    CHECK(says(call(at(S), at(V), at(D), at(C + 8), at(C), at(C)), "the workspace overlaps dst_mask"));
+    CHECK(says(call(at(S), at(V), at(D), at(E), at(C), at(C)), "the workspace overlaps n_regions"));
+    // each overlap by the least an aligned pointer allows, and the same two blocks touching
+    CHECK(says(call(at(S), at(V), at(S + 196), nullptr, nullptr, nullptr), "dst overlaps src") && !call(at(S), at(V), at(S + 200), nullptr, nullptr, nullptr));
+    CHECK(says(call(at(S), at(V), at(V + 96), nullptr, nullptr, nullptr), "dst overlaps src_mask") && !call(at(S), at(V), at(V + 100), nullptr, nullptr, nullptr));
+    CHECK(!call(at(S), nullptr, at(V + 96), nullptr, nullptr, nullptr));  // ... which is no input without a mask
+    CHECK(says(call(at(S), at(V), nullptr, at(S + 199), nullptr, nullptr), "dst_mask overlaps src") && !call(at(S), at(V), nullptr, at(S + 200), nullptr, nullptr));
+    CHECK(says(call(at(S), at(V), nullptr, at(V + 99), nullptr, nullptr), "dst_mask overlaps src_mask") && !call(at(S), at(V), nullptr, at(V + 100), nullptr, nullptr));
+    CHECK(says(call(at(S), at(V), nullptr, nullptr, at(S + 192), nullptr), "n_regions overlaps src") && !call(at(S), at(V), nullptr, nullptr, at(S + 200), nullptr));
+    CHECK(says(call(at(S), at(V), nullptr, nullptr, at(V), nullptr), "n_regions overlaps src_mask") && !call(at(S), at(V), nullptr, nullptr, at(V - 8), nullptr));
+    CHECK(says(call(at(S), at(V), at(D), nullptr, nullptr, at(S - W + 16)), "the workspace overlaps src") && !call(at(S), at(V), at(D), nullptr, nullptr, at(S - W)));
+    CHECK(says(call(at(S), at(V), at(D), nullptr, nullptr, at(V - W + 16)), "the workspace overlaps src_mask") && !call(at(S), at(V), at(D), nullptr, nullptr, at(V - W)));
+    CHECK(says(call(at(S), at(V), at(D), at(D + 399), nullptr, nullptr), "dst_mask overlaps dst") && !call(at(S), at(V), at(D), at(D + 400), nullptr, nullptr));
+    CHECK(says(call(at(S), at(V), at(D), nullptr, at(D + 392), nullptr), "n_regions overlaps dst") && !call(at(S), at(V), at(D), nullptr, at(D + 400), nullptr));
+    CHECK(says(call(at(S), at(V), nullptr, at(E), at(E + 96), nullptr), "n_regions overlaps dst_mask") && !call(at(S), at(V), nullptr, at(E), at(E + 104), nullptr) &&
+          !call(at(S), at(V), nullptr, at(E), at(E - 8), nullptr));
+    CHECK(says(call(at(S), at(V), at(D), nullptr, nullptr, at(D - W + 16)), "the workspace overlaps dst") && !call(at(S), at(V), at(D), nullptr, nullptr, at(D - W)));
+    CHECK(says(call(at(S), at(V), nullptr, at(E), nullptr, at(E - W + 16)), "the workspace overlaps dst_mask") && !call(at(S), at(V), nullptr, at(E), nullptr, at(E - W)));
+    CHECK(says(call(at(S), at(V), nullptr, nullptr, at(C), at(C - W + 16)), "the workspace overlaps n_regions") && !call(at(S), at(V), nullptr, nullptr, at(C), at(C - W)) &&
+          !call(at(S), at(V), nullptr, nullptr, at(C), at(C + 16)));
+    // the largest shape, and one past it: 2^30 cells of 8 bytes, every product in 64 bits
+    const uint64_t M = kRegMaxSide, N = M * M, WS = reg_workspace_bytes(M, M);
+    auto big = [&](uint64_t cols, uint64_t rows, const void* dst, const void* dm, const void* ws) {
+        return regions_refusal(8, far, at(FAR + 8 * N), cols, rows, 4, true, dst, dm, nullptr, ws);
+    };
+    CHECK(WS > 8 * N);
+    CHECK(!big(M, M, at(FAR + 9 * N), at(FAR + 13 * N), at(FAR + 14 * N)) && !big(M, M, at(FAR + 9 * N), at(FAR + 13 * N), at(FAR - WS)));
+    CHECK(says(big(M, M, at(FAR + 8 * N - 4), nullptr, nullptr), "dst overlaps src") && says(big(M, M, at(FAR + 9 * N - 4), nullptr, nullptr), "dst overlaps src_mask"));
+    CHECK(says(big(M, M, at(FAR + 9 * N), at(FAR + 13 * N - 1), nullptr), "dst_mask overlaps dst"));
+    CHECK(says(big(M, M, at(FAR + 9 * N), at(FAR + 13 * N), at(FAR - WS + 16)), "the workspace overlaps src"));
+    CHECK(says(big(M, M, at(FAR + 9 * N), at(FAR + 13 * N), at(FAR + 14 * N - 16)), "the workspace overlaps dst_mask"));
+    CHECK(says(big(M + 1, M, far, far, far), side) && says(big(M, M + 1, far, far, far), side) && says(big(1, uint64_t(1) << 63, far, far, far), side));
+}
+
 int main(int argc, char** argv) {
     const bool threads_only = argc > 1 && std::string_view(argv[1]) == "threads";
     if (!threads_only) {
         layout();
+        refusals();
         every_small_mask();
         random_rasters<uint8_t>(60, PLAIN);
         random_rasters<uint16_t>(30, PLAIN);

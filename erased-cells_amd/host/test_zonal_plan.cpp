@@ -94,8 +94,9 @@ int main() {
     bool bad = false;
     auto why = [&](int32_t nz, size_t cell, int zt, const void* p, const void* m, const void* z, size_t n, uint64_t max_cells, const void* out,
                    const void* ws, bool caller_ws = true) {
-        const char* w = stats_refusal(nz, cell, zt, p, m, z, n, max_cells, out, nz > 0 ? size_t(nz) * kRecordBytes : 0, ws, caller_ws, &bad);
-        return w ? w : "";
+        const ecv::Refusal r = stats_refusal(nz, cell, zt, p, m, z, n, max_cells, out, nz > 0 ? size_t(nz) * kRecordBytes : 0, ws, caller_ws);
+        bad = r.bad_type;
+        return r.why ? r.why : "";
     };
     CHECK(!*why(4, 2, 0, P, M, Z, 100, 0, OUT, WS) && !bad);
     CHECK(!*why(256, 8, 6, P, nullptr, Z, 100, 0, OUT, WS) && !*why(1, 1, 1, P, M, Z, 100, 0, OUT, WS));
@@ -129,8 +130,9 @@ int main() {
 
     // the broadcast
     auto bwhy = [&](int32_t nz, size_t cell, int zt, const void* z, const void* t, size_t n, const void* dst, const void* dm) {
-        const char* w = broadcast_refusal(nz, cell, zt, z, t, n, dst, dm, &bad);
-        return w ? w : "";
+        const ecv::Refusal r = broadcast_refusal(nz, cell, zt, z, t, n, dst, dm);
+        bad = r.bad_type;
+        return r.why ? r.why : "";
     };
     CHECK(!*bwhy(4, 2, 0, Z, P, 100, OUT, nullptr) && !*bwhy(4, 2, 0, Z, P, 100, OUT, WS));
     CHECK(std::strstr(bwhy(0, 0, 3, nullptr, nullptr, 100, nullptr, nullptr), "n_zones"));
@@ -151,8 +153,9 @@ int main() {
     // the table family: the same head and tail with its own cap and cap text, the kind's bound and text, the two alignments
     auto twhy = [&](int32_t nz, size_t cell, int kind, int zt, const void* p, const void* m, const void* z, size_t n, uint64_t max_cells, const void* out,
                     const void* ws, bool caller_ws = true) {
-        const char* w = ezt::table_refusal(nz, cell, kind, zt, p, m, z, n, max_cells, out, ws, caller_ws, &bad);
-        return w ? w : "";
+        const ecv::Refusal r = ezt::table_refusal(nz, cell, kind, zt, p, m, z, n, max_cells, out, ws, caller_ws);
+        bad = r.bad_type;
+        return r.why ? r.why : "";
     };
     static_assert(ezt::kMaxZones == 1 << 24, "the cap");
     CHECK(!*twhy(4, 2, 0, 0, P, M, Z, 100, 100, OUT, WS) && !bad);
@@ -191,8 +194,9 @@ int main() {
 
     // the lookup: the broadcast's refusals under the table family's cap
     auto lwhy = [&](int32_t nz, size_t cell, int zt, const void* z, const void* t, size_t n, const void* dst, const void* dm) {
-        const char* w = ezt::lookup_refusal(nz, cell, zt, z, t, n, dst, dm, &bad);
-        return w ? w : "";
+        const ecv::Refusal r = ezt::lookup_refusal(nz, cell, zt, z, t, n, dst, dm);
+        bad = r.bad_type;
+        return r.why ? r.why : "";
     };
     CHECK(!*lwhy(4, 2, 0, Z, P, 100, OUT, nullptr) && !*lwhy(257, 2, 0, Z, P, 100, OUT, WS) && !*lwhy(ezt::kMaxZones, 1, 6, Z, P, 100, OUT, WS));
     CHECK(std::strstr(bwhy(257, 2, 0, Z, P, 100, OUT, WS), "EC_ZONAL_MAX_ZONES (256)"));

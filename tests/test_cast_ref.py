@@ -10,8 +10,6 @@ own per-cell functions against the restatement — without a GPU.
    the address and undefined-behaviour sanitizers (float-cast-overflow named).  A stand-alone program: nothing of it is loaded
    into Python.
 """
-import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -19,11 +17,9 @@ import pytest
 
 import cast_ref as R
 import resample_ref
+from host_program import run_host_program
 from oracle import eco
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "erased-cells_amd", "host")
-CLANG = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
 NT, NP, NAMES = R.NT, R.NP, R.NAMES
 
 
@@ -167,19 +163,11 @@ def _same_line(answer: str, want) -> bool:
     return True
 
 
-def _build_and_run(target, stdin):
-    b = subprocess.run(["make", "-C", HOST, "-s", "-B", "CXX=" + CLANG, "SAN_CXX=" + CLANG, target], capture_output=True, text=True)
-    assert b.returncode == 0, b.stdout + b.stderr
-    return subprocess.run([os.path.join(HOST, target)], input=stdin, capture_output=True, text=True, timeout=300)
-
-
 @pytest.mark.parametrize("target", ["test_cast_cell", "test_cast_cell_san"])
 def test_the_cell_functions_from_the_header_alone(target):
     lines, expected = _lines_and_expected()
     assert len(lines) >= 10000
-    r = _build_and_run(target, "\n".join(lines) + "\n")
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
+    r = run_host_program(target, stdin="\n".join(lines) + "\n", passed=f"all lines answered: {len(lines)}")
     out = r.stdout.split("\n")
     assert out[len(lines)] == f"all lines answered: {len(lines)}"
     bad = [i for i, (g, e) in enumerate(zip(out, expected)) if not _same_line(g, e)]

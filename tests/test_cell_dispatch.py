@@ -7,21 +7,12 @@ position of a pair) and give the fallback back, the widths 1, 2, 4, 8 give the u
 maps are each other's inverse (static_assert).  Built plain and under the address and undefined-behaviour sanitizers.  A
 stand-alone program: nothing of it is loaded into Python.
 """
-import os
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "erased-cells_amd", "host")
-CLANG = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
+from host_program import run_host_program
 
 
 @pytest.mark.parametrize("target", ["test_cell_dispatch", "test_cell_dispatch_san"])
 def test_dispatcher_from_the_headers_alone(target):
-    b = subprocess.run(["make", "-C", HOST, "-s", "-B", "CXX=" + CLANG, "SAN_CXX=" + CLANG, target], capture_output=True, text=True)
-    assert b.returncode == 0, b.stdout + b.stderr
-    r = subprocess.run([os.path.join(HOST, target)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
+    r = run_host_program(target, passed="cell dispatch ok")
     assert r.stdout.strip().split("\n")[-1] == "cell dispatch ok", r.stdout[-2000:]

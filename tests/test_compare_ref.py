@@ -7,18 +7,12 @@ against the restatement — without a GPU.
    run — over the same table for all 100 pairs and 6 relations; its answers are compared with `compare_ref.relation`.  Built
    plain and under the address and undefined-behaviour sanitizers.  A stand-alone program: nothing of it is loaded into Python.
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import compare_ref as R
+from host_program import run_host_program
 from oracle import eco
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "erased-cells_amd", "host")
-CLANG = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
 
 
 def test_lattice_and_table():
@@ -76,19 +70,11 @@ def _lines_and_expected():
     return lines, expected
 
 
-def _build_and_run(target, stdin):
-    b = subprocess.run(["make", "-C", HOST, "-s", "-B", "CXX=" + CLANG, "SAN_CXX=" + CLANG, target], capture_output=True, text=True)
-    assert b.returncode == 0, b.stdout + b.stderr
-    return subprocess.run([os.path.join(HOST, target)], input=stdin, capture_output=True, text=True, timeout=300)
-
-
 @pytest.mark.parametrize("target", ["test_compare_cell", "test_compare_cell_san"])
 def test_cell_cmp_from_the_header_alone(target):
     lines, expected = _lines_and_expected()
     assert len(lines) >= 6000
-    r = _build_and_run(target, "\n".join(lines) + "\n")
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
+    r = run_host_program(target, stdin="\n".join(lines) + "\n", passed=f"all lines answered: {len(lines)}")
     out = r.stdout.split("\n")
     assert out[len(lines)] == f"all lines answered: {len(lines)}"
     bad = [i for i, (g, e) in enumerate(zip(out, expected)) if g != e]

@@ -7,11 +7,11 @@ import fractions
 import inspect
 import os
 import re
-import subprocess
 
 import pytest
 
 import distance_cases as K
+from host_program import run_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, UNSUPPORTED, ARG = 0, 2, 6
@@ -155,11 +155,4 @@ def test_the_line_header_alone_and_under_sanitizers(target):
     """erased-cells_amd/host/test_distance_line.cpp: the column sweeps and the row scans of csrc/ec_distance_line.hpp alone against
     brute force over every mask up to 4 x 4 and random ones up to 40 x 40 — a stand-alone program, built plainly and with
     -fsanitize=address,undefined"""
-    host = os.path.join(ROOT, "erased-cells_amd", "host")
-    clang = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
-    b = subprocess.run(["make", "-C", host, "-s", "-B", "CXX=" + clang, "SAN_CXX=" + clang, target], capture_output=True, text=True)
-    assert b.returncode == 0, b.stdout + b.stderr
-    r = subprocess.run([os.path.join(host, target)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
-    assert "checks passed" in r.stdout
+    run_host_program(target)

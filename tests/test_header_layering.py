@@ -38,6 +38,26 @@ def test_only_the_binop_units_compile_against_the_binop_kernels():
         assert BINOP_OWN.search(code), f"{name} includes ec_binop_kernels.hpp and uses nothing of the binop's own: include ec_tile.hpp"
 
 
+def test_the_refusal_header_stands_alone():
+    text = open(os.path.join(CSRC, "ec_refusal.hpp")).read()
+    assert INCLUDE.findall(text) == [], "ec_refusal.hpp includes no header of the project"
+    assert sorted(re.findall(r"^\s*#\s*include\s+<([^>]+)>", text, re.M)) == ["stddef.h", "stdint.h"]
+
+
+# an interval test of one's own: a predicate over two (pointer, byte count) pairs, or the comparison of two starts with two ends
+INTERVAL_TEST = re.compile(r"\bbool\s+\w+\s*\(\s*const\s+void\s*\*\s*\w+\s*,\s*size_t\s+\w+\s*,\s*const\s+void\s*\*\s*\w+\s*,\s*size_t\s+\w+\s*\)"
+                           r"|\b\w+\s*<\s*\w+\s*\+\s*\w+\s*&&\s*\w+\s*<\s*\w+\s*\+\s*\w+")
+
+
+def test_the_interval_test_is_defined_once():
+    assert len(INTERVAL_TEST.findall(re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "ec_refusal.hpp")).read()))) == 1
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.hip"))):
+        if os.path.basename(path) == "ec_refusal.hpp":
+            continue
+        found = INTERVAL_TEST.findall(re.sub(r"//[^\n]*", "", open(path).read()))
+        assert not found, f"{os.path.basename(path)} tests intervals for itself ({found[0]}): use ecv::overlap of ec_refusal.hpp"
+
+
 def test_the_focal_kernels_do_not_include_the_window_kernels():
     includes, _ = headers()["ec_focal_kernels.hpp"]
     assert "ec_window_kernels.hpp" not in includes and "ec_tile.hpp" in includes

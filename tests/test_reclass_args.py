@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import reclass_ref as Q
+from host_program import run_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, UNSUPPORTED, ARG = 0, 2, 6
@@ -259,12 +260,4 @@ def test_the_shape_the_tests_restate_is_the_kernels():
 def test_the_plan_header_alone_and_under_sanitizers(target):
     """erased-cells_amd/host/test_reclass_plan.cpp: csrc/ec_reclass_plan.hpp's thresholds against the predicate for every narrow
     cell, the refusals and the record — a stand-alone program, built plainly and with -fsanitize=address,undefined"""
-    import subprocess
-    host = os.path.join(ROOT, "erased-cells_amd", "host")
-    clang = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
-    b = subprocess.run(["make", "-C", host, "-s", "-B", "CXX=" + clang, "SAN_CXX=" + clang, target], capture_output=True, text=True)
-    assert b.returncode == 0, b.stdout + b.stderr
-    r = subprocess.run([os.path.join(host, target)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
-    assert "checks passed" in r.stdout
+    run_host_program(target)

@@ -7,11 +7,11 @@ with the address and undefined-behaviour sanitizers, and with the thread sanitiz
 import inspect
 import os
 import re
-import subprocess
 
 import pytest
 
 import regions_cases as K
+from host_program import run_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, UNSUPPORTED, ARG = 0, 2, 6
@@ -174,11 +174,4 @@ def test_the_cell_header_alone_and_under_sanitizers(target, args):
     """erased-cells_amd/host/test_regions_cell.cpp: the phases of csrc/ec_regions_cell.hpp alone against a flood fill over every mask up
     to 4 x 4 and random rasters up to 40 x 40, with stale loads, and the seam unions from up to 16 threads — a stand-alone program, built
     plainly, with -fsanitize=address,undefined and, for the threads, with -fsanitize=thread"""
-    host = os.path.join(ROOT, "erased-cells_amd", "host")
-    clang = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
-    b = subprocess.run(["make", "-C", host, "-s", "-B", "CXX=" + clang, "SAN_CXX=" + clang, "TSAN_CXX=" + clang, target], capture_output=True, text=True)
-    assert b.returncode == 0, b.stdout + b.stderr
-    r = subprocess.run([os.path.join(host, target)] + args, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
-    assert "checks passed, 0 failed" in r.stdout
+    run_host_program(target, *args, timeout=600, passed="checks passed, 0 failed")

@@ -11,10 +11,9 @@ import subprocess
 import pytest
 
 import stats_ref as R
+from host_program import run_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "erased-cells_amd", "host")
-CLANG = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
 
 
 @pytest.fixture(scope="module")
@@ -223,21 +222,12 @@ def test_bad_arguments_are_refused_without_a_device(ec):
     assert L.ec_sharded_stats(None, R.U8, p1, None, n1, C.byref(out)) == E.EC_ERR_ARG and b"null shard group" in L.ec_last_error_string()
 
 
-def _build_and_run(target):
-    b = subprocess.run(["make", "-C", HOST, "-s", "-B", "CXX=" + CLANG, "SAN_CXX=" + CLANG, target], capture_output=True, text=True)
-    assert b.returncode == 0, b.stdout + b.stderr
-    return subprocess.run([os.path.join(HOST, target)], capture_output=True, text=True, timeout=300)
-
-
 def test_fold_header_alone():
-    r = _build_and_run("test_stats_fold")
-    assert r.returncode == 0 and "all checks passed" in r.stdout, r.stdout + r.stderr
+    run_host_program("test_stats_fold", passed="all checks passed")
 
 
 def test_fold_header_under_the_address_and_undefined_behaviour_sanitizers():
-    r = _build_and_run("test_stats_fold_san")
-    assert r.returncode == 0 and "all checks passed" in r.stdout, r.stdout + r.stderr
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr
+    run_host_program("test_stats_fold_san", passed="all checks passed")
 
 
 def test_offset_data_loses_its_variance_without_the_pivot():

@@ -12,6 +12,7 @@ import pytest
 import stats_ref as R
 import zonal_ref as Z
 import zonal_table_ref as ZT
+from host_program import run_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, UNSUPPORTED, ARG = 0, 2, 6
@@ -223,12 +224,4 @@ def test_the_python_refusals(ec):
 def test_the_cell_header_alone_and_under_sanitizers(target):
     """erased-cells_amd/host/test_zonal_table_cell.cpp: csrc/ec_zonal_table_cell.hpp against 128-bit arithmetic — a stand-alone program,
     built plainly, with -fsanitize=address,undefined and with -fsanitize=thread"""
-    import subprocess
-    host = os.path.join(ROOT, "erased-cells_amd", "host")
-    clang = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
-    b = subprocess.run(["make", "-C", host, "-s", "-B", "CXX=" + clang, "SAN_CXX=" + clang, "TSAN_CXX=" + clang, target], capture_output=True, text=True)
-    assert b.returncode == 0, b.stdout + b.stderr
-    r = subprocess.run([os.path.join(host, target)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
-    assert "checks passed" in r.stdout
+    run_host_program(target)

@@ -8,7 +8,7 @@ scipy.ndimage.distance_transform_edt once (one CPU thread) and `within(cols, 7)`
 `dilate((7, 7))` — they compute different shapes.  The two kernels of a call are told apart by a kernel trace of this tool
 (`--trace`: one call per configuration, in the order printed), not here.
 
-    python tools/distance_bench.py [--blocks 5] [--calls 3] [--out profiles/distance/distance_times.md] [--trace]
+    python tools/distance_bench.py [--blocks 5] [--calls 3] [--sides 64] [--workspace caller] [--out profiles/distance/distance_times.md] [--trace]
 """
 import argparse
 import os
@@ -35,6 +35,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--calls", type=int, default=3, help="calls per timed block")
+    ap.add_argument("--sides", type=int, nargs="+", help="square rasters of these sides instead of the three shapes (a small one times the call's fixed cost)")
+    ap.add_argument("--workspace", choices=("pool", "caller"), default="pool", help="the library's pool, or one block of the caller's")
     ap.add_argument("--out")
     ap.add_argument("--trace", action="store_true", help="one call per configuration and nothing else: for a kernel trace")
     args = ap.parse_args()
@@ -82,19 +84,22 @@ def main():
             t.append(e0.elapsed_time(e1) / args.calls)
         return statistics.median(t), min(t), max(t)
 
-    say(f"ec_distance, pooled workspace; ms per call: median of {args.blocks} blocks of {args.calls} calls (least - greatest); floor = algorithmic bytes at 8 TB/s")
+    shapes = [(s, s) for s in args.sides] if args.sides else SHAPES
+    say(f"ec_distance, workspace: {args.workspace}; ms per call: median of {args.blocks} blocks of {args.calls} calls (least - greatest); floor = algorithmic bytes at 8 TB/s")
     say()
     say("| cols x rows | targets | form | ms | floor ms | time / floor | Mcells/s |")
     say("|---|---|---|---|---|---|---|")
-    for cols, rows in SHAPES:
+    for cols, rows in shapes:
         n = cols * rows
         dst = ec.CellBuffer.empty(n, ec.Float64)
         dm = ec.Mask.empty(n)
+        block = ec.CellBuffer.empty(L.ec_distance_workspace_bytes(cols, rows), ec.UInt8) if args.workspace == "caller" else None
+        ws = block.mem.ptr if block else None
         for dname, pct in DENSITIES:
             masks = masks_of(cols, rows, pct)
             for fname, ct, values, want_mask in FORMS:
                 def call(k, ct=ct, values=values, masks=masks):
-                    chk(L.ec_distance(masks[k].mem.ptr, cols, rows, 0xFFFFFFFF if values else 49, ct, dst.mem.ptr if values else None, dm.mem.ptr, None, stream))
+                    chk(L.ec_distance(masks[k].mem.ptr, cols, rows, 0xFFFFFFFF if values else 49, ct, dst.mem.ptr if values else None, dm.mem.ptr, ws, stream))
                 if args.trace:
                     call(0)
                     torch.cuda.synchronize()
@@ -123,7 +128,7 @@ def main():
                 med, lo, hi = timed(fn)
                 rows_.append(f"{name} {med:.2f} ms ({lo:.2f} - {hi:.2f})")
             say(f"| {cols} x {rows} | 1 % | " + " ; ".join(rows_) + " |")
-        del dst, dm
+        del dst, dm, block
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")

@@ -41,6 +41,7 @@ def main():
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--calls", type=int, default=3, help="calls per timed block")
     ap.add_argument("--sides", type=int, nargs="+", default=[4096, 16384])
+    ap.add_argument("--workspace", choices=("pool", "caller"), default="pool", help="the library's pool, or one block of the caller's")
     ap.add_argument("--out")
     ap.add_argument("--trace", action="store_true", help="one call per configuration and nothing else: for a kernel trace")
     args = ap.parse_args()
@@ -89,7 +90,7 @@ def main():
             t.append(e0.elapsed_time(e1) / args.calls)
         return statistics.median(t), min(t), max(t)
 
-    say(f"ec_regions, u8 classes, DENSE, labels + mask bytes + K, pooled workspace; ms per call: median of {args.blocks} blocks of {args.calls} calls "
+    say(f"ec_regions, u8 classes, DENSE, labels + mask bytes + K, workspace: {args.workspace}; ms per call: median of {args.blocks} blocks of {args.calls} calls "
         "(least - greatest); floor = 1 B read + 5 B written per cell at 8 TB/s")
     say()
     say("| side | pattern | connectivity | min_cells | K | ms | floor ms | time / floor | Mcells/s |")
@@ -98,12 +99,14 @@ def main():
         n = side * side
         dst, dm, k = ec.CellBuffer.empty(n, ec.Int32), ec.Mask.empty(n), ec.CellBuffer.empty(1, ec.UInt64)
         floor = n * 6 / PEAK_BYTES_PER_S * 1e3
+        block = ec.CellBuffer.empty(L.ec_regions_workspace_bytes(side, side), ec.UInt8) if args.workspace == "caller" else None
+        ws = block.mem.ptr if block else None
         for pattern in PATTERNS:
             src = raster(side, pattern)
             for c in (4, 8):
                 for min_cells in (0, 20):
                     def call(c=c, min_cells=min_cells):
-                        chk(L.ec_regions(ec.UInt8, src.mem.ptr, None, side, side, c, 1, min_cells, dst.mem.ptr, dm.mem.ptr, k.mem.ptr, None, stream))
+                        chk(L.ec_regions(ec.UInt8, src.mem.ptr, None, side, side, c, 1, min_cells, dst.mem.ptr, dm.mem.ptr, k.mem.ptr, ws, stream))
                     if args.trace:
                         call()
                         torch.cuda.synchronize()
@@ -122,7 +125,7 @@ def main():
                 torch.cuda.synchronize()
                 say(f"| 4096 | {pattern} | 4 | 0 | {count} | scipy.ndimage.label per class, one CPU thread: {cpu * 1e3:.0f} | | | {n / cpu / 1e6:.0f} | K equal: {count == int(k.to_numpy()[0])}")
             del src
-        del dst, dm, k
+        del dst, dm, k, block
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
